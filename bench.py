@@ -11,8 +11,14 @@ scaling of the per-GPU work is NOT used: total work per step is fixed, so scalin
 4096 spp, depth 16) measure the other BASELINE configs the same way; --integrator 1 the HEAD
 integrator (kernel.cu:217-415).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with:
+A plain run sets up, warms up, times --steps renders and prints ONE JSON line on rank 0 with:
   value      = Msamples/s, whole job (pixel samples per second)
+  ms_per_step = wall milliseconds per timed step
+--dump-outputs DIR also writes the last timed step's framebuffer (what a caller of the render path
+receives) as DIR/image.npy, float32; the inputs are fixed (procedural scene, seed 1234), so two builds
+can be compared value for value.
+
+--full adds what takes runs of its own (each still switched off by --no-count / --no-cpu-baseline):
   roofline   = measured memory-side bytes per launch (rocprof, calibrated; from profiles/traffic.json
                when it matches this kernel) / this run's kernel time vs 8 TB/s HBM, with the binding
                pipes beside it
@@ -501,6 +507,23 @@ def launch_ranks(n, backend, argv=None):
     return status
 
 
+DUMP_MAX_BYTES = 64 * 10**6   # --dump-outputs writes at most this much
+DUMP_SAMPLE_SEED = 1234
+
+
+def dump_outputs(dirpath, img):
+    """Write the framebuffer (H x W x 3, float32) as dirpath/image.npy.  An image above DUMP_MAX_BYTES is
+    written as an (n, 3) sample of its pixels: the same sorted, seeded choice of pixel indices on every run."""
+    os.makedirs(dirpath, exist_ok=True)
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    if img.nbytes > DUMP_MAX_BYTES:
+        flat = img.reshape(-1, 3)
+        n = DUMP_MAX_BYTES // (3 * img.itemsize)
+        pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(len(flat), size=n, replace=False))
+        img = flat[pick]
+    np.save(os.path.join(dirpath, "image.npy"), img)
+
+
 def KERNEL_NAME(args):
     if args.flags & 1:   # PT_FLAG_REFERENCE_TRAVERSAL: the tile kernel
         return "render_tiles"
@@ -520,6 +543,11 @@ def main():
     ap.add_argument("--bounces", type=int, default=None)
     ap.add_argument("--integrator", type=int, default=0)
     ap.add_argument("--flags", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the counting pass (roofline blocks) and the CPU baseline; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's framebuffer to DIR/image.npy (float32; a fixed seeded sample of "
+                         "its pixels when the whole image exceeds %d MB)" % (DUMP_MAX_BYTES // 10**6))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--cpu-threads", type=int, default=host_cores())
@@ -544,6 +572,11 @@ def main():
             setattr(args, k, v)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    # a plain run times the steps only; the counting pass and the CPU baseline are --full's
+    if not args.full:
+        args.no_count = args.no_cpu_baseline = True
     # PT_BENCH_BACKEND=gloo rehearses the multi-process path where RCCL cannot run (several ranks
     # on one GPU: the device index wraps over the visible GPUs when there are fewer than ranks)
     backend = os.environ.get("PT_BENCH_BACKEND", "nccl")
@@ -652,6 +685,8 @@ def main():
     if rank == 0:
         img = fb.cpu().numpy()
         finite = bool(np.isfinite(img).all())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, img)
         ms_step = elapsed / args.steps * 1e3
         kms = float(np.mean(kernel_ms))
         roof = roofline(counts, kms, W, H, args, world) if counts is not None else None

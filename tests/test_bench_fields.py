@@ -171,6 +171,31 @@ def test_plain_multi_gpu_bench_fails_loudly_without_enough_gpus():
     assert "RCCL needs one GPU per rank" in r.stderr
 
 
+def test_dump_outputs_writes_the_framebuffer_as_float32(tmp_path):
+    import numpy as np
+    img = np.random.default_rng(3).random((24, 40, 3)).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "new" / "dir"), img)
+    got = np.load(str(tmp_path / "new" / "dir" / "image.npy"))
+    assert got.dtype == np.float32 and got.shape == img.shape
+    assert got.tobytes() == img.tobytes()
+
+
+def test_dump_outputs_samples_an_image_above_the_cap(tmp_path, monkeypatch):
+    """Above DUMP_MAX_BYTES the file holds a pixel sample: within the cap, and the same pixels on every run."""
+    import numpy as np
+    assert bench.DUMP_MAX_BYTES <= 64 * 10**6
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1200)   # 100 pixels of 3 x float32
+    img = np.arange(24 * 40 * 3, dtype=np.float32).reshape(24, 40, 3)
+    bench.dump_outputs(str(tmp_path / "a"), img)
+    bench.dump_outputs(str(tmp_path / "b"), img)
+    a, b = np.load(str(tmp_path / "a" / "image.npy")), np.load(str(tmp_path / "b" / "image.npy"))
+    assert a.dtype == np.float32 and a.shape == (100, 3) and a.nbytes <= 1200
+    assert a.tobytes() == b.tobytes()
+    # whole pixels of the image, each at most once, in image order
+    pix = (a[:, 0] / 3).astype(np.int64)
+    assert np.array_equal(a, img.reshape(-1, 3)[pix]) and np.all(np.diff(pix) > 0)
+
+
 def test_shard_launch_inherits_the_full_frame_limiter(tmp_path):
     """At N > 1 the shard launch's profile holds only its bytes; bound still names the full-frame launch's limiter
     (same kernel on 1/N of the tiles), without the full frame's per-launch VALU pricing."""

@@ -19,7 +19,7 @@ for r in $(seq ${ROUNDS:-2}); do
     label=${cfg%%:*}
     envs=${cfg#*:}
     tag=${label}_$r
-    timeout -k 10 400 env ${envs//,/ } python3 bench.py --steps ${STEPS:-4} --warmup 1 --no-cpu-baseline ${NOCOUNT:---no-count} ${BENCH_ARGS} \
+    timeout -k 10 400 env ${envs//,/ } python3 bench.py --full --steps ${STEPS:-4} --warmup 1 --no-cpu-baseline ${NOCOUNT:---no-count} ${BENCH_ARGS} \
         > $OUT/$tag.json 2> $OUT/$tag.err || { echo "bench-fail $tag" > $OUT/done.txt; tail -5 $OUT/$tag.err; exit 1; }
     echo "$tag $(python3 -c "
 import json;d=json.load(open('$OUT/$tag.json'));r=d.get('roofline') or {}

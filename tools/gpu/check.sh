@@ -10,7 +10,7 @@ if [ -z "$NOTEST" ]; then
       > $OUT/pytest_gpu.log 2>&1 || { echo pytest-fail > $OUT/done.txt; tail -30 $OUT/pytest_gpu.log; exit 1; }
   tail -1 $OUT/pytest_gpu.log
 fi
-timeout -k 10 300 python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err \
+timeout -k 10 300 python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err \
     || { echo bench-fail > $OUT/done.txt; tail -20 $OUT/bench.err; exit 1; }
 python3 -c "
 import json;d=json.load(open('$OUT/bench.json'));r=d['roofline'] or {}

@@ -8,7 +8,7 @@ OUT=gpurun_out/${TAG:-configs}
 mkdir -p $OUT
 for c in ${CONFIGS:-C2 C5}; do
   mkdir -p $OUT/$c
-  B="python3 bench.py --config $c --steps ${STEPS:-2} --warmup 1 ${BENCH_ARGS}"
+  B="python3 bench.py --full --config $c --steps ${STEPS:-2} --warmup 1 ${BENCH_ARGS}"
   timeout -k 10 ${TLIM:-300} $B > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { echo "bench-fail $c" > $OUT/done.txt; exit 1; }
   [ "$PROF" = "0" ] && continue
   timeout -k 10 ${TLIM:-300} rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$c/ktrace -o run -- \

@@ -8,6 +8,6 @@ export TMPDIR=/tmp
 OUT=gpurun_out/${TAG:-dist}
 mkdir -p $OUT
 PT_BENCH_BACKEND=gloo timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 3 --warmup 1 ${BENCH_ARGS} \
+    --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 3 --warmup 1 ${BENCH_ARGS} \
     > $OUT/gloo2.json 2> $OUT/gloo2.err || { echo "gloo fail" > $OUT/done.txt; exit 1; }
 echo ok > $OUT/done.txt

@@ -14,7 +14,7 @@ i=0
 for kv in ${SWEEP:--}; do
   i=$((i+1))
   envs=""; [ "$kv" != "-" ] && envs=$(echo $kv | tr ',' ' ')
-  env $envs timeout -k 10 300 python3 bench.py --integrator 1 --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline ${BENCH_ARGS} \
+  env $envs timeout -k 10 300 python3 bench.py --full --integrator 1 --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline ${BENCH_ARGS} \
       > $OUT/b_$i.json 2> $OUT/b_$i.err || { echo "bench failed: $kv" > $OUT/done.txt; exit 1; }
   echo "$kv $(python3 -c "
 import json;d=json.load(open('$OUT/b_$i.json'));r=d['roofline'] or {}

@@ -18,7 +18,7 @@ rm -f $OUT/sweep.jsonl
 PT_PARITY_SWEEP=2000 PT_PARITY_SWEEP_LOG=$OUT/sweep.jsonl timeout -k 10 900 python3 -u -m pytest tests/test_gpu_parity_sweep.py \
     -m gpu -q --timeout 300 --timeout-method thread > $OUT/sweep.log 2>&1 || { echo sweep-fail; tail -30 $OUT/sweep.log; exit 1; }
 tail -1 $OUT/sweep.log
-PT_BENCH_BACKEND=gloo timeout -k 10 600 python3 bench.py --gpus 4 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/plain_gpus4_gloo.json \
+PT_BENCH_BACKEND=gloo timeout -k 10 600 python3 bench.py --full --gpus 4 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/plain_gpus4_gloo.json \
     2> $OUT/plain_gpus4_gloo.err || { echo gpus4-fail; tail -20 $OUT/plain_gpus4_gloo.err; exit 1; }
 echo "plain --gpus 4 (gloo): $(python3 -c "import json;d=json.load(open('$OUT/plain_gpus4_gloo.json'));print(d['value'], d['n_gpus'], d['image_finite'], d['config'].get('rank_launcher'))")"
 echo done

@@ -15,7 +15,7 @@ for n in 1 2 4 8; do
   echo "debug build, shard 0 of $n: $(python3 -c "import json;d=json.load(open('$OUT/shard_$n.json'));print(d['value'], d['image_finite'])")"
 done
 for r in 1 2 3; do
-  timeout -k 10 300 python3 bench.py --steps 10 --warmup 5 --no-cpu-baseline > $OUT/bench_$r.json 2> $OUT/bench_$r.err || { echo bench-fail; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --steps 10 --warmup 5 --no-cpu-baseline > $OUT/bench_$r.json 2> $OUT/bench_$r.err || { echo bench-fail; exit 1; }
   echo "product bench $r: $(python3 -c "import json;d=json.load(open('$OUT/bench_$r.json'));print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['bound'])")"
 done
 echo done

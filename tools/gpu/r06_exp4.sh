@@ -12,7 +12,7 @@ tail -1 $OUT/pytest_oct.log
 for r in 1 2 3; do
   for v in oct leafkey base; do
     lib=variants/$v/libptamd.so; [ $v = base ] && lib=""
-    PT_LIB=$lib timeout -k 10 300 python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline > $OUT/${v}_$r.json 2> $OUT/${v}_$r.err \
+    PT_LIB=$lib timeout -k 10 300 python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline >$OUT/${v}_$r.json 2> $OUT/${v}_$r.err \
         || { echo "bench-fail $v $r"; tail -5 $OUT/${v}_$r.err; exit 1; }
     echo "$v $r $(python3 -c "import json;d=json.load(open('$OUT/${v}_$r.json'));r=d['roofline'];print(d['value'], d['ms_per_step'], r['node_fetches'], r['tri_tests'])")" | tee -a $OUT/summary.txt
   done
@@ -29,7 +29,7 @@ done
 for cfg in C2; do
   for v in oct base; do
     lib=variants/$v/libptamd.so; [ $v = base ] && lib=""
-    PT_LIB=$lib timeout -k 10 300 python3 bench.py --config $cfg --steps 6 --warmup 2 --no-cpu-baseline > $OUT/${v}_$cfg.json 2> $OUT/${v}_$cfg.err \
+    PT_LIB=$lib timeout -k 10 300 python3 bench.py --full --config $cfg --steps 6 --warmup 2 --no-cpu-baseline > $OUT/${v}_$cfg.json 2> $OUT/${v}_$cfg.err \
         || { echo "bench-fail $v $cfg"; exit 1; }
     echo "$v $cfg $(python3 -c "import json;d=json.load(open('$OUT/${v}_$cfg.json'));print(d['value'], d['ms_per_step'])")" | tee -a $OUT/summary.txt
   done

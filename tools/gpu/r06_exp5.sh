@@ -10,7 +10,7 @@ tail -1 $OUT/pytest_tri64.log
 for r in 1 2 3; do
   for v in tri64 base; do
     lib=variants/$v/libptamd.so; [ $v = base ] && lib=""
-    PT_LIB=$lib timeout -k 10 300 python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline > $OUT/${v}_$r.json 2> $OUT/${v}_$r.err \
+    PT_LIB=$lib timeout -k 10 300 python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline >$OUT/${v}_$r.json 2> $OUT/${v}_$r.err \
         || { echo "bench-fail $v $r"; tail -5 $OUT/${v}_$r.err; exit 1; }
     echo "$v $r $(python3 -c "import json;d=json.load(open('$OUT/${v}_$r.json'));r=d['roofline'];print(d['value'], d['ms_per_step'], r['node_fetches'], r['tri_tests'])")" | tee -a $OUT/summary.txt
   done

@@ -25,7 +25,7 @@ for v in node256 base; do
       || { echo "pmc-fail $v"; exit 1; }
 done
 for coll in reduce gather; do
-  PT_BENCH_BACKEND=gloo timeout -k 10 600 python3 bench.py --gpus 8 --steps 2 --warmup 1 --no-cpu-baseline --collective $coll \
+  PT_BENCH_BACKEND=gloo timeout -k 10 600 python3 bench.py --full --gpus 8 --steps 2 --warmup 1 --no-cpu-baseline --collective $coll \
       > $OUT/plain_gpus8_gloo_$coll.json 2> $OUT/plain_gpus8_gloo_$coll.err || { echo "gpus8-fail $coll"; tail -20 $OUT/plain_gpus8_gloo_$coll.err; exit 1; }
   echo "plain --gpus 8 gloo $coll: $(python3 -c "import json;d=json.load(open('$OUT/plain_gpus8_gloo_$coll.json'));print(d['value'], d['n_gpus'], d['image_finite'], d['config'].get('rank_launcher'), d['config'].get('collective'))")"
 done

@@ -15,6 +15,6 @@ TAG=r06_final/shardsim_C3 bash tools/gpu/shardsim.sh || { echo shardsim-fail > $
 TAG=r06_final/shardsim_C4 STEPS=2 BENCH_ARGS="--config C4" bash tools/gpu/shardsim.sh || { echo shardsim4-fail > $OUT/done_b2.txt; exit 1; }
 echo shardsim ok
 timeout -k 10 300 python3 tools/gpu/host_rate.py > $OUT/host_rate.json 2> $OUT/host_rate.err || { echo hostrate-fail > $OUT/done_b2.txt; exit 1; }
-PT_BENCH_BACKEND=gloo timeout -k 10 300 python3 bench.py --gpus 2 --steps 4 --warmup 2 --no-cpu-baseline \
+PT_BENCH_BACKEND=gloo timeout -k 10 300 python3 bench.py --full --gpus 2 --steps 4 --warmup 2 --no-cpu-baseline \
     > $OUT/plain_gpus2_gloo.json 2> $OUT/plain_gpus2_gloo.err || { echo plain-fail > $OUT/done_b2.txt; exit 1; }
 echo ok > $OUT/done_b2.txt

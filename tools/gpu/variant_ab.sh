@@ -15,7 +15,7 @@ fi
 for r in $(seq ${ROUNDS:-2}); do
   for lib in "$V" ""; do
     tag=$([ -n "$lib" ] && echo var || echo base)_$r
-    PT_LIB=$lib timeout -k 10 300 python3 bench.py --steps ${STEPS:-4} --warmup 1 --no-cpu-baseline ${BENCH_ARGS} > $OUT/$tag.json 2> $OUT/$tag.err \
+    PT_LIB=$lib timeout -k 10 300 python3 bench.py --full --steps ${STEPS:-4} --warmup 1 --no-cpu-baseline ${BENCH_ARGS} > $OUT/$tag.json 2> $OUT/$tag.err \
         || { echo "bench-fail $tag" > $OUT/done.txt; tail -5 $OUT/$tag.err; exit 1; }
     echo "$tag $(python3 -c "
 import json;d=json.load(open('$OUT/$tag.json'));r=d['roofline'] or {}

@@ -16,7 +16,7 @@ RUNS=${RUNS:-var5:V:5 base5:-:5 var4:V:4 var5b:V:5 base5b:-:5 var4b:V:4}
 for run in $RUNS; do
   IFS=: read name lib wv <<< "$run"
   [ "$lib" = "V" ] && lib=$V || lib=""
-  PT_LIB=$lib PT_WF_MIN_WAVES=$wv timeout -k 10 300 python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline ${BENCH_ARGS} \
+  PT_LIB=$lib PT_WF_MIN_WAVES=$wv timeout -k 10 300 python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline ${BENCH_ARGS} \
       > $OUT/$name.json 2> $OUT/$name.err || { echo "bench-fail $name" > $OUT/done.txt; tail -5 $OUT/$name.err; exit 1; }
   echo "$name $(python3 -c "
 import json;d=json.load(open('$OUT/$name.json'));r=d['roofline'] or {}
