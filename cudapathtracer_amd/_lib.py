@@ -126,6 +126,15 @@ SIGNATURES = {
     "pt_group_destroy": (None, [C.c_void_p]),
     "pt_render_multi": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(Params), C.POINTER(Camera), C.c_void_p,
                                   C.POINTER(Stats)]),
+    "pt_accum_create": (C.c_void_p, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.POINTER(C.c_int)]),
+    "pt_accum_add": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "pt_accum_samples": (C.c_int64, [C.c_void_p]),
+    "pt_accum_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_accum_save": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "pt_accum_load": (C.c_void_p, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]),
+    "pt_accum_file_info": (C.c_int, [C.c_char_p, C.POINTER(Params), C.POINTER(Camera), C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_uint64)]),
+    "pt_accum_destroy": (None, [C.c_void_p]),
     "pt_destroy": (None, [C.c_void_p]),
 }
 

@@ -274,6 +274,29 @@ class Renderer:
         L.check(L.lib().pt_render_wait(self._h, C.byref(st)))
         return st.as_dict()
 
+    def accumulator(self, cam, width, height, bounces=3, integrator=0, seed=1234, flags=0, shard_index=0,
+                    shard_count=1, pixel_order=0, tile=0):
+        """A resumable render of this shard (pt_accum_create): everything but the sample count is fixed
+        here; Accumulator.add(spp) then renders the next spp samples of every pixel.  `tile`: the shard
+        tile size, one int or (tile_w, tile_h); 0 = 8."""
+        tw, th = (tile, tile) if np.isscalar(tile) else tile
+        p = self.params(width, height, 0, bounces, integrator, seed, flags, shard_index, shard_count, pixel_order,
+                        tw, th)
+        err = C.c_int(0)
+        h = L.lib().pt_accum_create(self._h, C.byref(p), C.byref(cam), C.byref(err))
+        if not h:
+            L.check(err.value if err.value != 0 else L.PT_E_HIP)
+        return Accumulator(self, h, p)
+
+    def load_accumulator(self, path):
+        """The accumulator a checkpoint file holds (pt_accum_load), on this renderer: the file names every
+        fixed parameter, the camera and the scene it was written for (PtError PT_E_SCENE if not this one)."""
+        err = C.c_int(0)
+        h = L.lib().pt_accum_load(self._h, str(path).encode(), C.byref(err))
+        if not h:
+            L.check(err.value if err.value != 0 else L.PT_E_IO)
+        return Accumulator(self, h, accum_file_info(path)["params"])
+
     def tonemap(self, img):
         """Output step on the GPU: (H, W, 3) float32 mean image -> int32 codes equal to
         pt_tonemap_u8 (kernel.cu:763-778) per channel."""
@@ -320,6 +343,73 @@ class Renderer:
         L.check(L.lib().pt_trace(self._h, n, rays.ctypes.data, tri.ctypes.data, t.ctypes.data,
                                  L.PT_FLAG_REFERENCE_BVH if reference_bvh else 0))
         return tri, t
+
+
+def accum_file_info(path):
+    """Header of a checkpoint file (pt_accum_file_info, host-only): dict of params (spp = 0), camera,
+    samples done and the scene digest."""
+    p, cam, n, dg = L.Params(), L.Camera(), C.c_int64(0), C.c_uint64(0)
+    L.check(L.lib().pt_accum_file_info(str(path).encode(), C.byref(p), C.byref(cam), C.byref(n), C.byref(dg)))
+    return dict(params=p, camera=cam, samples=int(n.value), scene_digest=int(dg.value))
+
+
+class Accumulator:
+    """Per-pixel XORWOW state and f64 running mean of one shard, kept on the renderer's device between
+    passes (the reference's randState_device / imgBuffer_device, kernel.cu:527-553): a render built up
+    with add() equals Renderer.render of the same total in every bit.  Close it before its renderer."""
+
+    def __init__(self, renderer, handle, params):
+        self._renderer = renderer   # (keeps the context alive as long as the accumulator)
+        self._h = handle
+        self.params = params
+
+    def close(self):
+        if self._h:
+            L.lib().pt_accum_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, spp, d_out_ptr=None, stream_ptr=None):
+        """Render the next spp samples of every pixel; returns this pass's stats dict.  d_out_ptr: a device
+        buffer of W*H*3 float32 that receives this shard's fp32 mean (other pixels untouched)."""
+        st = L.Stats()
+        L.check(L.lib().pt_accum_add(self._h, int(spp), None if d_out_ptr is None else C.c_void_p(int(d_out_ptr)),
+                                     None if stream_ptr is None else C.c_void_p(int(stream_ptr)), C.byref(st)))
+        return st.as_dict()
+
+    @property
+    def samples(self):
+        return int(L.lib().pt_accum_samples(self._h))
+
+    def _shape(self):
+        p = self.params
+        return (p.height * p.width, 3) if p.pixel_order == L.PT_ORDER_MORTON else (p.height, p.width, 3)
+
+    def image(self):
+        """The fp32 mean image as Renderer.render returns it (pixels outside the shard 0)."""
+        out = np.zeros(self._shape(), dtype=np.float32)
+        L.check(L.lib().pt_accum_read(self._h, out.ctypes.data, None))
+        return out
+
+    def mean64(self):
+        """The f64 running mean itself (the reference's imgBuffer)."""
+        out = np.zeros(self._shape(), dtype=np.float64)
+        L.check(L.lib().pt_accum_read(self._h, None, out.ctypes.data))
+        return out
+
+    def save(self, path):
+        L.check(L.lib().pt_accum_save(self._h, str(path).encode()))
 
 
 class Group:

@@ -16,6 +16,14 @@
 // --tri-counts out.csv                    per-triangle test counts (the reference's out.csv,
 //                                         kernel.cu:742-750); --reference-walk makes them the
 //                                         reference's own (its exact trace() sequence)
+// --checkpoint FILE                       render through an accumulator (pt_accum_*) and write its state
+//                                         (per-pixel XORWOW + f64 mean) to FILE after rendering
+// --resume FILE                           continue the render FILE holds: every fixed parameter and the
+//                                         camera come from the file, --spp is the samples to ADD; an
+//                                         option that contradicts the file is an error
+// --pass-spp K                            render in passes of K samples (the reference's progressive
+//                                         loop, kernel.cu:709-736), rewriting --out / --pfm /
+//                                         --checkpoint after each and printing its "sample %d" line
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -42,7 +50,8 @@ struct Obj {
             "              [--width W] [--height H] [--spp N | --num-samples N] [--bounces D]\n"
             "              [--integrator unidir|head] [--seed S] [--cam X,Y,Z] [--dist D] [--focal F]\n"
             "              [--radius R] [--gpus N] [--out image.ppm] [--pfm image.pfm] [--quiet]\n"
-            "              [--tri-counts out.csv [--reference-walk]] [--morton] [--tile WxH]\n");
+            "              [--tri-counts out.csv [--reference-walk]] [--morton] [--tile WxH]\n"
+            "              [--checkpoint FILE] [--resume FILE] [--pass-spp K]\n");
     exit(2);
 }
 
@@ -89,9 +98,12 @@ int main(int argc, char** argv)
     pt_camera cam{{0, 1, 3}, 1, 3, 0, 0, 0};                      // kernel.cu:642-648
     int gpus = 1;
     bool quiet = false, ref_walk = false;
-    std::string tri_csv;
+    std::string tri_csv, checkpoint, resume;
+    int pass_spp = 0;
+    std::vector<std::string> given;   // the options on the command line (a resumed file may contradict them)
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
+        given.push_back(a);
         auto next = [&]() -> std::string {
             if (i + 1 >= argc) usage(("missing value for " + a).c_str());
             return argv[++i];
@@ -123,6 +135,9 @@ int main(int argc, char** argv)
         else if (a == "--tile") {
             if (sscanf(next().c_str(), "%dx%d", &p.tile_w, &p.tile_h) != 2) usage("--tile is WxH");
         }
+        else if (a == "--checkpoint") checkpoint = next();
+        else if (a == "--resume") resume = next();
+        else if (a == "--pass-spp") { pass_spp = atoi(next().c_str()); if (pass_spp < 1) usage("--pass-spp must be >= 1"); }
         else if (a == "-h" || a == "--help") usage(nullptr);
         else usage(("unknown option " + a).c_str());
     }
@@ -135,6 +150,39 @@ int main(int argc, char** argv)
     if (ref_walk) p.flags |= PT_FLAG_REFERENCE_TRAVERSAL | PT_FLAG_NO_PRIMARY_CACHE | PT_FLAG_NO_DEAD_PATH_SKIP;
     cam.pxl_width = p.width;
     cam.pxl_height = p.height;
+    const bool accumulate = !checkpoint.empty() || !resume.empty() || pass_spp > 0;
+    if (accumulate && gpus != 1) usage("--checkpoint / --resume / --pass-spp need --gpus 1 (one accumulator per shard)");
+    if (accumulate && (!tri_csv.empty() || ref_walk)) usage("--tri-counts and --reference-walk do not accumulate");
+    if (!resume.empty()) {
+        // the file fixes the render; what the command line says as well must say the same
+        pt_params fp;
+        pt_camera fc;
+        int64_t done = 0;
+        if (pt_accum_file_info(resume.c_str(), &fp, &fc, &done, nullptr) != PT_OK) return die("--resume");
+        auto has = [&](const char* o) { for (const std::string& g : given) if (g == o) return true; return false; };
+        auto conflict = [&](const char* o, bool differs) {
+            if (has(o) && differs) {
+                fprintf(stderr, "pt_cli: %s contradicts the resumed file %s\n", o, resume.c_str());
+                exit(2);
+            }
+        };
+        conflict("--width", p.width != fp.width);
+        conflict("--height", p.height != fp.height);
+        conflict("--bounces", p.bounces != fp.bounces);
+        conflict("--integrator", p.integrator != fp.integrator);
+        conflict("--seed", p.seed != fp.seed);
+        conflict("--morton", p.pixel_order != fp.pixel_order);
+        conflict("--tile", p.tile_w != fp.tile_w || p.tile_h != fp.tile_h);
+        conflict("--cam", memcmp(&cam.pos, &fc.pos, sizeof(pt_vec3)) != 0);
+        conflict("--dist", cam.dist_from_film != fc.dist_from_film);
+        conflict("--focal", cam.focal_length != fc.focal_length);
+        conflict("--radius", cam.radius != fc.radius);
+        const int add = p.spp;
+        p = fp;
+        p.spp = add;
+        cam = fc;
+        if (!quiet) printf("resuming %s: %dx%d, %lld samples done, adding %d\n", resume.c_str(), p.width, p.height, (long long)done, add);
+    }
 
     const auto t0 = std::chrono::steady_clock::now();
     pt_host_scene* s = pt_scene_new();
@@ -160,13 +208,57 @@ int main(int argc, char** argv)
         if (!ctx[g]) return die("pt_create");
     }
     std::vector<float> img(n, 0.0f);
+    // the image files of the current `img` (after the render; with --pass-spp after every pass)
+    auto write_images = [&]() -> const char* {
+        if (p.pixel_order == PT_ORDER_MORTON) {
+            // the buffer as the reference holds it (imgBuff[mortonPxltoI(x,y)]): the PPM loop of
+            // kernel.cu:763-778 reads it through the Morton map
+            if (pt_write_ppm_order(out.c_str(), img.data(), p.width, p.height, PT_ORDER_MORTON) != PT_OK) return "write PPM";
+            if (!pfm.empty()) {
+                std::vector<float> scan(n);
+                for (int y = 0; y < p.height; ++y)
+                    for (int x = 0; x < p.width; ++x)
+                        memcpy(&scan[((size_t)y * p.width + x) * 3], &img[(size_t)pt_morton_pxl_to_i(x, y) * 3], 12);
+                if (pt_write_pfm(pfm.c_str(), scan.data(), p.width, p.height) != PT_OK) return "write PFM";
+            }
+        } else {
+            std::vector<int32_t> codes(n);
+            if (pt_tonemap(ctx[0], img.data(), p.width, p.height, codes.data()) != PT_OK) return "tone map";
+            if (pt_write_ppm_codes(out.c_str(), codes.data(), p.width, p.height) != PT_OK) return "write PPM";
+            if (!pfm.empty() && pt_write_pfm(pfm.c_str(), img.data(), p.width, p.height) != PT_OK) return "write PFM";
+        }
+        return nullptr;
+    };
     pt_stats st{};
     const auto t1 = std::chrono::steady_clock::now();
-    // one GPU: pt_render; N GPUs: image-tile shards on devices 0..N-1 summed by one RCCL reduce
-    const int rc = (gpus == 1) ? pt_render(ctx[0], &p, &cam, img.data(), &st)
-                               : pt_render_multi(ctx.data(), gpus, &p, &cam, img.data(), &st);
+    if (accumulate) {
+        // the reference's progressive loop (kernel.cu:709-736) as passes of an accumulator
+        int err = 0;
+        pt_accum* acc = resume.empty() ? pt_accum_create(ctx[0], &p, &cam, &err) : pt_accum_load(ctx[0], resume.c_str(), &err);
+        if (!acc) return die(resume.empty() ? "pt_accum_create" : "--resume");
+        const int step = pass_spp > 0 ? pass_spp : (p.spp > 0 ? p.spp : 1);
+        for (int left = p.spp; left > 0; left -= step) {
+            pt_stats ps{};
+            if (pt_accum_add(acc, left < step ? left : step, nullptr, nullptr, &ps) != PT_OK) return die("pt_accum_add");
+            st.samples += ps.samples; st.rays_traced += ps.rays_traced; st.rays_reference += ps.rays_reference;
+            st.rays_nominal += ps.rays_nominal;
+            if (pass_spp > 0 && !quiet) printf("sample %lld\n", (long long)pt_accum_samples(acc));   // kernel.cu:731
+            if (pass_spp > 0 && left > step) {   // (the last pass's files are written below)
+                if (pt_accum_read(acc, img.data(), nullptr) != PT_OK) return die("pt_accum_read");
+                if (const char* what = write_images()) return die(what);
+                if (!checkpoint.empty() && pt_accum_save(acc, checkpoint.c_str()) != PT_OK) return die("--checkpoint");
+            }
+        }
+        if (pt_accum_read(acc, img.data(), nullptr) != PT_OK) return die("pt_accum_read");
+        if (!checkpoint.empty() && pt_accum_save(acc, checkpoint.c_str()) != PT_OK) return die("--checkpoint");
+        pt_accum_destroy(acc);
+    } else {
+        // one GPU: pt_render; N GPUs: image-tile shards on devices 0..N-1 summed by one RCCL reduce
+        const int rc = (gpus == 1) ? pt_render(ctx[0], &p, &cam, img.data(), &st)
+                                   : pt_render_multi(ctx.data(), gpus, &p, &cam, img.data(), &st);
+        if (rc != PT_OK) return die("pt_render");
+    }
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
-    if (rc != PT_OK) return die("pt_render");
     const uint64_t samples = st.samples, traced = st.rays_traced, reference = st.rays_reference;
     const uint64_t nominal = st.rays_nominal;   // (summed over the shards)
     if (!tri_csv.empty()) {
@@ -184,23 +276,7 @@ int main(int argc, char** argv)
                "%.1f Mrays/s nominal (kernel.cu:757)\n",
                gpus, secs, samples / secs / 1e6, traced / secs / 1e6, reference / secs / 1e6, nominal / secs / 1e6);
     }
-    if (p.pixel_order == PT_ORDER_MORTON) {
-        // the buffer as the reference holds it (imgBuff[mortonPxltoI(x,y)]): the PPM loop of
-        // kernel.cu:763-778 reads it through the Morton map
-        if (pt_write_ppm_order(out.c_str(), img.data(), p.width, p.height, PT_ORDER_MORTON) != PT_OK) return die("write PPM");
-        if (!pfm.empty()) {
-            std::vector<float> scan(n);
-            for (int y = 0; y < p.height; ++y)
-                for (int x = 0; x < p.width; ++x)
-                    memcpy(&scan[((size_t)y * p.width + x) * 3], &img[(size_t)pt_morton_pxl_to_i(x, y) * 3], 12);
-            if (pt_write_pfm(pfm.c_str(), scan.data(), p.width, p.height) != PT_OK) return die("write PFM");
-        }
-    } else {
-        std::vector<int32_t> codes(n);
-        if (pt_tonemap(ctx[0], img.data(), p.width, p.height, codes.data()) != PT_OK) return die("tone map");
-        if (pt_write_ppm_codes(out.c_str(), codes.data(), p.width, p.height) != PT_OK) return die("write PPM");
-        if (!pfm.empty() && pt_write_pfm(pfm.c_str(), img.data(), p.width, p.height) != PT_OK) return die("write PFM");
-    }
+    if (const char* what = write_images()) return die(what);
     for (pt_ctx* c : ctx) pt_destroy(c);
     pt_scene_free(s);
     return 0;

@@ -1,0 +1,306 @@
+// pt_accum.cpp -- resumable sample accumulation (include/pt/pt.h, pt_accum_*): the reference's progressive
+// loop (kernel.cu:702-737: one drawPixel launch per sample over randState_device and imgBuffer_device,
+// kernel.cu:527-553) as passes of the wavefront kernels over a per-pixel state kept on the device, and that
+// state's checkpoint file.  Host code over the HIP runtime (no kernels): the passes themselves are
+// pt::accum_pass (pt_render.hip).
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "../host/host_internal.h"
+
+namespace {
+
+#define ACC_HIP(call)                                                                                      \
+    do {                                                                                                   \
+        const hipError_t e_ = (call);                                                                      \
+        if (e_ != hipSuccess) return pt::fail(PT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_));    \
+    } while (0)
+
+// The checkpoint header (documented in pt.h); every field little-endian at a fixed offset.
+constexpr char kMagic[8] = {'P', 'T', 'A', 'C', 'C', 'U', 'M', '\0'};
+constexpr uint32_t kVersion = 1;
+constexpr size_t kRecordBytes = 48;
+struct Header {
+    char magic[8];
+    uint32_t version;
+    uint32_t header_bytes;
+    pt_params params;        // 56 B: spp = 0, the 4 bytes of tail padding 0
+    pt_camera cam;           // 32 B
+    int64_t samples;
+    uint64_t scene_digest;
+    uint32_t num_tris, num_spheres;
+};
+static_assert(sizeof(pt_params) == 56, "pt_params is 56 B in the checkpoint header");
+static_assert(sizeof(Header) == 128, "checkpoint header is 128 B");
+struct Record {
+    uint32_t rng[6];   // v0..v4, d
+    double mean[3];
+};
+static_assert(sizeof(Record) == kRecordBytes, "checkpoint record is 48 B");
+
+bool little_endian()
+{
+    const uint32_t one = 1;
+    unsigned char b;
+    memcpy(&b, &one, 1);
+    return b == 1;
+}
+
+// Reads and validates the header of `path`; *file_bytes = the file's size.
+int read_header(const char* what, const char* path, Header* h, FILE** keep)
+{
+    if (!little_endian()) return pt::fail(PT_E_INVALID, "%s: checkpoint files are little-endian; this host is not", what);
+    FILE* f = fopen(path, "rb");
+    if (!f) return pt::fail(PT_E_IO, "%s: cannot open %s", what, path);
+    auto bail = [&](int code) { fclose(f); return code; };
+    if (fread(h, 1, sizeof(Header), f) != sizeof(Header))
+        return bail(pt::fail(PT_E_IO, "%s: %s is shorter than the %zu-byte header", what, path, sizeof(Header)));
+    if (memcmp(h->magic, kMagic, 8) != 0) return bail(pt::fail(PT_E_INVALID, "%s: %s is not a checkpoint file (bad magic)", what, path));
+    if (h->version != kVersion)
+        return bail(pt::fail(PT_E_INVALID, "%s: %s has format version %u, this build reads %u", what, path, h->version, kVersion));
+    if (h->header_bytes != sizeof(Header))
+        return bail(pt::fail(PT_E_INVALID, "%s: %s has a %u-byte header, expected %zu", what, path, h->header_bytes, sizeof(Header)));
+    const pt_params& p = h->params;
+    if (p.width <= 0 || p.height <= 0 || p.width > 65535 || p.height > 65535 || h->samples < 0 ||
+        h->samples > (int64_t)pt::accum_max_samples())
+        return bail(pt::fail(PT_E_INVALID, "%s: %s: image %dx%d with %lld samples is out of range", what, path, p.width, p.height,
+                             (long long)h->samples));
+    if (fseek(f, 0, SEEK_END) != 0) return bail(pt::fail(PT_E_IO, "%s: cannot seek in %s", what, path));
+    const long long size = ftell(f);
+    const long long want = (long long)sizeof(Header) + (long long)p.width * p.height * (long long)kRecordBytes;
+    if (size < want)
+        return bail(pt::fail(PT_E_IO, "%s: %s is truncated: %lld bytes, %dx%d records need %lld", what, path, size, p.width, p.height, want));
+    if (size > want)
+        return bail(pt::fail(PT_E_INVALID, "%s: %s has %lld bytes, %dx%d records make %lld", what, path, size, p.width, p.height, want));
+    if (keep) {
+        if (fseek(f, (long)sizeof(Header), SEEK_SET) != 0) return bail(pt::fail(PT_E_IO, "%s: cannot seek in %s", what, path));
+        *keep = f;
+    } else {
+        fclose(f);
+    }
+    return PT_OK;
+}
+
+}  // namespace
+
+struct pt_accum {
+    pt_ctx* ctx = nullptr;
+    pt_params params;
+    pt_camera cam;
+    int64_t samples = 0;
+    std::vector<uint32_t> slot_pix;   // work slot -> scanline pixel id (0xffffffff: outside the image)
+    uint32_t* d_rng = nullptr;        // 6 words per slot, word-major
+    double* d_mean = nullptr;         // 3 doubles per slot, channel-major
+    size_t slots() const { return slot_pix.size(); }
+};
+
+namespace {
+
+// The accumulator of (c, p, cam) with zeroed state (0 samples), or null with the error recorded.
+pt_accum* make_accum(pt_ctx* c, const pt_params* p, const pt_camera* cam, int* code)
+{
+    *code = pt::accum_check(c, p, cam);
+    if (*code != PT_OK) return nullptr;
+    pt_accum* a = new (std::nothrow) pt_accum();
+    if (!a) { *code = pt::fail(PT_E_OOM, "pt_accum_create: out of host memory"); return nullptr; }
+    a->ctx = c;
+    memset(&a->params, 0, sizeof(a->params));   // (padding too: the header is written from it)
+    a->params.width = p->width; a->params.height = p->height; a->params.spp = 0; a->params.bounces = p->bounces;
+    a->params.integrator = p->integrator; a->params.flags = p->flags; a->params.seed = p->seed;
+    a->params.shard_index = p->shard_index; a->params.shard_count = p->shard_count; a->params.pixel_order = p->pixel_order;
+    a->params.tile_w = p->tile_w; a->params.tile_h = p->tile_h;
+    a->cam = *cam;
+    pt::shard_slots(&a->params, &a->slot_pix);
+    auto alloc = [&]() -> int {
+        ACC_HIP(hipSetDevice(pt::ctx_device(c)));
+        const size_t n = a->slots() ? a->slots() : 1;
+        ACC_HIP(hipMalloc(reinterpret_cast<void**>(&a->d_rng), n * 6 * sizeof(uint32_t)));
+        ACC_HIP(hipMalloc(reinterpret_cast<void**>(&a->d_mean), n * 3 * sizeof(double)));
+        ACC_HIP(hipMemset(a->d_rng, 0, n * 6 * sizeof(uint32_t)));
+        ACC_HIP(hipMemset(a->d_mean, 0, n * 3 * sizeof(double)));
+        ACC_HIP(hipDeviceSynchronize());
+        return PT_OK;
+    };
+    *code = alloc();
+    if (*code != PT_OK) { pt_accum_destroy(a); return nullptr; }
+    return a;
+}
+
+// The state as scanline records (pixels outside the shard: all zero).
+int fetch_records(pt_accum* a, std::vector<Record>* rec)
+{
+    const size_t n = a->slots();
+    std::vector<uint32_t> rng(n * 6);
+    std::vector<double> mean(n * 3);
+    ACC_HIP(hipSetDevice(pt::ctx_device(a->ctx)));
+    if (n) {
+        ACC_HIP(hipMemcpy(rng.data(), a->d_rng, n * 6 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        ACC_HIP(hipMemcpy(mean.data(), a->d_mean, n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    Record zero;
+    memset(&zero, 0, sizeof(zero));
+    rec->assign((size_t)a->params.width * a->params.height, zero);
+    if (a->samples == 0) return PT_OK;
+    for (size_t q = 0; q < n; ++q) {
+        const uint32_t pix = a->slot_pix[q];
+        if (pix == 0xffffffffu) continue;
+        Record& r = (*rec)[pix];
+        for (int k = 0; k < 6; ++k) r.rng[k] = rng[(size_t)k * n + q];
+        for (int k = 0; k < 3; ++k) r.mean[k] = mean[(size_t)k * n + q];
+    }
+    return PT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+pt_accum* pt_accum_create(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, int* err)
+{
+    pt::clear_error();
+    int code;
+    pt_accum* a = nullptr;
+    if (!ctx || !params || !cam) code = pt::fail(PT_E_INVALID, "pt_accum_create: null argument");
+    else a = make_accum(ctx, params, cam, &code);
+    if (err) *err = code;
+    return a;
+}
+
+int pt_accum_add(pt_accum* acc, int32_t spp, float* d_out, void* stream, pt_stats* stats)
+{
+    pt::clear_error();
+    if (!acc) return pt::fail(PT_E_INVALID, "pt_accum_add: null accumulator");
+    if (spp < 0) return pt::fail(PT_E_INVALID, "pt_accum_add: spp < 0");
+    if (pt::ctx_in_flight(acc->ctx) > 0)
+        return pt::fail(PT_E_INVALID, "pt_accum_add: %d asynchronous renders in flight (pt_render_wait first)",
+                        pt::ctx_in_flight(acc->ctx));
+    if (acc->samples + (int64_t)spp > (int64_t)pt::accum_max_samples())
+        return pt::fail(PT_E_INVALID, "pt_accum_add: %lld + %d samples exceed what a unit word carries (%u; bit 31 of a "
+                        "unit's first sample number is the lens flag, bit 30 marks the pixel's first unit of a pass)",
+                        (long long)acc->samples, spp, pt::accum_max_samples());
+    if (spp == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return PT_OK;
+    }
+    pt_params p = acc->params;
+    p.spp = spp;
+    const pt::AccumPass pass{(uint32_t)acc->samples, acc->d_rng, acc->d_mean};
+    if (int rc = pt::accum_pass(acc->ctx, &p, &acc->cam, pass, d_out, stream, stats)) return rc;
+    acc->samples += spp;
+    return PT_OK;
+}
+
+int64_t pt_accum_samples(const pt_accum* acc) { return acc ? acc->samples : 0; }
+
+int pt_accum_read(pt_accum* acc, float* out_rgb, double* out_mean)
+{
+    pt::clear_error();
+    if (!acc) return pt::fail(PT_E_INVALID, "pt_accum_read: null accumulator");
+    std::vector<Record> rec;
+    if (int rc = fetch_records(acc, &rec)) return rc;
+    const uint32_t w = (uint32_t)acc->params.width, h = (uint32_t)acc->params.height;
+    for (uint32_t y = 0; y < h; ++y)
+        for (uint32_t x = 0; x < w; ++x) {
+            const Record& r = rec[(size_t)y * w + x];
+            const size_t o = (acc->params.pixel_order == PT_ORDER_MORTON) ? (size_t)pt_morton_pxl_to_i(x, y) : (size_t)y * w + x;
+            for (int k = 0; k < 3; ++k) {
+                if (out_mean) out_mean[o * 3 + k] = r.mean[k];
+                if (out_rgb) out_rgb[o * 3 + k] = (float)r.mean[k];   // the render kernels' own conversion
+            }
+        }
+    return PT_OK;
+}
+
+int pt_accum_save(pt_accum* acc, const char* path)
+{
+    pt::clear_error();
+    if (!acc || !path) return pt::fail(PT_E_INVALID, "pt_accum_save: null argument");
+    if (!little_endian()) return pt::fail(PT_E_INVALID, "pt_accum_save: checkpoint files are little-endian; this host is not");
+    std::vector<Record> rec;
+    if (int rc = fetch_records(acc, &rec)) return rc;
+    Header h;
+    memset(&h, 0, sizeof(h));
+    memcpy(h.magic, kMagic, 8);
+    h.version = kVersion;
+    h.header_bytes = (uint32_t)sizeof(Header);
+    h.params = acc->params;
+    h.cam = acc->cam;
+    h.samples = acc->samples;
+    pt::ctx_scene_id(acc->ctx, &h.scene_digest, &h.num_tris, &h.num_spheres);
+    FILE* f = fopen(path, "wb");
+    if (!f) return pt::fail(PT_E_IO, "pt_accum_save: cannot open %s for writing", path);
+    const bool ok = fwrite(&h, 1, sizeof(h), f) == sizeof(h) && fwrite(rec.data(), sizeof(Record), rec.size(), f) == rec.size();
+    if (fclose(f) != 0 || !ok) return pt::fail(PT_E_IO, "pt_accum_save: short write to %s", path);
+    return PT_OK;
+}
+
+pt_accum* pt_accum_load(pt_ctx* ctx, const char* path, int* err)
+{
+    pt::clear_error();
+    auto bail = [&](int code) -> pt_accum* { if (err) *err = code; return nullptr; };
+    if (!ctx || !path) return bail(pt::fail(PT_E_INVALID, "pt_accum_load: null argument"));
+    Header h;
+    FILE* f = nullptr;
+    if (int rc = read_header("pt_accum_load", path, &h, &f)) return bail(rc);
+    std::vector<Record> rec((size_t)h.params.width * h.params.height);
+    const bool got = fread(rec.data(), sizeof(Record), rec.size(), f) == rec.size();
+    fclose(f);
+    if (!got) return bail(pt::fail(PT_E_IO, "pt_accum_load: cannot read the records of %s", path));
+    uint64_t digest;
+    uint32_t nt, ns;
+    pt::ctx_scene_id(ctx, &digest, &nt, &ns);
+    if (digest != h.scene_digest || nt != h.num_tris || ns != h.num_spheres)
+        return bail(pt::fail(PT_E_SCENE, "pt_accum_load: %s was written for another scene (%u triangles, %u spheres, digest "
+                             "%016llx; this context: %u, %u, %016llx)", path, h.num_tris, h.num_spheres,
+                             (unsigned long long)h.scene_digest, nt, ns, (unsigned long long)digest));
+    int code;
+    pt_accum* a = make_accum(ctx, &h.params, &h.cam, &code);
+    if (!a) return bail(code);
+    const size_t n = a->slots();
+    std::vector<uint32_t> rng(n * 6, 0u);
+    std::vector<double> mean(n * 3, 0.0);
+    for (size_t q = 0; q < n; ++q) {
+        const uint32_t pix = a->slot_pix[q];
+        if (pix == 0xffffffffu) continue;
+        for (int k = 0; k < 6; ++k) rng[(size_t)k * n + q] = rec[pix].rng[k];
+        for (int k = 0; k < 3; ++k) mean[(size_t)k * n + q] = rec[pix].mean[k];
+    }
+    auto upload = [&]() -> int {
+        if (!n) return PT_OK;
+        ACC_HIP(hipMemcpy(a->d_rng, rng.data(), n * 6 * sizeof(uint32_t), hipMemcpyHostToDevice));
+        ACC_HIP(hipMemcpy(a->d_mean, mean.data(), n * 3 * sizeof(double), hipMemcpyHostToDevice));
+        return PT_OK;
+    };
+    if (int rc = upload()) { pt_accum_destroy(a); return bail(rc); }
+    a->samples = h.samples;
+    if (err) *err = PT_OK;
+    return a;
+}
+
+int pt_accum_file_info(const char* path, pt_params* params, pt_camera* cam, int64_t* samples, uint64_t* scene_digest)
+{
+    pt::clear_error();
+    if (!path) return pt::fail(PT_E_INVALID, "pt_accum_file_info: null path");
+    Header h;
+    if (int rc = read_header("pt_accum_file_info", path, &h, nullptr)) return rc;
+    if (params) *params = h.params;
+    if (cam) *cam = h.cam;
+    if (samples) *samples = h.samples;
+    if (scene_digest) *scene_digest = h.scene_digest;
+    return PT_OK;
+}
+
+void pt_accum_destroy(pt_accum* acc)
+{
+    if (!acc) return;
+    (void)hipSetDevice(pt::ctx_device(acc->ctx));
+    if (acc->d_rng) (void)hipFree(acc->d_rng);
+    if (acc->d_mean) (void)hipFree(acc->d_mean);
+    delete acc;
+}
+
+}  // extern "C"

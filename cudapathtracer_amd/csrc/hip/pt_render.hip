@@ -113,7 +113,19 @@ struct Args {
     unsigned long long* lane_times; // diagnostic (PT_LANE_TIMING): wall clock of each lane's end, then each
                                     // wave's start and exit (render_unidir_wf), or null
     uint32_t head;                  // integrator 1 on the wavefront kernel (init_pixel_states' replay)
+    // A pass of an accumulator (pt_accum_add; kAccum kernels): spp is then the samples of THIS pass, which
+    // are the pixel's samples acc_n0 + 1 .. acc_n0 + spp.  (New fields go here, at the end: the offsets
+    // above are what the plain kernels' scalar loads were tuned with.)
+    uint32_t accum;                 // 1: accumulating pass
+    uint32_t acc_n0;                // samples every pixel of the shard has already (N)
+    uint32_t* acc_rng;              // per pixel slot q: XORWOW after its last finished sample, word k (v0..v4, d)
+                                    // at [k * npix + q] (a wave's 64 slots: one 256-B row per word)
+    double* acc_mean;               // per pixel slot q: the f64 running mean, channel k at [k * npix + q]
 };
+// Unit words of an accumulating pass: UW_N0 bit 30 marks a pixel's first unit of the pass (chunk 0, or the
+// whole pixel) -- `n == 1` no longer does; its sample numbers are the 30 bits below.
+constexpr uint32_t kUnitFirst = 0x40000000u;
+constexpr uint32_t kAccumMaxSamples = kUnitFirst - 1u;
 
 __device__ __forceinline__ V3 ld_norm(const DShade* s, int32_t tri)
 {
@@ -801,7 +813,13 @@ __global__ __launch_bounds__(256) void init_pixel_states(Args a, uint32_t* __res
     }
     const uint32_t idx = morton2(px, py);
     Rng r;
-    if (a.jump_bytes) {
+    const uint32_t n_done = a.accum ? a.acc_n0 : 0u;   // samples the pixel has before this render
+    if (n_done != 0u) {
+        // a later pass of an accumulator: the stream continues where the pixel's last sample left it
+        const size_t P = a.npix;
+        r.v0 = a.acc_rng[q]; r.v1 = a.acc_rng[P + q]; r.v2 = a.acc_rng[2 * P + q];
+        r.v3 = a.acc_rng[3 * P + q]; r.v4 = a.acc_rng[4 * P + q]; r.d = a.acc_rng[5 * P + q];
+    } else if (a.jump_bytes) {
         // curand_init(seed, idx, 0) = J(idx) v(seed): the jump matrices are powers of one matrix,
         // so they commute and J(idx) = J(idx & 0xff0000) J(idx & 0xff00) J(idx & 0xff) -- the low
         // byte's product is tabulated per render (seed_states), the next two bytes' per context
@@ -839,9 +857,11 @@ __global__ __launch_bounds__(256) void init_pixel_states(Args a, uint32_t* __res
         st[4 * N + u] = r.v4;
         st[5 * N + u] = r.d;       // the Weyl counter advances with every draw
         st[UW_PXY * N + u] = px | (py << 16);
-        st[UW_N0 * N + u] = (s0 + 1u) | (lens ? 0x80000000u : 0u);
-        st[UW_NEND * N + u] = split ? chunk_first(a, c + 1, nc) : (uint32_t)a.spp;
-        st[UW_TQ * N + u] = split ? t : 0u;
+        // (an accumulating pass: sample numbers continue from n_done, the pixel's first unit is flagged,
+        // and a whole-pixel unit carries its slot -- the row of its stored mean and XORWOW state)
+        st[UW_N0 * N + u] = (n_done + s0 + 1u) | (lens ? 0x80000000u : 0u) | ((a.accum && c == 0u) ? kUnitFirst : 0u);
+        st[UW_NEND * N + u] = n_done + (split ? chunk_first(a, c + 1, nc) : (uint32_t)a.spp);
+        st[UW_TQ * N + u] = split ? t : (a.accum ? q : 0u);
         st[UW_CD * N + u] = __float_as_uint(d.x);
         st[(UW_CD + 1) * N + u] = __float_as_uint(d.y);
         st[(UW_CD + 2) * N + u] = __float_as_uint(d.z);
@@ -891,7 +911,12 @@ __global__ __launch_bounds__(256) void finalize_pixels(Args a)
     // integrator 1 stores every sample (its chunk 0 keeping the mean measured -1% on the 1/8 shard)
     const uint32_t e0 = a.head ? 0u : chunk_first(a, 1u, slot_chunks(a, t));
     double m0 = 0.0, m1 = 0.0, m2 = 0.0;
+    // an accumulating pass: the fold continues the slot's stored mean (unless chunk 0 already did), over
+    // this pass's rows, with the pixel's own sample numbers nb + 1 .. nb + spp
+    const int nb = a.accum ? (int)a.acc_n0 : 0;
+    double* const am = a.accum ? a.acc_mean + (size_t)a.nwhole + t : nullptr;
     if (e0 != 0u) { m0 = L[0]; m1 = L[1]; m2 = L[2]; }
+    else if (am) { m0 = am[0]; m1 = am[a.npix]; m2 = am[2 * (size_t)a.npix]; }
     L += (size_t)e0 * stride;
     // one sample: the six quotients by fn as one IEEE reciprocal + Markstein corrections (RN(x/fn)
     // for finite x clear of under/overflow, as in the render kernel's sample end) -- else the wave
@@ -927,13 +952,17 @@ __global__ __launch_bounds__(256) void finalize_pixels(Args a)
             for (int k = 0; k < 8; ++k) { q[3 * k] = L[k * stride]; q[3 * k + 1] = L[k * stride + 1]; q[3 * k + 2] = L[k * stride + 2]; }
         }
 #pragma unroll
-        for (int k = 0; k < 8; ++k) step(n + k, v[3 * k], v[3 * k + 1], v[3 * k + 2]);
+        for (int k = 0; k < 8; ++k) step(nb + n + k, v[3 * k], v[3 * k + 1], v[3 * k + 2]);
         if (more) {
 #pragma unroll
             for (int k = 0; k < 24; ++k) v[k] = q[k];
         }
     }
-    for (; n <= a.spp; ++n, L += stride) step(n, L[0], L[1], L[2]);
+    for (; n <= a.spp; ++n, L += stride) step(nb + n, L[0], L[1], L[2]);
+    if (am) {
+        am[0] = m0; am[a.npix] = m1; am[2 * (size_t)a.npix] = m2;
+        if (!a.out) return;
+    }
     float* o3 = a.out + pix * 3;
     o3[0] = (float)m0;
     o3[1] = (float)m1;
@@ -991,7 +1020,10 @@ __device__ __forceinline__ const Args& kernel_args_opaque()
     return *(const Args*)p;
 }
 
-template <bool kCount>
+// kAccum: a pass of an accumulator (Args::accum): a pixel's first unit starts from the slot's stored f64
+// mean, the unit that runs a pixel's last sample of the pass stores the XORWOW state back, and a whole
+// pixel's unit stores its mean.  Sample numbers, and so the divisors of the mean, continue from acc_n0.
+template <bool kCount, bool kAccum>
 __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, int lane, uint32_t& state, V3& ro, V3& rd,
                                            int32_t& htri, float& ht, W4& w, const Stack4& S,
                                            unsigned long long* lcnt, const uint32_t* lprobe, uint32_t* done_rel,
@@ -1282,10 +1314,20 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
                             double* P = a.lbuf + (size_t)c8.w * 3;
                             P[0] = m0; P[1] = m1; P[2] = m2;
                         } else {
-                            float* o3 = a.out + out_pixel(a, px, py) * 3;
-                            o3[0] = (float)m0;
-                            o3[1] = (float)m1;
-                            o3[2] = (float)m2;
+                            if (kAccum) {   // the slot's mean and stream (c8.w: a whole unit's slot), for the next pass
+                                const size_t P = a.npix;
+                                double* am = a.acc_mean + c8.w;
+                                am[0] = m0; am[P] = m1; am[2 * P] = m2;
+                                uint32_t* ar = a.acc_rng + c8.w;
+                                ar[0] = rng.v0; ar[P] = rng.v1; ar[2 * P] = rng.v2; ar[3 * P] = rng.v3; ar[4 * P] = rng.v4;
+                                ar[5 * P] = rng.d;
+                            }
+                            if (!kAccum || a.out) {
+                                float* o3 = a.out + out_pixel(a, px, py) * 3;
+                                o3[0] = (float)m0;
+                                o3[1] = (float)m1;
+                                o3[2] = (float)m2;
+                            }
                         }
                         state = ST_IDLE;
                         break;
@@ -1295,11 +1337,18 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
                     // split pixel: keep L_n, finalize_pixels forms the ordered mean
                     // (the slot is cell 8's last word, fetched with this sample's end: no dependent fetch
                     // before the stores)
-                    double* L = a.lbuf + ((size_t)(uint32_t)(n - 1) * a.ntail + c8.w) * 3;
+                    // (an accumulating pass: rows count from the pass's first sample)
+                    double* L = a.lbuf + ((size_t)((uint32_t)(n - 1) - (kAccum ? a.acc_n0 : 0u)) * a.ntail + c8.w) * 3;
                     L[0] = acc.r;
                     L[1] = acc.g;
                     L[2] = acc.b;
                     if ((uint32_t)n >= nend) {
+                        if (kAccum && nend == a.acc_n0 + (uint32_t)a.spp) {   // the pixel's last sample of the pass
+                            const size_t P = a.npix;
+                            uint32_t* ar = a.acc_rng + a.nwhole + c8.w;
+                            ar[0] = rng.v0; ar[P] = rng.v1; ar[2 * P] = rng.v2; ar[3 * P] = rng.v3; ar[4 * P] = rng.v4;
+                            ar[5 * P] = rng.d;
+                        }
                         state = ST_IDLE;
                         break;
                     }
@@ -1420,7 +1469,9 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
                     rng.v4 = a.pix_states[4 * N + u];
                     rng.d = a.pix_states[5 * N + u];
                     nend = a.pix_states[UW_NEND * N + u];
-                    n = (int)(n0 & 0x7fffffffu);
+                    n = (int)(n0 & (kAccum ? kAccumMaxSamples : 0x7fffffffu));
+                    // the pixel's first unit (of the pass): sample 1, or the unit word's flag
+                    const bool first = kAccum ? (n0 & kUnitFirst) != 0u : n == 1;
                     const bool split = u >= a.nwhole;
                     fl = (n0 >> 31) ? CF_LENS : CF_CAMC;
                     uint4 c8 = make_uint4(0u, 0u, 0u, 0u);
@@ -1429,17 +1480,26 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
                                         a.pix_states[(UW_CD + 2) * N + u], a.pix_states[UW_TQ * N + u]);
                         R.st4(CW_CD, c8.x, c8.y, c8.z, c8.w);
                     }
-                    if (split) fl |= (n == 1) ? CF_SPLIT | CF_CHUNK0 : CF_SPLIT;
+                    if (split) fl |= first ? CF_SPLIT | CF_CHUNK0 : CF_SPLIT;
 #ifdef PT_DEBUG_CHECKS
                     // finalize_pixels continues a CF_CHUNK0 slot's mean from sample chunk_first(1): the unit must end there
-                    if (split && n == 1 && nend != chunk_first(a, 1u, slot_chunks(a, a.pix_states[UW_TQ * N + u])))
+                    if (split && first &&
+                        nend != (kAccum ? a.acc_n0 : 0u) + chunk_first(a, 1u, slot_chunks(a, a.pix_states[UW_TQ * N + u])))
                         __builtin_trap();
 #endif
                     if (split && !(fl & CF_LENS) && !(a.flags & PT_FLAG_NO_PRIMARY_CACHE))
-                        fl |= (n == 1) ? CF_OWNER : CF_SHARE;   // (chunk 0 starts at sample 1)
+                        fl |= first ? CF_OWNER : CF_SHARE;   // (chunk 0 starts the pixel: sample 1 of a plain render)
                     R.st2(CW_PX, px, py);
-                    if (split && (fl & CF_LENS)) R.st(CW_Q, a.pix_states[UW_TQ * N + u]);
-                    R.st2(CW_M, 0u, 0u); R.st4(CW_M + 2, 0u, 0u, 0u, 0u);
+                    if ((split || kAccum) && (fl & CF_LENS)) R.st(CW_Q, a.pix_states[UW_TQ * N + u]);
+                    if (kAccum && (!split || first)) {
+                        // the unit keeps the running mean: it continues the slot's stored one
+                        const size_t P = a.npix;
+                        const double* am = a.acc_mean + (split ? a.nwhole : 0u) + a.pix_states[UW_TQ * N + u];
+                        const double s0 = am[0], s1 = am[P], s2 = am[2 * P];
+                        R.std_(CW_M, s0); R.st4(CW_M + 2, dlo(s1), dhi(s1), dlo(s2), dhi(s2));
+                    } else {
+                        R.st2(CW_M, 0u, 0u); R.st4(CW_M + 2, 0u, 0u, 0u, 0u);
+                    }
                     // (a new unit: no memo yet; its pinhole direction and slot are in c8 -- a lens
                     // unit reads neither, and its slot from the record)
                     again = start_sample(px, py, !(fl & CF_LENS), make_uint4(0u, 0u, 0u, 0u), c8);
@@ -1647,7 +1707,7 @@ __device__ __forceinline__ float head_vis_occluded(float len)
     return (len > 0.04f) ? len - 0.03f : -1.0f;
 }
 
-template <bool kCount>
+template <bool kCount, bool kAccum>
 __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint32_t& state, V3& ro, V3& rd,
                                                 int32_t& htri, float& ht, W4& w, const Stack4& S,
                                                 unsigned long long* lcnt, const uint32_t* lprobe, uint32_t* done_rel,
@@ -1972,22 +2032,37 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
                     mm1 = x1 / fn + acc.g / fn;
                     mm2 = x2 / fn + acc.b / fn;
                 }
-                if (n >= a.spp) {
-                    float* o3 = a.out + out_pixel(a, px, py) * 3;
-                    o3[0] = (float)m0;
-                    o3[1] = (float)mm1;
-                    o3[2] = (float)mm2;
+                if (kAccum ? (uint32_t)n >= r2.y : n >= a.spp) {   // (the unit's end: a plain whole pixel's is spp)
+                    if (kAccum) {   // the slot's mean and stream (c13.y: a whole unit's slot), for the next pass
+                        const size_t P = a.npix;
+                        double* am = a.acc_mean + c13.y;
+                        am[0] = m0; am[P] = mm1; am[2 * P] = mm2;
+                        uint32_t* ar = a.acc_rng + c13.y;
+                        ar[0] = r1.x; ar[P] = r1.y; ar[2 * P] = r1.z; ar[3 * P] = r1.w; ar[4 * P] = r2.x; ar[5 * P] = rng.d;
+                    }
+                    if (!kAccum || a.out) {
+                        float* o3 = a.out + out_pixel(a, px, py) * 3;
+                        o3[0] = (float)m0;
+                        o3[1] = (float)mm1;
+                        o3[2] = (float)mm2;
+                    }
                     state = ST_IDLE;
                     break;
                 }
                 R.st4(HW_M, dlo(m0), dhi(m0), dlo(mm1), dhi(mm1));
                 R.st2(HW_M + 4, dlo(mm2), dhi(mm2));
             } else {
-                double* Lb = a.lbuf + ((size_t)(uint32_t)(n - 1) * a.ntail + c13.y) * 3;
+                // (an accumulating pass: rows count from the pass's first sample)
+                double* Lb = a.lbuf + ((size_t)((uint32_t)(n - 1) - (kAccum ? a.acc_n0 : 0u)) * a.ntail + c13.y) * 3;
                 Lb[0] = acc.r;
                 Lb[1] = acc.g;
                 Lb[2] = acc.b;
                 if ((uint32_t)n >= r2.y) {
+                    if (kAccum && r2.y == a.acc_n0 + (uint32_t)a.spp) {   // the pixel's last sample of the pass
+                        const size_t P = a.npix;
+                        uint32_t* ar = a.acc_rng + a.nwhole + c13.y;
+                        ar[0] = r1.x; ar[P] = r1.y; ar[2 * P] = r1.z; ar[3 * P] = r1.w; ar[4 * P] = r2.x; ar[5 * P] = rng.d;
+                    }
                     state = ST_IDLE;
                     break;
                 }
@@ -2023,7 +2098,8 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
                       rng.v4 = a.pix_states[4 * N + u];
                       rng.d = a.pix_states[5 * N + u];
                       R.st(HW_NEND, a.pix_states[UW_NEND * N + u]);
-                      n = (int)(n0 & 0x7fffffffu);
+                      n = (int)(n0 & (kAccum ? kAccumMaxSamples : 0x7fffffffu));
+                      const bool first = kAccum ? (n0 & kUnitFirst) != 0u : n == 1;   // the pixel's first unit (of the pass)
                       const bool split = u >= a.nwhole;
                       fl = (n0 >> 31) ? CF_LENS : CF_CAMC;
                       if (!(fl & CF_LENS))
@@ -2031,9 +2107,16 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
                                 a.pix_states[(UW_CD + 2) * N + u], 0u);
                       if (split) fl |= CF_SPLIT;
                       if (split && !(fl & CF_LENS) && !(a.flags & PT_FLAG_NO_PRIMARY_CACHE))
-                          fl |= (n == 1) ? CF_OWNER : CF_SHARE;
-                      R.st4(HW_PXY, pxy, split ? a.pix_states[UW_TQ * N + u] : 0u, 0u, 0u);
-                      R.st4(HW_M, 0u, 0u, 0u, 0u); R.st2(HW_M + 4, 0u, 0u);
+                          fl |= first ? CF_OWNER : CF_SHARE;
+                      R.st4(HW_PXY, pxy, (split || kAccum) ? a.pix_states[UW_TQ * N + u] : 0u, 0u, 0u);
+                      if (kAccum && !split) {   // a whole pixel continues its slot's stored mean
+                          const size_t P = a.npix;
+                          const double* am = a.acc_mean + a.pix_states[UW_TQ * N + u];
+                          const double s0 = am[0], s1 = am[P], s2 = am[2 * P];
+                          R.st4(HW_M, dlo(s0), dhi(s0), dlo(s1), dhi(s1)); R.st2(HW_M + 4, dlo(s2), dhi(s2));
+                      } else {
+                          R.st4(HW_M, 0u, 0u, 0u, 0u); R.st2(HW_M + 4, 0u, 0u);
+                      }
                       again = start_sample(pxy & 0xffffu, pxy >> 16, true);
                   }
               }
@@ -2057,7 +2140,7 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
 // The wavefront kernel's body, shared by both integrators (kHead: integrator 1, shade_lane_head).
 // kLdsWalk: walk steps read the staged top from LDS (integrator 1 always; integrator 0 when the LDS
 // top holds the whole tree) instead of issuing every node's loads to memory.
-template <bool kCount, bool kHead, bool kLdsWalk = kHead>
+template <bool kCount, bool kHead, bool kLdsWalk = kHead, bool kAccum = false>
 __device__ __forceinline__ void wf_main(const Args& a)
 {
     extern __shared__ uint32_t lds_wf[];
@@ -2198,8 +2281,8 @@ __device__ __forceinline__ void wf_main(const Args& a)
         if (kCount) ++shade_slots;
         // (the lane id is recomputed for the shading pass: one VGPR less live across the walk loop)
         if (state != ST_TRACE && state != ST_DONE) {
-            if (kHead) shade_lane_head<kCount>(R, (int)__lane_id(), state, ro, rd, htri, ht, w, S, lcnt, lprobe, done_rel, cnt);
-            else shade_lane<kCount>(a, R, (int)__lane_id(), state, ro, rd, htri, ht, w, S, lcnt, lprobe, done_rel, cnt);
+            if (kHead) shade_lane_head<kCount, kAccum>(R, (int)__lane_id(), state, ro, rd, htri, ht, w, S, lcnt, lprobe, done_rel, cnt);
+            else shade_lane<kCount, kAccum>(a, R, (int)__lane_id(), state, ro, rd, htri, ht, w, S, lcnt, lprobe, done_rel, cnt);
         }
         if (kCount) shade_clk += clock64() - clk0;
         if (__ballot(state != ST_DONE) == 0ull) break;
@@ -2261,6 +2344,18 @@ template <bool kCount, int kMinWaves>
 __global__ __launch_bounds__(256, kMinWaves) void render_head_wf(Args a)
 {
     wf_main<kCount, true>(a);
+}
+
+// The accumulating instances (pt_accum_add; kAccum): default occupancy, no counting -- kernels of their own
+// names, so the plain kernels keep theirs (profiles and tools refer to them).
+template <bool kLdsWalk>
+__global__ __launch_bounds__(256, 5) void render_unidir_accum_wf(Args a)
+{
+    wf_main<false, false, kLdsWalk, true>(a);
+}
+__global__ __launch_bounds__(256, 5) void render_head_accum_wf(Args a)
+{
+    wf_main<false, true, true, true>(a);
 }
 
 // ------------------------------------------------------------------ output step
@@ -2529,6 +2624,8 @@ struct pt_ctx {
     uint32_t* tri_counts = nullptr;   // PT_FLAG_COUNT: per-triangle test counts (num_tris entries, >= 1)
     DTri* emis = nullptr;             // last-bounce light probe: records of the emissive triangles
     uint32_t num_emis = 0;            // (0 = probe off: spheres present, too many emitters, PT_NO_LIGHT_PROBE)
+    uint64_t scene_digest = 0;        // FNV-1a of the scene arrays (a checkpoint file names its scene by it)
+    uint32_t scene_spheres = 0;       // ... and the sphere count of that scene
 };
 
 int pt::ctx_device(const pt_ctx* c) { return c->device; }
@@ -2631,6 +2728,18 @@ pt_ctx* pt_create(const pt_scene* sc, int device, int* err)
     c->device = device;
     c->num_cus = prop.multiProcessorCount;
     c->num_tris = nt;
+    {   // what the scene is, for pt_accum_save / pt_accum_load: every array the caller passed
+        uint64_t h = pt::kFnvBasis;
+        h = pt::fnv1a(sc->verts, (size_t)sc->num_verts * sizeof(pt_vec3), h);
+        h = pt::fnv1a(sc->tris, (size_t)nt * sizeof(pt_triangle), h);
+        h = pt::fnv1a(sc->mats, (size_t)sc->num_mats * sizeof(pt_material), h);
+        h = pt::fnv1a(sc->lights, (size_t)sc->num_lights * sizeof(uint32_t), h);
+        h = pt::fnv1a(&sc->total_light_area, sizeof(float), h);
+        h = pt::fnv1a(sc->bvh, (size_t)nn * sizeof(pt_bvh_node), h);
+        h = pt::fnv1a(sc->spheres, (size_t)sc->num_spheres * sizeof(pt_sphere), h);
+        c->scene_digest = h;
+        c->scene_spheres = sc->num_spheres;
+    }
     c->depth = sc->bvh_depth;
 
     std::vector<uint32_t> ref_parent(nt, 0u);
@@ -3058,11 +3167,10 @@ static void write_lane_timing(const char* path, const std::vector<unsigned long 
     }
 }
 
-int pt_render_device_async(pt_ctx* c, const pt_params* p, const pt_camera* cam, float* d_out, void* stream_v)
+// What a render's parameters and camera must satisfy whatever the context (pt_render_device_async and
+// pt_accum_create share it).
+static int validate_render(const pt_params* p, const pt_camera* cam)
 {
-    if (!c || !p || !cam || !d_out) return pt::fail(PT_E_INVALID, "pt_render: null argument");
-    if (c->fl_n >= pt_ctx::kFlights)
-        return pt::fail(PT_E_INVALID, "pt_render_device_async: %d renders in flight (pt_render_wait first)", c->fl_n);
     if (p->width <= 0 || p->height <= 0 || p->width > 65535 || p->height > 65535)
         return pt::fail(PT_E_INVALID, "pt_render: image size %dx%d out of range (1..65535)", p->width, p->height);
     if (p->spp < 0) return pt::fail(PT_E_INVALID, "pt_render: spp < 0");
@@ -3081,10 +3189,6 @@ int pt_render_device_async(pt_ctx* c, const pt_params* p, const pt_camera* cam, 
     for (const int32_t v : {p->tile_w, p->tile_h})
         if (v != 0 && (v < 8 || v > 256 || v % 8 != 0))
             return pt::fail(PT_E_INVALID, "pt_render: tile size %dx%d (0 = 8, else multiples of 8 up to 256)", p->tile_w, p->tile_h);
-    // the per-triangle counts live in one context-wide buffer (pt_tri_counts reads it back): only one render
-    // in flight may fill them
-    if ((p->flags & PT_FLAG_COUNT) && (p->flags & PT_FLAG_TRI_COUNTS) && c->fl_n > 0)
-        return pt::fail(PT_E_INVALID, "pt_render_device_async: PT_FLAG_TRI_COUNTS while a render is in flight");
     {   // the padded tile grid (tiles x tile_w x tile_h slots) must fit the kernels' 32-bit unit indices
         const uint64_t tw64 = p->tile_w ? (uint64_t)p->tile_w : 8u, th64 = p->tile_h ? (uint64_t)p->tile_h : 8u;
         const uint64_t slots = (((uint64_t)p->width + tw64 - 1) / tw64) * (((uint64_t)p->height + th64 - 1) / th64) * tw64 * th64;
@@ -3092,6 +3196,37 @@ int pt_render_device_async(pt_ctx* c, const pt_params* p, const pt_camera* cam, 
             return pt::fail(PT_E_INVALID, "pt_render: %dx%d in %llux%llu tiles pads to %llu pixel slots (limit 2^32-1)",
                             p->width, p->height, (unsigned long long)tw64, (unsigned long long)th64, (unsigned long long)slots);
     }
+    return PT_OK;
+}
+
+// Whether a render of (p, cam) on this context takes the wavefront kernels (else render_tiles).
+static bool takes_wavefront(const pt_ctx* c, const pt_params* p, const pt_camera* cam)
+{
+    // the render-path BVH's box margin assumes ray origins within ~2^6 of the scene extent
+    const float cam_ext = std::fmax(std::fabs(cam->pos.x), std::fmax(std::fabs(cam->pos.y), std::fabs(cam->pos.z)));
+    const bool near_cam = cam_ext <= 64.0f * c->scene_extent;
+    // integrator 1 takes the wavefront kernel too (PT_HEAD_WF=0: the tile kernel, for comparisons)
+    const bool head = p->integrator == PT_INTEGRATOR_HEAD;
+    return (p->integrator == PT_INTEGRATOR_UNIDIR || (head && c->head_wf)) && !(p->flags & PT_FLAG_REFERENCE_TRAVERSAL) &&
+           !(p->flags & PT_FLAG_REFERENCE_BVH) && near_cam &&
+           p->width < 65536 && p->height < 65536;   // (16-bit pixel coordinates per unit)
+}
+
+// One render enqueued on `stream` in the context's next flight slot: the body of pt_render_device_async.
+// acc: the render is a pass of an accumulator (pt::accum_pass) -- p->spp more samples of every pixel on top
+// of its acc->n0, from and to the accumulator's state; d_out may then be null.  Everything else -- the
+// unit split, the buffers' growth, the jump and seed tables, the flight slots -- is the plain render's.
+static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, float* d_out, void* stream_v,
+                          const pt::AccumPass* acc)
+{
+    if (!c || !p || !cam || (!d_out && !acc)) return pt::fail(PT_E_INVALID, "pt_render: null argument");
+    if (c->fl_n >= pt_ctx::kFlights)
+        return pt::fail(PT_E_INVALID, "pt_render_device_async: %d renders in flight (pt_render_wait first)", c->fl_n);
+    if (int rc = validate_render(p, cam)) return rc;
+    // the per-triangle counts live in one context-wide buffer (pt_tri_counts reads it back): only one render
+    // in flight may fill them
+    if ((p->flags & PT_FLAG_COUNT) && (p->flags & PT_FLAG_TRI_COUNTS) && c->fl_n > 0)
+        return pt::fail(PT_E_INVALID, "pt_render_device_async: PT_FLAG_TRI_COUNTS while a render is in flight");
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
     // this render's slot: its events and its buffer set.  The slot's previous render was collected by
@@ -3150,11 +3285,16 @@ int pt_render_device_async(pt_ctx* c, const pt_params* p, const pt_camera* cam, 
     // the render-path BVH's box margin assumes ray origins within ~2^6 of the scene extent
     const float cam_ext = std::fmax(std::fabs(cam->pos.x), std::fmax(std::fabs(cam->pos.y), std::fabs(cam->pos.z)));
     const bool near_cam = cam_ext <= 64.0f * c->scene_extent;
-    // integrator 1 takes the wavefront kernel too (PT_HEAD_WF=0: the tile kernel, for comparisons)
     const bool head = p->integrator == PT_INTEGRATOR_HEAD;
-    const bool wavefront = (p->integrator == PT_INTEGRATOR_UNIDIR || (head && c->head_wf)) && !refwalk &&
-                           !(p->flags & PT_FLAG_REFERENCE_BVH) && near_cam &&
-                           p->width < 65536 && p->height < 65536;   // (16-bit pixel coordinates per unit)
+    const bool wavefront = takes_wavefront(c, p, cam);
+    if (acc) {   // (pt_accum_create refused these already: never a silent fall-back to another kernel)
+        if (!wavefront || count || c->wf_min_waves != 5 || c->head_min_waves != 5)
+            return pt::fail(PT_E_INVALID, "pt_accum_add: this mode has no accumulating kernel");
+        if ((uint64_t)acc->n0 + (uint64_t)p->spp > kAccumMaxSamples)
+            return pt::fail(PT_E_INVALID, "pt_accum_add: %u + %d samples exceed what a unit word carries (%u)", acc->n0, p->spp,
+                            kAccumMaxSamples);
+        a.accum = 1u; a.acc_n0 = acc->n0; a.acc_rng = acc->rng; a.acc_mean = acc->mean;
+    }
 
     // (the wavefront path's init_pixel_states resets the counters itself: one launch less per frame)
     if (!(p->spp > 0 && a.ntiles_shard > 0 && wavefront)) {
@@ -3382,7 +3522,12 @@ int pt_render_device_async(pt_ctx* c, const pt_params* p, const pt_camera* cam, 
         kernel_events = true;
         units = b.nunits;
         split = b.ntail;
-        if (head) {
+        if (acc) {   // the accumulating instances: default occupancy, no counting
+            if (head) hipLaunchKernelGGL(render_head_accum_wf, dim3(blocks), dim3(256), lds_wf, stream, b);
+            else if (lds_tree) hipLaunchKernelGGL(render_unidir_accum_wf<true>, dim3(blocks), dim3(256), lds_wf, stream, b);
+            else hipLaunchKernelGGL(render_unidir_accum_wf<false>, dim3(blocks), dim3(256), lds_wf, stream, b);
+        }
+        else if (head) {
             if (count) hipLaunchKernelGGL((render_head_wf<true, 5>), dim3(blocks), dim3(256), lds_wf, stream, b);
             else if (c->head_min_waves == 4) hipLaunchKernelGGL((render_head_wf<false, 4>), dim3(blocks), dim3(256), lds_wf, stream, b);
             else hipLaunchKernelGGL((render_head_wf<false, 5>), dim3(blocks), dim3(256), lds_wf, stream, b);
@@ -3436,6 +3581,12 @@ int pt_render_device_async(pt_ctx* c, const pt_params* p, const pt_camera* cam, 
     }
     ++c->fl_n;
     return PT_OK;
+}
+
+int pt_render_device_async(pt_ctx* c, const pt_params* p, const pt_camera* cam, float* d_out, void* stream_v)
+{
+    if (!d_out) return pt::fail(PT_E_INVALID, "pt_render: null argument");
+    return render_enqueue(c, p, cam, d_out, stream_v, nullptr);
 }
 
 int pt_render_wait(pt_ctx* c, pt_stats* st)
@@ -3508,6 +3659,41 @@ int pt_render_device(pt_ctx* c, const pt_params* p, const pt_camera* cam, float*
 }
 
 }  // extern "C"
+
+// ---- accumulating passes (host_internal.h): the render context's side of pt_accum.cpp
+int pt::accum_check(const pt_ctx* c, const pt_params* p, const pt_camera* cam)
+{
+    if (int rc = validate_render(p, cam)) return rc;
+    if (p->flags & ~(uint32_t)(PT_FLAG_NO_DEAD_PATH_SKIP | PT_FLAG_NO_PRIMARY_CACHE))
+        return pt::fail(PT_E_INVALID, "pt_accum_create: flags 0x%x: only PT_FLAG_NO_DEAD_PATH_SKIP and PT_FLAG_NO_PRIMARY_CACHE "
+                        "accumulate (the reference walks and the counting variants have no accumulating kernel)", p->flags);
+    if (!takes_wavefront(c, p, cam))
+        return pt::fail(PT_E_INVALID, "pt_accum_create: this render would take the tile kernel (%s), which does not accumulate",
+                        (p->integrator == PT_INTEGRATOR_HEAD && !c->head_wf) ? "integrator 1 with PT_HEAD_WF=0"
+                                                                              : "camera beyond 64 scene extents");
+    if (c->wf_min_waves != 5 || c->head_min_waves != 5)
+        return pt::fail(PT_E_INVALID, "pt_accum_create: only the default-occupancy kernels accumulate (PT_WF_MIN_WAVES / "
+                        "PT_HEAD_MIN_WAVES are set)");
+    return PT_OK;
+}
+
+int pt::accum_pass(pt_ctx* c, const pt_params* p, const pt_camera* cam, const AccumPass& acc, float* d_out, void* stream,
+                   pt_stats* stats)
+{
+    if (c->fl_n > 0)
+        return pt::fail(PT_E_INVALID, "pt_accum_add: %d asynchronous renders in flight (pt_render_wait first)", c->fl_n);
+    if (int rc = render_enqueue(c, p, cam, d_out, stream, &acc)) return rc;
+    return pt_render_wait(c, stats);
+}
+
+void pt::ctx_scene_id(const pt_ctx* c, uint64_t* digest, uint32_t* num_tris, uint32_t* num_spheres)
+{
+    *digest = c->scene_digest;
+    *num_tris = c->num_tris;
+    *num_spheres = c->scene_spheres;
+}
+int pt::ctx_in_flight(const pt_ctx* c) { return c->fl_n; }
+uint32_t pt::accum_max_samples() { return kAccumMaxSamples; }
 
 int pt::copy_to_host(void* dst, const void* src, size_t bytes, void* stream_v, void** pinned, size_t* pinned_bytes)
 {
@@ -3735,6 +3921,27 @@ extern "C" int pt_shard_pixels(int w, int h, int shard_index, int shard_count, i
         ++n;
     }
     *n_out = n;
+    return PT_OK;
+}
+
+int pt::shard_slots(const pt_params* p, std::vector<uint32_t>* pix)
+{
+    TileMap m;
+    m.w = p->width; m.h = p->height; m.shard_index = p->shard_index; m.shard_count = p->shard_count;
+    m.tile_w = p->tile_w ? (uint32_t)p->tile_w : kTile;
+    m.tile_h = p->tile_h ? (uint32_t)p->tile_h : kTile;
+    m.tiles_x = ((uint32_t)p->width + m.tile_w - 1) / m.tile_w;
+    const uint32_t ntiles = m.tiles_x * (((uint32_t)p->height + m.tile_h - 1) / m.tile_h);
+    m.tile_bx = m.tile_w / kTile;
+    m.tile_blocks = m.tile_bx * (m.tile_h / kTile);
+    const uint32_t nts = (ntiles > (uint32_t)p->shard_index)
+                             ? (ntiles - (uint32_t)p->shard_index + (uint32_t)p->shard_count - 1) / (uint32_t)p->shard_count : 0u;
+    const size_t slots = (size_t)nts * m.tile_w * m.tile_h;   // (= Args::npix of this shard's renders)
+    pix->assign(slots, 0xffffffffu);
+    for (size_t q = 0; q < slots; ++q) {
+        uint32_t px, py;
+        if (unit_pixel(m, (uint32_t)q, &px, &py)) (*pix)[q] = py * (uint32_t)p->width + px;
+    }
     return PT_OK;
 }
 

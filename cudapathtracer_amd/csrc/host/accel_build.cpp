@@ -613,11 +613,8 @@ extern "C" int pt_accel_digest(const pt_scene* sc, uint64_t* digest, uint32_t* n
     if (getenv("PT_TIMING"))
         fprintf(stderr, "pt_accel_digest: SAH cost %.6g, binary depth %d, BVH4 depth %d, BVH4 nodes %zu, BVH4 cost (1, 0.3) %.6g\n",
                 pt::accel_sah_cost(acc), acc.depth, acc4.depth, acc4.nodes.size(), pt::accel4_cost(acc4, acc.root_box, 1.0, 0.3));
-    uint64_t h = 1469598103934665603ull;
-    auto mix = [&](const void* p, size_t n) {
-        const unsigned char* c = static_cast<const unsigned char*>(p);
-        for (size_t i = 0; i < n; ++i) { h ^= c[i]; h *= 1099511628211ull; }
-    };
+    uint64_t h = pt::kFnvBasis;
+    auto mix = [&](const void* p, size_t n) { h = pt::fnv1a(p, n, h); };
     mix(acc.nodes.data(), acc.nodes.size() * sizeof(pt::AccelNode));
     mix(acc.leaf_order.data(), acc.leaf_order.size() * sizeof(uint32_t));
     mix(acc4.nodes.data(), acc4.nodes.size() * sizeof(acc4.nodes[0]));

@@ -24,6 +24,36 @@ void clear_error();
 // The HIP device ordinal a render context lives on (pt_render.hip; used by pt_multi.cpp).
 int ctx_device(const pt_ctx* c);
 
+// 64-bit FNV-1a over a byte range, chained through `h` (pt_accel_digest, the scene digest of pt_create).
+constexpr uint64_t kFnvBasis = 1469598103934665603ull;
+inline uint64_t fnv1a(const void* p, size_t n, uint64_t h = kFnvBasis)
+{
+    const unsigned char* c = static_cast<const unsigned char*>(p);
+    for (size_t i = 0; i < n; ++i) { h ^= c[i]; h *= 1099511628211ull; }
+    return h;
+}
+
+// ---- accumulating passes: what pt_accum.cpp (the pt_accum_* entry points) needs of a render context
+// (pt_render.hip).  The state is device memory of the context's device, in the shard's work-slot order:
+// rng[k * slots + q] (k = v0..v4, d) and mean[k * slots + q] (k = r, g, b) of slot q.
+struct AccumPass {
+    uint32_t n0;      // samples every pixel has before this pass
+    uint32_t* rng;
+    double* mean;
+};
+// Validates (params, cam) as pt_render_device_async does and refuses every mode without an accumulating
+// kernel (render_tiles, the counting variants, non-default occupancy).
+int accum_check(const pt_ctx* c, const pt_params* p, const pt_camera* cam);
+// p->spp more samples of every pixel, blocking; d_out (device, W*H*3) may be null.
+int accum_pass(pt_ctx* c, const pt_params* p, const pt_camera* cam, const AccumPass& acc, float* d_out, void* stream,
+               pt_stats* stats);
+// Work slot q of the shard -> scanline pixel id y*W + x, or 0xffffffff for a slot outside the image.
+int shard_slots(const pt_params* p, std::vector<uint32_t>* pix);
+// The FNV-1a digest of the scene arrays the context was created from, and their primitive counts.
+void ctx_scene_id(const pt_ctx* c, uint64_t* digest, uint32_t* num_tris, uint32_t* num_spheres);
+int ctx_in_flight(const pt_ctx* c);
+uint32_t accum_max_samples();
+
 // ---- OBJ/MTL ingest with tinyobj 0.9.13 semantics (tiny_obj_loader.cc) ------------------
 // Only what loadOBJ (modelLoader.h:125-210) consumes is kept: positions, per-triangle
 // indices, per-triangle material ids, material diffuse/emission.  Vertex dedupe keys still

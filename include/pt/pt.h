@@ -239,6 +239,67 @@ int pt_render_device(pt_ctx* ctx, const pt_params* params, const pt_camera* cam,
 int pt_render_device_async(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, float* d_out, void* stream);
 int pt_render_wait(pt_ctx* ctx, pt_stats* stats);
 
+/* ------------------------------------------------- resumable accumulation (progressive rendering)
+ * The reference renders progressively: one drawPixel launch per sample (kernel.cu:702-737), the
+ * whole render state in two device buffers between launches -- randState_device, the per-pixel
+ * XORWOW state (setupCurand, kernel.cu:527-533), and imgBuffer_device, the per-pixel f64 running
+ * mean m*(n-1)/n + L/n (kernel.cu:535-553).  An accumulator keeps exactly that state (48 B per
+ * pixel: 24 B XORWOW after the pixel's last finished sample, 24 B f64 mean) on the context's device,
+ * and pt_accum_add runs the NEXT spp samples of every pixel on top of it -- a pass of the wavefront
+ * kernels that continues each pixel's stream and mean.  A render built up in passes equals the
+ * one-shot pt_render of the same total in every bit; the state can be written to a file and loaded
+ * into another process.  The reference's loop, kernel.cu:709-736, is
+ *     for (i = 1; i < NUM_SAMPLES; ++i) pt_accum_add(acc, 1, NULL, NULL, NULL);
+ *
+ * pt_accum_create fixes everything in `params` except spp (ignored) and the camera, validates them
+ * as pt_render_device_async does, and allocates the state with 0 samples done.  Accumulation runs on
+ * the wavefront kernels only: both integrators, flags drawn from 0, PT_FLAG_NO_DEAD_PATH_SKIP and
+ * PT_FLAG_NO_PRIMARY_CACHE.  Whatever would take another kernel is refused here with PT_E_INVALID
+ * (never a silent fall-back): PT_FLAG_REFERENCE_TRAVERSAL, PT_FLAG_REFERENCE_BVH, PT_FLAG_COUNT, a
+ * camera farther than 64 scene extents from the origin, integrator 1 with PT_HEAD_WF=0, a
+ * non-default PT_WF_MIN_WAVES / PT_HEAD_MIN_WAVES.  An accumulator belongs to one context (one
+ * shard: shard_index / shard_count are fixed params; a multi-GPU job keeps one accumulator per
+ * shard and reduces d_out as for pt_render_device) and is destroyed before it.
+ *
+ * pt_accum_add renders samples N+1 .. N+spp of every pixel of the shard (N = pt_accum_samples).
+ * Blocking; refuses to run while asynchronous renders are in flight.  d_out: a DEVICE buffer
+ * W*H*3 on `stream` or NULL; if given, this shard's pixels receive the fp32 mean after N+spp
+ * samples (params->pixel_order), other pixels are untouched.  `stats` describes this pass alone
+ * (the primary-hit memo is re-traced once per pixel per pass, so rays_traced summed over passes may
+ * exceed a one-shot render's; samples and rays_reference do not).  spp = 0: a no-op.  A total
+ * beyond 2^30 - 1 samples is PT_E_INVALID.  If a pass fails, the state is undefined: destroy it.
+ *
+ * pt_accum_read copies to HOST buffers (either may be NULL), both W*H*3 in params->pixel_order,
+ * pixels outside the shard 0: out_rgb the fp32 mean as pt_render returns it, out_mean the f64
+ * running mean itself (the reference's imgBuffer; pt_write_ppm_f64 takes it).
+ *
+ * Checkpoint file (pt_accum_save / pt_accum_load / pt_accum_file_info), little-endian:
+ *   offset  0  char[8]   magic "PTACCUM\0"
+ *           8  uint32    format version (1)
+ *          12  uint32    header size in bytes (128)
+ *          16  pt_params 56 B as laid out above (seed at +24; spp = 0; 4 bytes of zero padding last)
+ *          72  pt_camera 32 B
+ *         104  int64     samples done
+ *         112  uint64    FNV-1a digest of the scene arrays the context was created from (verts, tris,
+ *                        mats, lights, total_light_area, bvh, spheres, in that order)
+ *         120  uint32    num_tris
+ *         124  uint32    num_spheres
+ *         128  W*H records in scanline order (pixel (x,y) at y*W + x), 48 B each: six uint32
+ *              (XORWOW v0..v4, d) and three f64 (the mean r, g, b); pixels outside the shard all zero.
+ * pt_accum_load fails with PT_E_IO for an unreadable or truncated file, PT_E_INVALID for a wrong
+ * magic, version, header size or a file longer than its records, PT_E_SCENE when the digest or the
+ * counts differ from the context's scene.  pt_accum_file_info is host-only: it reads and validates
+ * the header and the file's size; any out pointer may be NULL. */
+typedef struct pt_accum pt_accum;
+pt_accum* pt_accum_create(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, int* err);
+int pt_accum_add(pt_accum* acc, int32_t spp, float* d_out, void* stream, pt_stats* stats);
+int64_t pt_accum_samples(const pt_accum* acc);
+int pt_accum_read(pt_accum* acc, float* out_rgb, double* out_mean);
+int pt_accum_save(pt_accum* acc, const char* path);
+pt_accum* pt_accum_load(pt_ctx* ctx, const char* path, int* err);
+int pt_accum_file_info(const char* path, pt_params* params, pt_camera* cam, int64_t* samples, uint64_t* scene_digest);
+void pt_accum_destroy(pt_accum* acc);
+
 /* The reference's trace() (kernel.cu:112-161) for n rays given as rays[6n] = {o.xyz, d.xyz}
  * (host buffers): tri_out[i] = winning ORIGINAL triangle index or -1, t_out[i] = its closestT
  * (MAX_FLOAT = 1e5 on a miss).  flags: 0 = the render path's walk, PT_FLAG_REFERENCE_BVH = the
