@@ -80,6 +80,21 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+PT_FEATURE_EMISSIVE = 0x40000000   # pt_feature.prim bit: the hit material emits
+PT_DENOISE_NO_DEMODULATE = 0x1
+
+
+class Feature(C.Structure):   # pt_feature, 48 B
+    _fields_ = [("albedo", C.c_float * 3), ("depth", C.c_float), ("normal", C.c_float * 3), ("prim", C.c_int32),
+                ("position", C.c_float * 3), ("reserved", C.c_float)]
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("normal_power_log2", C.c_int32), ("sigma_depth", C.c_float),
+                ("sigma_color", C.c_float), ("flags", C.c_uint32)]
+
+
+assert C.sizeof(Feature) == 48
 assert C.sizeof(Vec3) == 12 and C.sizeof(Triangle) == 28 and C.sizeof(Material) == 48
 assert C.sizeof(BvhNode) == 32 and C.sizeof(Camera) == 32
 
@@ -135,6 +150,13 @@ SIGNATURES = {
     "pt_accum_file_info": (C.c_int, [C.c_char_p, C.POINTER(Params), C.POINTER(Camera), C.POINTER(C.c_int64),
                                      C.POINTER(C.c_uint64)]),
     "pt_accum_destroy": (None, [C.c_void_p]),
+    "pt_denoise_defaults": (None, [C.POINTER(DenoiseParams)]),
+    "pt_render_features_device": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.c_void_p, C.c_void_p]),
+    "pt_render_features": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.c_void_p]),
+    "pt_denoise_device": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                             C.c_void_p]),
     "pt_destroy": (None, [C.c_void_p]),
 }
 

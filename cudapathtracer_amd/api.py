@@ -27,6 +27,16 @@ TRI = np.dtype([("v0", "<i4"), ("v1", "<i4"), ("v2", "<i4"), ("nx", "<f4"), ("ny
 MAT = np.dtype([("albedo", "<f8", (3,)), ("emission", "<f8", (3,))])
 NODE = np.dtype([("lo", "<f4", (3,)), ("hi", "<f4", (3,)), ("left", "<u4"), ("right", "<u4")])
 SPHERE = np.dtype([("pos", "<f4", (3,)), ("rad", "<f4"), ("diffuse", "<f8", (3,)), ("emission", "<f8", (3,))])
+FEATURE = np.dtype([("albedo", "<f4", (3,)), ("depth", "<f4"), ("normal", "<f4", (3,)), ("prim", "<i4"),
+                    ("position", "<f4", (3,)), ("reserved", "<f4")])   # pt_feature, 48 B
+assert FEATURE.itemsize == 48
+
+
+def denoise_defaults():
+    """pt_denoise_defaults as a dict."""
+    dp = L.DenoiseParams()
+    L.lib().pt_denoise_defaults(C.byref(dp))
+    return {k: getattr(dp, k) for k, _ in dp._fields_}
 
 
 def _arr(ptr, n, dtype):
@@ -296,6 +306,62 @@ class Renderer:
         if not h:
             L.check(err.value if err.value != 0 else L.PT_E_IO)
         return Accumulator(self, h, accum_file_info(path)["params"])
+
+    def features(self, cam, width, height, pixel_order=0, shard_index=0, shard_count=1, tile=0):
+        """Primary-hit feature buffers (pt_render_features): a FEATURE structured array of shape (H, W) -- (W*H,)
+        in Morton order -- with albedo, depth, normal, prim and position of each pixel's pinhole camera ray.
+        Pixels outside the shard are all zero with prim = -1.  `tile`: one int or (tile_w, tile_h); 0 = 8."""
+        tw, th = (tile, tile) if np.isscalar(tile) else tile
+        p = self.params(width, height, 0, 1, 0, 0, 0, shard_index, shard_count, pixel_order, tw, th)
+        shape = (height * width,) if pixel_order == L.PT_ORDER_MORTON else (height, width)
+        out = np.zeros(shape, dtype=FEATURE)
+        L.check(L.lib().pt_render_features(self._h, C.byref(p), C.byref(cam), out.ctypes.data))
+        return out
+
+    def features_device(self, cam, d_feat_ptr, width, height, pixel_order=0, shard_index=0, shard_count=1, tile=0,
+                        stream_ptr=None):
+        """This shard's features into a caller-owned device buffer of W*H 48-byte records (16-byte aligned);
+        records of other pixels are left untouched."""
+        tw, th = (tile, tile) if np.isscalar(tile) else tile
+        p = self.params(width, height, 0, 1, 0, 0, 0, shard_index, shard_count, pixel_order, tw, th)
+        L.check(L.lib().pt_render_features_device(self._h, C.byref(p), C.byref(cam), C.c_void_p(int(d_feat_ptr)),
+                                                  None if stream_ptr is None else C.c_void_p(int(stream_ptr))))
+
+    @staticmethod
+    def denoise_params(iterations=5, normal_power_log2=5, sigma_depth=0.02, sigma_color=0.0, demodulate=True):
+        dp = L.DenoiseParams()
+        dp.iterations, dp.normal_power_log2 = int(iterations), int(normal_power_log2)
+        dp.sigma_depth, dp.sigma_color = float(sigma_depth), float(sigma_color)
+        dp.flags = 0 if demodulate else L.PT_DENOISE_NO_DEMODULATE
+        return dp
+
+    def denoise(self, img, features, iterations=5, normal_power_log2=5, sigma_depth=0.02, sigma_color=0.0,
+                demodulate=True, pixel_order=0):
+        """The edge-avoiding a-trous filter (pt_denoise) over a mean image as render returns it, guided by
+        `features` (features() of the same size and pixel order); returns the filtered image, same shape."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        feat = np.ascontiguousarray(features, dtype=FEATURE)
+        if pixel_order == L.PT_ORDER_MORTON:
+            n = img.size // 3
+            w = h = int(round(n ** 0.5))
+        else:
+            h, w = img.shape[:2]
+        if feat.size != w * h or img.size != w * h * 3:
+            raise ValueError("denoise: image and features differ in size")
+        dp = self.denoise_params(iterations, normal_power_log2, sigma_depth, sigma_color, demodulate)
+        out = np.empty_like(img)
+        L.check(L.lib().pt_denoise(self._h, C.byref(dp), w, h, int(pixel_order), img.ctypes.data, feat.ctypes.data,
+                                   out.ctypes.data))
+        return out
+
+    def denoise_device(self, d_in_ptr, d_feat_ptr, d_out_ptr, width, height, iterations=5, normal_power_log2=5,
+                       sigma_depth=0.02, sigma_color=0.0, demodulate=True, pixel_order=0, stream_ptr=None):
+        """pt_denoise_device on raw device pointers (d_out_ptr may equal d_in_ptr); blocking."""
+        dp = self.denoise_params(iterations, normal_power_log2, sigma_depth, sigma_color, demodulate)
+        L.check(L.lib().pt_denoise_device(self._h, C.byref(dp), int(width), int(height), int(pixel_order),
+                                          C.c_void_p(int(d_in_ptr)), C.c_void_p(int(d_feat_ptr)),
+                                          C.c_void_p(int(d_out_ptr)),
+                                          None if stream_ptr is None else C.c_void_p(int(stream_ptr))))
 
     def tonemap(self, img):
         """Output step on the GPU: (H, W, 3) float32 mean image -> int32 codes equal to

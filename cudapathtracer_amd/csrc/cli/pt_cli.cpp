@@ -24,6 +24,13 @@
 // --pass-spp K                            render in passes of K samples (the reference's progressive
 //                                         loop, kernel.cu:709-736), rewriting --out / --pfm /
 //                                         --checkpoint after each and printing its "sample %d" line
+// --denoise [ITERS]                       filter the image with the edge-avoiding a-trous denoiser (pt_denoise,
+//                                         ITERS iterations, default 5) before the PPM / PFM is written -- also
+//                                         after every --pass-spp pass, after --resume and after the multi-GPU
+//                                         reduce (features and filter then run for the whole frame on GPU 0)
+// --aov PREFIX                            write the primary-hit feature buffers as PREFIX_albedo.pfm,
+//                                         PREFIX_normal.pfm, PREFIX_position.pfm and PREFIX_depth.pfm (depth
+//                                         replicated to 3 channels)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -51,7 +58,10 @@ struct Obj {
             "              [--integrator unidir|head] [--seed S] [--cam X,Y,Z] [--dist D] [--focal F]\n"
             "              [--radius R] [--gpus N] [--out image.ppm] [--pfm image.pfm] [--quiet]\n"
             "              [--tri-counts out.csv [--reference-walk]] [--morton] [--tile WxH]\n"
-            "              [--checkpoint FILE] [--resume FILE] [--pass-spp K]\n");
+            "              [--checkpoint FILE] [--resume FILE] [--pass-spp K]\n"
+            "              [--denoise [ITERS]] [--aov PREFIX]\n"
+            "  --denoise [ITERS]  filter the image (edge-avoiding a-trous, ITERS iterations, default 5) before it is written\n"
+            "  --aov PREFIX       write PREFIX_albedo.pfm, PREFIX_normal.pfm, PREFIX_position.pfm, PREFIX_depth.pfm\n");
     exit(2);
 }
 
@@ -100,6 +110,10 @@ int main(int argc, char** argv)
     bool quiet = false, ref_walk = false;
     std::string tri_csv, checkpoint, resume;
     int pass_spp = 0;
+    bool denoise = false;
+    pt_denoise_params dparams;
+    pt_denoise_defaults(&dparams);
+    std::string aov;
     std::vector<std::string> given;   // the options on the command line (a resumed file may contradict them)
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -138,6 +152,12 @@ int main(int argc, char** argv)
         else if (a == "--checkpoint") checkpoint = next();
         else if (a == "--resume") resume = next();
         else if (a == "--pass-spp") { pass_spp = atoi(next().c_str()); if (pass_spp < 1) usage("--pass-spp must be >= 1"); }
+        else if (a == "--denoise") {
+            denoise = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') dparams.iterations = atoi(argv[++i]);
+            if (dparams.iterations > 8) usage("--denoise takes 0..8 iterations");
+        }
+        else if (a == "--aov") aov = next();
         else if (a == "-h" || a == "--help") usage(nullptr);
         else usage(("unknown option " + a).c_str());
     }
@@ -208,8 +228,22 @@ int main(int argc, char** argv)
         if (!ctx[g]) return die("pt_create");
     }
     std::vector<float> img(n, 0.0f);
+    // --denoise / --aov: the whole frame's primary-hit features, once, on the first context
+    std::vector<pt_feature> feat;
+    auto features = [&]() -> bool {
+        if (!feat.empty()) return true;
+        feat.resize((size_t)p.width * p.height);
+        pt_params fp = p;
+        fp.shard_index = 0; fp.shard_count = 1;
+        return pt_render_features(ctx[0], &fp, &cam, feat.data()) == PT_OK;
+    };
     // the image files of the current `img` (after the render; with --pass-spp after every pass)
     auto write_images = [&]() -> const char* {
+        if (denoise) {
+            if (!features()) return "pt_render_features";
+            if (pt_denoise(ctx[0], &dparams, p.width, p.height, p.pixel_order, img.data(), feat.data(), img.data()) != PT_OK)
+                return "pt_denoise";
+        }
         if (p.pixel_order == PT_ORDER_MORTON) {
             // the buffer as the reference holds it (imgBuff[mortonPxltoI(x,y)]): the PPM loop of
             // kernel.cu:763-778 reads it through the Morton map
@@ -277,6 +311,21 @@ int main(int argc, char** argv)
                gpus, secs, samples / secs / 1e6, traced / secs / 1e6, reference / secs / 1e6, nominal / secs / 1e6);
     }
     if (const char* what = write_images()) return die(what);
+    if (!aov.empty()) {
+        if (!features()) return die("pt_render_features");
+        std::vector<float> plane(n);
+        const char* names[4] = {"albedo", "normal", "position", "depth"};
+        for (int which = 0; which < 4; ++which) {
+            for (int y = 0; y < p.height; ++y)
+                for (int x = 0; x < p.width; ++x) {
+                    const pt_feature& f = feat[p.pixel_order == PT_ORDER_MORTON ? (size_t)pt_morton_pxl_to_i(x, y) : (size_t)y * p.width + x];
+                    const float* v = which == 0 ? f.albedo : which == 1 ? f.normal : f.position;
+                    for (int k = 0; k < 3; ++k) plane[((size_t)y * p.width + x) * 3 + k] = which == 3 ? f.depth : v[k];
+                }
+            const std::string path = aov + "_" + names[which] + ".pfm";
+            if (pt_write_pfm(path.c_str(), plane.data(), p.width, p.height) != PT_OK) return die("--aov");
+        }
+    }
     for (pt_ctx* c : ctx) pt_destroy(c);
     pt_scene_free(s);
     return 0;

@@ -2451,8 +2451,73 @@ __global__ __launch_bounds__(256) void trace_rays(Args a, const float* __restric
     }
 }
 
+// ------------------------------------------------------------------ primary-hit features
+// pt_render_features: the camera ray of every pixel of the shard (pinhole: no lens draws), traced as
+// trace_rays<false, false> traces a ray, then the hit's material and normal as one 48-B pt_feature.
+// One lane per work slot, in the wavefront kernels' slot order (unit_pixel: a wave = one 8x8 block, so
+// its rays are coherent); slots outside the image write nothing.
+__global__ __launch_bounds__(256) void primary_features(Args a, float4* __restrict__ out)
+{
+    extern __shared__ uint32_t lds_tr[];
+    const int lane = threadIdx.x & 63;
+    Counters cnt;
+    Stack4 S;
+    uint32_t* const wave_lds = lds_tr + (threadIdx.x >> 6) * a.stack_words;
+    S.ring = wave_lds + lane;
+    S.stride = a.spill_stride;
+    const uint32_t lane_off = (blockIdx.x * blockDim.x + threadIdx.x) * 4u;
+    S.spill_base = a.spill;
+    S.lane_off = &lane_off;
+    S.off_mask = ~0u;
+    for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < a.npix; q += gridDim.x * blockDim.x) {
+        uint32_t px, py;
+        if (!unit_pixel(a, q, &px, &py)) continue;
+        V3 o, d;
+        camera_ray<false>(a.cam, px, py, false, 0.0f, 0.0f, &o, &d);
+        int32_t htri = -1;
+        float ht = kMaxFloat;
+        if (a.num_tris == 0) {
+            // spheres only
+        } else if (!((a.scene_fast != 0u) && ray_fast(o, d))) {
+            trace_slow(o, d, a.root, a.nodes, a.tris_leaf, S.spill(), S.stride, a.cull_rel, a.cull_abs, &htri, &ht,
+                       cnt.tri_counts);
+        } else {
+            W4 w;
+            if (walk4_begin(w, o, d, a.acc_root, a.cull_abs)) {
+                while (walk4_step<false>(w, o, d, a.nodes4, a.acc_tris, S, a.cull_rel, a.cull_abs, a.node_mask, cnt)) {
+                }
+                ht = w.best_t;
+                bool ok = true;
+                if (w.best_slot != kNone) {
+                    const float4 C = a.acc_tris[w.best_slot].c;
+                    htri = (int32_t)__float_as_uint(C.y);
+                    ok = ref_tested(__float_as_uint(C.w), o, d, a.rnodes, a.rparent);
+                }
+                if (!ok)
+                    trace_slow(o, d, a.root, a.nodes, a.tris_leaf, S.spill(), S.stride, a.cull_rel, a.cull_abs,
+                               &htri, &ht, cnt.tri_counts);
+            }
+        }
+        if (a.num_spheres) apply_spheres(a, o, d, &htri, &ht);
+        float4 r0 = make_float4(0.0f, 0.0f, 0.0f, ht);                       // albedo, depth
+        float4 r1 = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));       // normal, prim
+        float4 r2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);                     // position, reserved
+        if (htri >= 0) {
+            const V3 p = o + d * ht;
+            const V3 n = prim_normal(a, htri, p);
+            const DMat* m = a.mats + prim_mat(a, htri);
+            const int32_t prim = htri | ((m->emission[0] != 0.0) ? (int32_t)PT_FEATURE_EMISSIVE : 0);
+            r0 = make_float4((float)m->albedo[0], (float)m->albedo[1], (float)m->albedo[2], ht);
+            r1 = make_float4(n.x, n.y, n.z, __int_as_float(prim));
+            r2 = make_float4(p.x, p.y, p.z, 0.0f);
+        }
+        float4* rec = out + out_pixel(a, px, py) * 3;
+        rec[0] = r0; rec[1] = r1; rec[2] = r2;
+    }
+}
+
 // ------------------------------------------------------------------ host side
-#define HIP_TRY(expr)                                                                            \
+#define HIP_TRY(expr)                                                                           \
     do {                                                                                         \
         hipError_t e_ = (expr);                                                                  \
         if (e_ != hipSuccess) return pt::fail(PT_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
@@ -2626,6 +2691,7 @@ struct pt_ctx {
     uint32_t num_emis = 0;            // (0 = probe off: spheres present, too many emitters, PT_NO_LIGHT_PROBE)
     uint64_t scene_digest = 0;        // FNV-1a of the scene arrays (a checkpoint file names its scene by it)
     uint32_t scene_spheres = 0;       // ... and the sphere count of that scene
+    pt::DenoiseScratch denoise;       // pt_denoise*'s device scratch (pt_denoise.hip), grown on demand
 };
 
 int pt::ctx_device(const pt_ctx* c) { return c->device; }
@@ -3121,7 +3187,7 @@ void pt_destroy(pt_ctx* c)
     void* bufs[] = {c->nodes, c->rnodes, c->tris_leaf, c->tris_orig, c->shade, c->mats,
                     c->lights, c->jump, c->jump_bytes, c->shade_m, c->scratch_out,
                     c->nodes4, c->acc_tris, c->rparent, c->hrec,
-                    c->tone_thr, c->spheres, c->tri_counts, c->emis};
+                    c->tone_thr, c->spheres, c->tri_counts, c->emis, c->denoise.mem};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (pt_ctx::Bufs& B : c->rb)
@@ -3693,6 +3759,8 @@ void pt::ctx_scene_id(const pt_ctx* c, uint64_t* digest, uint32_t* num_tris, uin
     *num_spheres = c->scene_spheres;
 }
 int pt::ctx_in_flight(const pt_ctx* c) { return c->fl_n; }
+pt::DenoiseScratch* pt::ctx_denoise_scratch(pt_ctx* c) { return &c->denoise; }
+int pt::ctx_num_cus(const pt_ctx* c) { return c->num_cus; }
 uint32_t pt::accum_max_samples() { return kAccumMaxSamples; }
 
 int pt::copy_to_host(void* dst, const void* src, size_t bytes, void* stream_v, void** pinned, size_t* pinned_bytes)
@@ -3887,6 +3955,100 @@ extern "C" int pt_trace_counts(pt_ctx* c, uint32_t n, const float* rays, int32_t
     if (d_tri) (void)hipFree(d_tri);
     if (d_t) (void)hipFree(d_t);
     if (d_cnt) (void)hipFree(d_cnt);
+    return rc;
+}
+
+// What pt_render_features* checks before touching the device; *vp = params with the ignored fields neutral.
+static int features_check(const pt_ctx* c, const pt_params* p, const pt_camera* cam, const void* feat, pt_params* vp)
+{
+    if (!c || !p || !cam || !feat) return pt::fail(PT_E_INVALID, "pt_render_features: null argument");
+    if (c->fl_n > 0)
+        return pt::fail(PT_E_INVALID, "pt_render_features: %d asynchronous renders in flight (pt_render_wait first)", c->fl_n);
+    *vp = *p;
+    vp->spp = 0; vp->bounces = 1; vp->integrator = PT_INTEGRATOR_UNIDIR; vp->flags = 0; vp->seed = 0;
+    if (int rc = validate_render(vp, cam)) return rc;
+    if ((uint64_t)c->num_tris + (uint64_t)c->num_spheres >= (uint64_t)PT_FEATURE_EMISSIVE)
+        return pt::fail(PT_E_INVALID, "pt_render_features: %u triangles + %u spheres do not fit the 30 id bits of pt_feature.prim",
+                        c->num_tris, c->num_spheres);
+    return PT_OK;
+}
+
+extern "C" int pt_render_features_device(pt_ctx* c, const pt_params* p_in, const pt_camera* cam, pt_feature* d_feat, void* stream_v)
+{
+    pt::clear_error();
+    static_assert(sizeof(pt_feature) == 48, "pt_feature is 48 B");
+    pt_params pv;
+    if (int rc = features_check(c, p_in, cam, d_feat, &pv)) return rc;
+    if (reinterpret_cast<uintptr_t>(d_feat) % 16 != 0)
+        return pt::fail(PT_E_INVALID, "pt_render_features_device: d_feat must be 16-byte aligned");
+    const pt_params* p = &pv;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+    Args a;
+    memset(&a, 0, sizeof(a));
+    a.nodes = c->nodes; a.rnodes = c->rnodes; a.tris_leaf = c->tris_leaf; a.tris_orig = c->tris_orig;
+    a.shade = c->shade; a.mats = c->mats;
+    a.spheres = c->spheres; a.num_spheres = c->num_spheres; a.num_tris = c->num_tris;
+    a.sphere_mat_base = c->sphere_mat_base;
+    memcpy(a.root, c->root, sizeof(a.root));
+    memcpy(a.acc_root, c->acc_root, sizeof(a.acc_root));
+    a.cam.pos[0] = cam->pos.x; a.cam.pos[1] = cam->pos.y; a.cam.pos[2] = cam->pos.z;
+    a.cam.dist = cam->dist_from_film; a.cam.focal = cam->focal_length; a.cam.radius = cam->radius;
+    a.cam.w = cam->pxl_width; a.cam.h = cam->pxl_height;
+    a.w = p->width; a.h = p->height;
+    a.shard_index = p->shard_index; a.shard_count = p->shard_count;
+    const uint32_t tw = p->tile_w ? (uint32_t)p->tile_w : kTile, th = p->tile_h ? (uint32_t)p->tile_h : kTile;
+    const uint32_t tx = (p->width + tw - 1) / tw, ty = (p->height + th - 1) / th;
+    const uint32_t ntiles = tx * ty;
+    a.tiles_x = tx;
+    a.tile_w = tw; a.tile_h = th;
+    a.tile_bx = tw / kTile; a.tile_blocks = (tw / kTile) * (th / kTile);
+    a.morton_out = (p->pixel_order == PT_ORDER_MORTON) ? 1u : 0u;
+    a.ntiles_shard = (ntiles > (uint32_t)p->shard_index) ? (ntiles - (uint32_t)p->shard_index + (uint32_t)p->shard_count - 1) / (uint32_t)p->shard_count : 0;
+    a.npix = a.ntiles_shard * tw * th;
+    a.cull_rel = kCullRel;
+    a.cull_abs = c->scene_extent * 1e-4f;
+    a.scene_fast = c->scene_fast ? 1u : 0u;
+    a.node_mask = c->node4_mask;
+    a.nodes4 = c->nodes4;
+    a.acc_tris = c->acc_tris;
+    a.rparent = c->rparent;
+    a.stack_words = kWaveLdsWords;
+    const size_t lds = (size_t)a.stack_words * 4 * 4;
+    if (a.npix == 0) return PT_OK;
+    uint32_t blocks = (uint32_t)(((uint64_t)a.npix + 255) / 256);
+    const uint32_t cap = (uint32_t)c->num_cus * 8u;
+    if (blocks > cap) blocks = cap;
+    if (int rc = ensure_spill(c->rb[0], stack_words_per_lane(c) * (size_t)blocks * 256)) return rc;
+    a.spill = c->rb[0].spill;
+    a.spill_stride = blocks * 256;
+    hipLaunchKernelGGL(primary_features, dim3(blocks), dim3(256), lds, stream, a, reinterpret_cast<float4*>(d_feat));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
+    return PT_OK;
+}
+
+extern "C" int pt_render_features(pt_ctx* c, const pt_params* p, const pt_camera* cam, pt_feature* feat)
+{
+    pt::clear_error();
+    pt_params pv;
+    if (int rc = features_check(c, p, cam, feat, &pv)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = (size_t)p->width * (size_t)p->height;
+    pt_feature none;
+    memset(&none, 0, sizeof(none));
+    none.prim = -1;
+    for (size_t i = 0; i < n; ++i) feat[i] = none;   // pixels outside the shard stay like this
+    pt_feature* d_feat = nullptr;
+    auto run = [&]() -> int {
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_feat), n * sizeof(pt_feature)));
+        HIP_TRY(hipMemcpy(d_feat, feat, n * sizeof(pt_feature), hipMemcpyHostToDevice));
+        if (int rc = pt_render_features_device(c, p, cam, d_feat, nullptr)) return rc;
+        HIP_TRY(hipMemcpy(feat, d_feat, n * sizeof(pt_feature), hipMemcpyDeviceToHost));
+        return PT_OK;
+    };
+    const int rc = run();
+    if (d_feat) (void)hipFree(d_feat);
     return rc;
 }
 

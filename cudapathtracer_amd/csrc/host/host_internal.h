@@ -54,6 +54,15 @@ void ctx_scene_id(const pt_ctx* c, uint64_t* digest, uint32_t* num_tris, uint32_
 int ctx_in_flight(const pt_ctx* c);
 uint32_t accum_max_samples();
 
+// ---- the denoiser (pt_denoise.hip) keeps its device scratch in the render context (pt_render.hip), which
+// frees it in pt_destroy
+struct DenoiseScratch {
+    void* mem = nullptr;
+    size_t bytes = 0;
+};
+DenoiseScratch* ctx_denoise_scratch(pt_ctx* c);
+int ctx_num_cus(const pt_ctx* c);
+
 // ---- OBJ/MTL ingest with tinyobj 0.9.13 semantics (tiny_obj_loader.cc) ------------------
 // Only what loadOBJ (modelLoader.h:125-210) consumes is kept: positions, per-triangle
 // indices, per-triangle material ids, material diffuse/emission.  Vertex dedupe keys still

@@ -15,6 +15,9 @@
  *        pt_create       <- the uploads of kernel.cu:637-700 (scene, camera, BVH to device)
  *        pt_render       <- setupCurand (kernel.cu:527-533, :639) + setupImgBuffer (:520-526, :662)
  *                           + the NUM_SAMPLES-1 launches of drawPixel (kernel.cu:535-553, :709-736)
+ *        pt_accum_*      <- the progressive loop's state between launches (kernel.cu:527-553, 702-737)
+ *        pt_render_features / pt_denoise  (no counterpart in the reference) per-pixel first-hit feature
+ *                           buffers and an edge-avoiding a-trous filter: a preview from a few samples per pixel
  *        pt_destroy      <- cudaFree (kernel.cu:782-783)
  *        pt_last_error   <- checkError (kernel.cu:37-42), but returned instead of printed
  *
@@ -329,6 +332,76 @@ int pt_tri_counts(pt_ctx* ctx, uint32_t* counts, uint32_t n);
  * pt_tonemap: host buffers, negatives handled. */
 int pt_tonemap_device(pt_ctx* ctx, const float* d_rgb, int width, int height, int32_t* d_codes, void* stream);
 int pt_tonemap(pt_ctx* ctx, const float* rgb, int width, int height, int32_t* codes);
+
+/* ------------------------------------------- primary-hit feature buffers and the preview denoiser
+ * What a progressive renderer shows after 1, 2 or 4 samples per pixel is mostly noise.  Two additions
+ * turn it into a preview: the per-pixel features of the camera ray's first hit, and a feature-guided,
+ * edge-avoiding a-trous filter over the fp32 mean image (hand-written gfx950 kernels, pt_denoise.hip).
+ *
+ * pt_render_features*: one pt_feature per pixel.  Uses width, height, pixel_order, shard_index,
+ * shard_count, tile_w and tile_h of `params` (validated as pt_render_device validates them, including the
+ * refusal while asynchronous renders are in flight) and ignores spp, bounces, integrator, seed and flags.
+ * The ray of pixel (x, y) is pt_camera_ray(cam, pt_morton_pxl_to_i(x, y), lens = 0, ...) -- a thin-lens
+ * camera still gets its pinhole ray, the features are the sharp ones -- traced by the render path's own
+ * walk (what pt_trace(flags = 0) runs: the reference's trace() bit for bit); hit ids as pt_trace's (the
+ * original triangle index, num_tris + i for sphere i).  A scene with num_tris + num_spheres >= 2^30 is
+ * PT_E_INVALID (the id shares its word with PT_FEATURE_EMISSIVE).  Records are indexed like the image
+ * (params->pixel_order).  _device: d_feat is a device buffer of W*H records, 16-byte aligned (PT_E_INVALID
+ * otherwise); only this shard's pixels are written, all others are left untouched.
+ * Host variant: pixels outside the shard are all zero bytes with prim = -1.  Both block.
+ *
+ * pt_denoise*: filters the whole width x height image `in` (W*H*3 fp32, as pt_render returns it) guided
+ * by `feat`, both and `out` in `pixel_order`; out may equal in.  Blocking; the scratch (64 B per pixel)
+ * grows on demand inside the context and is freed by pt_destroy.  Refused while asynchronous renders are
+ * in flight.  PT_E_INVALID: null pointers, sizes <= 0, iterations outside 0..8, normal_power_log2
+ * outside 0..7, a non-finite or <= 0 sigma_depth, unknown flags, Morton order on a non-square or
+ * non-power-of-two image.
+ *
+ * The filter's arithmetic (all f32, every operation rounded on its own, no contraction, IEEE division;
+ * max(a, b) below is `b > a ? b : a`, so a NaN second operand gives the first):
+ *   pass-through: pixel p with prim < 0 or prim & PT_FEATURE_EMISSIVE keeps its input bit for bit and
+ *     contributes to no neighbour.  iterations = 0: every pixel keeps its input bit for bit.
+ *   demodulation: a_p[k] = max(1e-3f, albedo[k]) (1 with PT_DENOISE_NO_DEMODULATE), c_p[k] = in_p[k] / a_p[k],
+ *     s_p = sigma_depth * depth_p.
+ *   iteration it = 0 .. iterations-1, step = 1 << it, h = {1/16, 1/4, 3/8, 1/4, 1/16}; for j = -2..2
+ *     (outer), i = -2..2 (inner), q = (x + i*step, y + j*step), skipped when outside the image or
+ *     pass-through:
+ *       dn = max(0, (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z);  wn = dn squared normal_power_log2 times
+ *       e  = (n_p.x*(P_q.x-P_p.x) + n_p.y*(P_q.y-P_p.y)) + n_p.z*(P_q.z-P_p.z)
+ *       r  = e / s_p;  wz = 1 / (1 + r*r);  w = ((h[j]*h[i]) * wn) * wz
+ *       sigma_color > 0: dc = ((D0*D0 + D1*D1) + D2*D2) over D = c_q - c_p, sc = sigma_color / (float)(1 << it),
+ *                        w = w * (1 / (1 + dc / (sc*sc)))
+ *       acc[k] = acc[k] + w*c_q[k];  wsum = wsum + w
+ *     c'_p[k] = acc[k] / wsum if wsum > 0, else c_p[k] (also when wsum is NaN).  Every pixel of iteration
+ *     it reads the image of iteration it - 1.
+ *   output: out_p[k] = c_p[k] * a_p[k].
+ * The edge-stopping weights are rational on purpose (no exp): a numpy restatement agrees in every bit. */
+#define PT_FEATURE_EMISSIVE 0x40000000   /* OR'ed into prim when the hit material has emission[0] != 0 */
+typedef struct {            /* 48 B, static_assert'ed */
+    float albedo[3];        /* (float) of mats[mat].albedo / sphere diffuse; 0 on a miss          */
+    float depth;            /* trace()'s closestT of the camera ray; 1e5 (MAX_FLOAT) on a miss     */
+    float normal[3];        /* tris[id].norm, or (position - pos)/rad for a sphere; 0 on a miss    */
+    int32_t prim;           /* -1 miss (test prim < 0 first); else hit id [| PT_FEATURE_EMISSIVE]  */
+    float position[3];      /* o + d*depth, each component (o + (d*depth)) in f32; 0 on a miss     */
+    float reserved;         /* written as 0 */
+} pt_feature;
+
+#define PT_DENOISE_NO_DEMODULATE 0x1u
+typedef struct {
+    int32_t iterations;         /* 0..8; iteration i samples at a spacing of 2^i pixels             */
+    int32_t normal_power_log2;  /* 0..7: normal weight = max(0, n_p.n_q) squared this many times    */
+    float sigma_depth;          /* > 0, finite                                                      */
+    float sigma_color;          /* <= 0: colour term off                                            */
+    uint32_t flags;             /* PT_DENOISE_NO_DEMODULATE 0x1                                     */
+} pt_denoise_params;
+void pt_denoise_defaults(pt_denoise_params* p);   /* {5, 5, 0.02f, 0.0f, 0} */
+
+int pt_render_features_device(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, pt_feature* d_feat, void* stream);
+int pt_render_features(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, pt_feature* feat /* host */);
+int pt_denoise_device(pt_ctx* ctx, const pt_denoise_params* dp, int width, int height, int pixel_order,
+                      const float* d_in, const pt_feature* d_feat, float* d_out, void* stream);
+int pt_denoise(pt_ctx* ctx, const pt_denoise_params* dp, int width, int height, int pixel_order,
+               const float* in, const pt_feature* feat, float* out /* host */);
 
 /* ----------------------------------------------------------- one process, N GPUs
  * A group of contexts on distinct devices with one RCCL communicator per device
