@@ -94,7 +94,30 @@ class DenoiseParams(C.Structure):
                 ("sigma_color", C.c_float), ("flags", C.c_uint32)]
 
 
+class NoiseParams(C.Structure):
+    _fields_ = [("tol", C.c_float), ("y_floor", C.c_float)]
+
+
+class NoiseSummary(C.Structure):
+    _fields_ = [("samples", C.c_int64), ("batches", C.c_int32), ("pixels", C.c_uint64), ("converged", C.c_uint64),
+                ("hist", C.c_uint64 * 64)]
+
+    def as_dict(self):
+        return dict(samples=int(self.samples), batches=int(self.batches), pixels=int(self.pixels),
+                    converged=int(self.converged), hist=[int(v) for v in self.hist])
+
+
+class ConvergeParams(C.Structure):
+    _fields_ = [("pass_spp", C.c_int32), ("max_samples", C.c_int32), ("min_batches", C.c_int32),
+                ("quantile", C.c_float), ("noise", NoiseParams)]
+
+
+class ConvergeResult(C.Structure):
+    _fields_ = [("passes", C.c_int32), ("stopped_converged", C.c_int32), ("last", NoiseSummary)]
+
+
 assert C.sizeof(Feature) == 48
+assert C.sizeof(NoiseSummary) == 32 + 64 * 8 and C.sizeof(ConvergeParams) == 24
 assert C.sizeof(Vec3) == 12 and C.sizeof(Triangle) == 28 and C.sizeof(Material) == 48
 assert C.sizeof(BvhNode) == 32 and C.sizeof(Camera) == 32
 
@@ -150,6 +173,15 @@ SIGNATURES = {
     "pt_accum_file_info": (C.c_int, [C.c_char_p, C.POINTER(Params), C.POINTER(Camera), C.POINTER(C.c_int64),
                                      C.POINTER(C.c_uint64)]),
     "pt_accum_destroy": (None, [C.c_void_p]),
+    "pt_noise_defaults": (None, [C.POINTER(NoiseParams)]),
+    "pt_noise_create": (C.c_void_p, [C.c_void_p, C.POINTER(C.c_int)]),
+    "pt_noise_update": (C.c_int, [C.c_void_p, C.POINTER(NoiseParams), C.c_void_p, C.POINTER(NoiseSummary)]),
+    "pt_noise_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_noise_map": (C.c_int, [C.c_void_p, C.POINTER(NoiseParams), C.c_void_p]),
+    "pt_noise_map_device": (C.c_int, [C.c_void_p, C.POINTER(NoiseParams), C.c_void_p, C.c_void_p]),
+    "pt_noise_destroy": (None, [C.c_void_p]),
+    "pt_accum_add_until": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ConvergeParams), C.c_void_p, C.c_void_p,
+                                     C.POINTER(ConvergeResult)]),
     "pt_denoise_defaults": (None, [C.POINTER(DenoiseParams)]),
     "pt_render_features_device": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.c_void_p, C.c_void_p]),
     "pt_render_features": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.c_void_p]),

@@ -39,6 +39,21 @@ def denoise_defaults():
     return {k: getattr(dp, k) for k, _ in dp._fields_}
 
 
+def noise_defaults():
+    """pt_noise_defaults as a dict (tol, y_floor)."""
+    np_ = L.NoiseParams()
+    L.lib().pt_noise_defaults(C.byref(np_))
+    return {k: getattr(np_, k) for k, _ in np_._fields_}
+
+
+def _noise_params(tol, y_floor):
+    d = noise_defaults()
+    np_ = L.NoiseParams()
+    np_.tol = float(d["tol"] if tol is None else tol)
+    np_.y_floor = float(d["y_floor"] if y_floor is None else y_floor)
+    return np_
+
+
 def _arr(ptr, n, dtype):
     if n == 0:
         return np.zeros(0, dtype=dtype)
@@ -428,8 +443,11 @@ class Accumulator:
         self._renderer = renderer   # (keeps the context alive as long as the accumulator)
         self._h = handle
         self.params = params
+        self._noise = None          # the live NoiseEstimate, if any (closed before the accumulator)
 
     def close(self):
+        if self._noise is not None:
+            self._noise.close()
         if self._h:
             L.lib().pt_accum_destroy(self._h)
             self._h = None
@@ -476,6 +494,90 @@ class Accumulator:
 
     def save(self, path):
         L.check(L.lib().pt_accum_save(self._h, str(path).encode()))
+
+    def noise(self):
+        """Attach a noise estimator (pt_noise_create): its window starts at the samples done so far.  One live
+        estimator per accumulator; closing the accumulator closes it."""
+        err = C.c_int(0)
+        h = L.lib().pt_noise_create(self._h, C.byref(err))
+        if not h:
+            L.check(err.value if err.value != 0 else L.PT_E_HIP)
+        self._noise = NoiseEstimate(self, h)
+        return self._noise
+
+    def add_until(self, pass_spp, max_samples, tol=None, quantile=0.95, min_batches=2, y_floor=None, d_out_ptr=None,
+                  stream_ptr=None):
+        """Add passes of pass_spp samples until `quantile` of the pixels have a relative standard error <= tol
+        (after at least min_batches passes), or the total reaches max_samples (pt_accum_add_until).  Uses the
+        live estimator, or attaches one.  Returns dict(passes, stopped_converged, samples, summary)."""
+        est = self._noise if self._noise is not None else self.noise()
+        cp = L.ConvergeParams()
+        cp.pass_spp, cp.max_samples, cp.min_batches = int(pass_spp), int(max_samples), int(min_batches)
+        cp.quantile = float(quantile)
+        cp.noise = _noise_params(tol, y_floor)
+        res = L.ConvergeResult()
+        L.check(L.lib().pt_accum_add_until(self._h, est._h, C.byref(cp),
+                                           None if d_out_ptr is None else C.c_void_p(int(d_out_ptr)),
+                                           None if stream_ptr is None else C.c_void_p(int(stream_ptr)), C.byref(res)))
+        return dict(passes=int(res.passes), stopped_converged=bool(res.stopped_converged), samples=self.samples,
+                    summary=res.last.as_dict())
+
+
+class NoiseEstimate:
+    """Per-pixel noise estimate of an accumulator (pt_noise_*): batch means of the passes added since it was
+    attached give the variance of each pixel's mean luminance; update() folds the newest pass and counts the
+    converged pixels in the same sweep."""
+
+    def __init__(self, accumulator, handle):
+        self._acc = accumulator
+        self._h = handle
+
+    def close(self):
+        if self._h:
+            L.lib().pt_noise_destroy(self._h)
+            self._h = None
+            if self._acc._noise is self:
+                self._acc._noise = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _shape(self):
+        p = self._acc.params
+        return (p.height * p.width,) if p.pixel_order == L.PT_ORDER_MORTON else (p.height, p.width)
+
+    def update(self, tol=None, y_floor=None, stream_ptr=None):
+        """Fold the samples added since the last update (if any) and return the summary dict: samples, batches,
+        pixels, converged (relative standard error <= tol) and the 64-bin histogram of the squared error."""
+        np_ = _noise_params(tol, y_floor)
+        s = L.NoiseSummary()
+        L.check(L.lib().pt_noise_update(self._h, C.byref(np_), None if stream_ptr is None else C.c_void_p(int(stream_ptr)),
+                                        C.byref(s)))
+        return s.as_dict()
+
+    def read(self):
+        """(mu, m2): the window's mean luminance and weighted sum of squared deviations, float64, shaped like the
+        image without its channel axis (pixels outside the shard 0)."""
+        mu, m2 = np.zeros(self._shape(), dtype=np.float64), np.zeros(self._shape(), dtype=np.float64)
+        L.check(L.lib().pt_noise_read(self._h, mu.ctypes.data, m2.ctypes.data))
+        return mu, m2
+
+    def error_map(self, y_floor=None):
+        """The squared relative standard error of every pixel's mean luminance, float32 (inf before two batches;
+        pixels outside the shard 0)."""
+        np_ = _noise_params(None, y_floor)
+        out = np.zeros(self._shape(), dtype=np.float32)
+        L.check(L.lib().pt_noise_map(self._h, C.byref(np_), out.ctypes.data))
+        return out
 
 
 class Group:

@@ -24,6 +24,13 @@
 // --pass-spp K                            render in passes of K samples (the reference's progressive
 //                                         loop, kernel.cu:709-736), rewriting --out / --pfm /
 //                                         --checkpoint after each and printing its "sample %d" line
+// --until-error TOL                       with --pass-spp K: attach a noise estimator (pt_noise_*) and stop as soon as
+//   [--error-quantile Q] [--min-batches B]  the fraction Q (default 0.95) of the pixels has a relative standard error
+//                                         of its mean luminance <= TOL, after at least B (default 2) passes; --spp
+//                                         (with --resume: the samples done plus --spp) is the cap.  A resumed render
+//                                         starts a fresh estimator window at the resumed state
+// --error-map FILE.pfm                    with --pass-spp K: write the squared relative standard error of every
+//                                         pixel ((float)rel2 of pt_noise_map) as a grey PFM
 // --denoise [ITERS]                       filter the image with the edge-avoiding a-trous denoiser (pt_denoise,
 //                                         ITERS iterations, default 5) before the PPM / PFM is written -- also
 //                                         after every --pass-spp pass, after --resume and after the multi-GPU
@@ -32,6 +39,7 @@
 //                                         PREFIX_normal.pfm, PREFIX_position.pfm and PREFIX_depth.pfm (depth
 //                                         replicated to 3 channels)
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -60,6 +68,10 @@ struct Obj {
             "              [--tri-counts out.csv [--reference-walk]] [--morton] [--tile WxH]\n"
             "              [--checkpoint FILE] [--resume FILE] [--pass-spp K]\n"
             "              [--denoise [ITERS]] [--aov PREFIX]\n"
+            "              [--until-error TOL [--error-quantile Q] [--min-batches B]] [--error-map FILE.pfm]\n"
+            "  --until-error TOL  with --pass-spp: stop once the fraction Q (default 0.95) of the pixels has a relative\n"
+            "                     standard error <= TOL after at least B (default 2) passes; --spp is the cap\n"
+            "  --error-map FILE   with --pass-spp: write the per-pixel squared relative standard error as a grey PFM\n"
             "  --denoise [ITERS]  filter the image (edge-avoiding a-trous, ITERS iterations, default 5) before it is written\n"
             "  --aov PREFIX       write PREFIX_albedo.pfm, PREFIX_normal.pfm, PREFIX_position.pfm, PREFIX_depth.pfm\n");
     exit(2);
@@ -114,6 +126,11 @@ int main(int argc, char** argv)
     pt_denoise_params dparams;
     pt_denoise_defaults(&dparams);
     std::string aov;
+    bool until_error = false;
+    std::string error_map;
+    pt_converge_params conv{};
+    conv.min_batches = 2; conv.quantile = 0.95f;
+    pt_noise_defaults(&conv.noise);
     std::vector<std::string> given;   // the options on the command line (a resumed file may contradict them)
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -158,6 +175,10 @@ int main(int argc, char** argv)
             if (dparams.iterations > 8) usage("--denoise takes 0..8 iterations");
         }
         else if (a == "--aov") aov = next();
+        else if (a == "--until-error") { until_error = true; conv.noise.tol = strtof(next().c_str(), nullptr); }
+        else if (a == "--error-quantile") conv.quantile = strtof(next().c_str(), nullptr);
+        else if (a == "--min-batches") conv.min_batches = atoi(next().c_str());
+        else if (a == "--error-map") error_map = next();
         else if (a == "-h" || a == "--help") usage(nullptr);
         else usage(("unknown option " + a).c_str());
     }
@@ -170,6 +191,12 @@ int main(int argc, char** argv)
     if (ref_walk) p.flags |= PT_FLAG_REFERENCE_TRAVERSAL | PT_FLAG_NO_PRIMARY_CACHE | PT_FLAG_NO_DEAD_PATH_SKIP;
     cam.pxl_width = p.width;
     cam.pxl_height = p.height;
+    const bool estimate = until_error || !error_map.empty();
+    if (estimate && gpus != 1) usage("--until-error / --error-map need --gpus 1 (one estimator per accumulator)");
+    if (estimate && pass_spp < 1) usage("--until-error / --error-map need --pass-spp K (the passes are the batches)");
+    if (!(conv.noise.tol > 0.0f)) usage("--until-error takes a tolerance > 0");
+    if (!(conv.quantile > 0.0f && conv.quantile <= 1.0f)) usage("--error-quantile is in (0, 1]");
+    if (conv.min_batches < 2) usage("--min-batches must be >= 2");
     const bool accumulate = !checkpoint.empty() || !resume.empty() || pass_spp > 0;
     if (accumulate && gpus != 1) usage("--checkpoint / --resume / --pass-spp need --gpus 1 (one accumulator per shard)");
     if (accumulate && (!tri_csv.empty() || ref_walk)) usage("--tri-counts and --reference-walk do not accumulate");
@@ -271,13 +298,33 @@ int main(int argc, char** argv)
         pt_accum* acc = resume.empty() ? pt_accum_create(ctx[0], &p, &cam, &err) : pt_accum_load(ctx[0], resume.c_str(), &err);
         if (!acc) return die(resume.empty() ? "pt_accum_create" : "--resume");
         const int step = pass_spp > 0 ? pass_spp : (p.spp > 0 ? p.spp : 1);
-        for (int left = p.spp; left > 0; left -= step) {
+        pt_noise* noise = nullptr;
+        if (estimate) {
+            noise = pt_noise_create(acc, &err);
+            if (!noise) return die("pt_noise_create");
+            if (!resume.empty() && !quiet)
+                printf("noise estimate: a fresh window starts at the resumed state (%lld samples)\n", (long long)pt_accum_samples(acc));
+        }
+        bool converged = false;
+        for (int left = p.spp; left > 0 && !converged; left -= step) {
             pt_stats ps{};
             if (pt_accum_add(acc, left < step ? left : step, nullptr, nullptr, &ps) != PT_OK) return die("pt_accum_add");
             st.samples += ps.samples; st.rays_traced += ps.rays_traced; st.rays_reference += ps.rays_reference;
             st.rays_nominal += ps.rays_nominal;
             if (pass_spp > 0 && !quiet) printf("sample %lld\n", (long long)pt_accum_samples(acc));   // kernel.cu:731
-            if (pass_spp > 0 && left > step) {   // (the last pass's files are written below)
+            if (noise) {
+                // pt_accum_add_until's loop, spelled out here for the per-pass stats, lines and files: fold the pass,
+                // then its stop rule
+                pt_noise_summary ns;
+                if (pt_noise_update(noise, &conv.noise, nullptr, &ns) != PT_OK) return die("pt_noise_update");
+                converged = until_error && ns.batches >= conv.min_batches &&
+                            ns.converged >= (uint64_t)ceil((double)conv.quantile * (double)ns.pixels);
+                if (!quiet)
+                    printf("converged %llu of %llu pixels (%.4f) at tolerance %g after %d batches\n", (unsigned long long)ns.converged,
+                           (unsigned long long)ns.pixels, ns.pixels ? (double)ns.converged / (double)ns.pixels : 0.0,
+                           (double)conv.noise.tol, ns.batches);
+            }
+            if (pass_spp > 0 && left > step && !converged) {   // (the last pass's files are written below)
                 if (pt_accum_read(acc, img.data(), nullptr) != PT_OK) return die("pt_accum_read");
                 if (const char* what = write_images()) return die(what);
                 if (!checkpoint.empty() && pt_accum_save(acc, checkpoint.c_str()) != PT_OK) return die("--checkpoint");
@@ -285,6 +332,21 @@ int main(int argc, char** argv)
         }
         if (pt_accum_read(acc, img.data(), nullptr) != PT_OK) return die("pt_accum_read");
         if (!checkpoint.empty() && pt_accum_save(acc, checkpoint.c_str()) != PT_OK) return die("--checkpoint");
+        if (until_error)   // (printed with --quiet too: it is the run's result)
+            printf("stopped at %lld samples: %s\n", (long long)pt_accum_samples(acc),
+                   converged ? "converged" : "not converged (the sample cap)");
+        if (!error_map.empty()) {
+            const size_t npix = (size_t)p.width * p.height;
+            std::vector<float> rel2(npix), grey(npix * 3);
+            if (pt_noise_map(noise, &conv.noise, rel2.data()) != PT_OK) return die("pt_noise_map");
+            for (int y = 0; y < p.height; ++y)
+                for (int x = 0; x < p.width; ++x) {
+                    const float v = rel2[p.pixel_order == PT_ORDER_MORTON ? (size_t)pt_morton_pxl_to_i(x, y) : (size_t)y * p.width + x];
+                    for (int k = 0; k < 3; ++k) grey[((size_t)y * p.width + x) * 3 + k] = v;
+                }
+            if (pt_write_pfm(error_map.c_str(), grey.data(), p.width, p.height) != PT_OK) return die("--error-map");
+        }
+        pt_noise_destroy(noise);
         pt_accum_destroy(acc);
     } else {
         // one GPU: pt_render; N GPUs: image-tile shards on devices 0..N-1 summed by one RCCL reduce

@@ -5,6 +5,7 @@
 // pt::accum_pass (pt_render.hip).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -95,8 +96,14 @@ struct pt_accum {
     std::vector<uint32_t> slot_pix;   // work slot -> scanline pixel id (0xffffffff: outside the image)
     uint32_t* d_rng = nullptr;        // 6 words per slot, word-major
     double* d_mean = nullptr;         // 3 doubles per slot, channel-major
+    pt_noise* noise = nullptr;        // the live estimator attached to this accumulator (pt_noise.hip), if any
     size_t slots() const { return slot_pix.size(); }
 };
+
+pt::AccumView pt::accum_view(pt_accum* a)
+{
+    return pt::AccumView{a->ctx, &a->params, a->d_mean, &a->slot_pix, a->samples, &a->noise};
+}
 
 namespace {
 
@@ -195,6 +202,33 @@ int pt_accum_add(pt_accum* acc, int32_t spp, float* d_out, void* stream, pt_stat
 }
 
 int64_t pt_accum_samples(const pt_accum* acc) { return acc ? acc->samples : 0; }
+
+int pt_accum_add_until(pt_accum* acc, pt_noise* noise, const pt_converge_params* cp, float* d_out, void* stream,
+                       pt_converge_result* result)
+{
+    pt::clear_error();
+    if (!acc || !noise || !cp || !result) return pt::fail(PT_E_INVALID, "pt_accum_add_until: null argument");
+    if (acc->noise != noise) return pt::fail(PT_E_INVALID, "pt_accum_add_until: the estimator belongs to another accumulator");
+    if (cp->pass_spp < 1) return pt::fail(PT_E_INVALID, "pt_accum_add_until: pass_spp %d < 1", cp->pass_spp);
+    if (!(cp->quantile > 0.0f && cp->quantile <= 1.0f)) return pt::fail(PT_E_INVALID, "pt_accum_add_until: quantile must be in (0, 1]");
+    if (cp->min_batches < 2) return pt::fail(PT_E_INVALID, "pt_accum_add_until: min_batches %d < 2", cp->min_batches);
+    if (cp->max_samples < 0 || (int64_t)cp->max_samples > (int64_t)pt::accum_max_samples())
+        return pt::fail(PT_E_INVALID, "pt_accum_add_until: max_samples %d outside 0..%u", cp->max_samples, pt::accum_max_samples());
+    memset(result, 0, sizeof(*result));
+    while (acc->samples < (int64_t)cp->max_samples) {
+        const int64_t left = (int64_t)cp->max_samples - acc->samples;
+        if (int rc = pt_accum_add(acc, left < cp->pass_spp ? (int32_t)left : cp->pass_spp, d_out, stream, nullptr)) return rc;
+        if (int rc = pt_noise_update(noise, &cp->noise, stream, &result->last)) return rc;
+        ++result->passes;
+        const pt_noise_summary& s = result->last;
+        if (s.batches >= cp->min_batches && s.converged >= (uint64_t)ceil((double)cp->quantile * (double)s.pixels)) {
+            result->stopped_converged = 1;
+            return PT_OK;
+        }
+    }
+    if (result->passes == 0) return pt_noise_update(noise, &cp->noise, stream, &result->last);
+    return PT_OK;
+}
 
 int pt_accum_read(pt_accum* acc, float* out_rgb, double* out_mean)
 {

@@ -54,6 +54,18 @@ void ctx_scene_id(const pt_ctx* c, uint64_t* digest, uint32_t* num_tris, uint32_
 int ctx_in_flight(const pt_ctx* c);
 uint32_t accum_max_samples();
 
+// ---- what the noise estimator (pt_noise.hip) needs of an accumulator (pt_accum.cpp): read-only, except the
+// slot that names the accumulator's one live estimator (null: none)
+struct AccumView {
+    pt_ctx* ctx;
+    const pt_params* params;
+    const double* mean;                      // device, mean[k * slots + q]
+    const std::vector<uint32_t>* slot_pix;   // work slot -> scanline pixel id, 0xffffffff outside the image
+    int64_t samples;
+    pt_noise** noise;
+};
+AccumView accum_view(pt_accum* acc);
+
 // ---- the denoiser (pt_denoise.hip) keeps its device scratch in the render context (pt_render.hip), which
 // frees it in pt_destroy
 struct DenoiseScratch {

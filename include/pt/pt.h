@@ -16,6 +16,8 @@
  *        pt_render       <- setupCurand (kernel.cu:527-533, :639) + setupImgBuffer (:520-526, :662)
  *                           + the NUM_SAMPLES-1 launches of drawPixel (kernel.cu:535-553, :709-736)
  *        pt_accum_*      <- the progressive loop's state between launches (kernel.cu:527-553, 702-737)
+ *        pt_noise_* / pt_accum_add_until  (no counterpart in the reference) per-pixel noise estimates of an
+ *                           accumulator from batch means, and a loop that adds passes until the image converged
  *        pt_render_features / pt_denoise  (no counterpart in the reference) per-pixel first-hit feature
  *                           buffers and an edge-avoiding a-trous filter: a preview from a few samples per pixel
  *        pt_destroy      <- cudaFree (kernel.cu:782-783)
@@ -302,6 +304,86 @@ int pt_accum_save(pt_accum* acc, const char* path);
 pt_accum* pt_accum_load(pt_ctx* ctx, const char* path, int* err);
 int pt_accum_file_info(const char* path, pt_params* params, pt_camera* cam, int64_t* samples, uint64_t* scene_digest);
 void pt_accum_destroy(pt_accum* acc);
+
+/* --------------------------------------------- per-pixel noise estimates and a convergence stop
+ * An accumulator can add samples forever; a pt_noise attached to it says how noisy the image still is.
+ * The f64 mean before and after a pass gives the mean of that pass's samples, and the spread of those
+ * pass means (batch means) is an unbiased estimate of the variance of the pixel mean -- with no change
+ * to any render kernel: pt_accum_add behaves exactly as without an estimator.
+ *
+ * pt_noise_create attaches an estimator to `acc` (at most one live estimator per accumulator; it is
+ * destroyed before the accumulator).  Its window starts at the accumulator's state at that moment:
+ * prev = the current mean, n_start = n0 = pt_accum_samples, batches = 0, window weight W = 0 -- so a
+ * resumed or half-finished accumulator gets one too.  It holds 40 B per work slot on the accumulator's
+ * device (f64 planes prev[3], mu, m2 in the accumulator's slot order) plus a 4-B slot -> pixel index.
+ *
+ * The arithmetic (all f64, every operation rounded on its own, no contraction, IEEE division; integers
+ * convert to double exactly; max(a, b) is `b > a ? b : a`):
+ *   update  pt_noise_update at n1 = pt_accum_samples folds when n1 > n0 (n0: the sample count at the last
+ *           fold, or n_start).  With s = n1 - n0 and m1 the accumulator's mean, per pixel:
+ *             b[k] = (m1[k]*n1 - prev[k]*n0) / s            k = r, g, b: the mean of the pass's samples
+ *             y    = (0.2126*b[0] + 0.7152*b[1]) + 0.0722*b[2]
+ *             Wn   = W + s;   d = y - mu;   mu' = mu + d*(s/Wn);   m2' = m2 + (s*d)*(y - mu');   prev = m1
+ *           then W = Wn, n0 = n1, batches += 1.  When n1 == n0 nothing is folded; the summary is recomputed
+ *           with the given parameters (ask again with another tol).
+ *   error   batches >= 2:  var = m2 / ((batches-1) * W);  den = max(y_floor, mu);  rel2 = var / (den*den)
+ *           -- the squared relative standard error of the mean luminance over the window (no square root).
+ *           batches < 2:   rel2 = +inf for every pixel of the shard.
+ *   summary a pixel is converged iff rel2 <= (double)tol*(double)tol (NaN and inf are not).  hist[] bins
+ *           r = (float)rel2, tested in this order: r != r -> 63; !(r > 0) -> 0; inf -> 63; otherwise
+ *           clamp(((bits >> 23) & 255) - 127 + 48, 1, 62).  Work slots outside the image are not pixels.
+ *           All counts are integers: the summary does not depend on the reduction order.
+ *   map     (float)rel2 at the pixel's index in the accumulator's pixel_order.  pt_noise_map (host buffer,
+ *           W*H) writes pixels outside the shard as 0; pt_noise_map_device (device buffer on `stream`)
+ *           leaves them untouched.  pt_noise_read returns mu and m2 the same way (host, W*H each, pixels
+ *           outside the shard 0; either pointer may be NULL).
+ * Every call blocks.  PT_E_INVALID: null arguments, tol or y_floor not finite or <= 0, asynchronous
+ * renders in flight, a second estimator on one accumulator.
+ *
+ * pt_accum_add_until is a host loop over the two steps: while pt_accum_samples < max_samples it calls
+ * pt_accum_add(min(pass_spp, max_samples - samples), d_out, stream) and then pt_noise_update, and stops
+ * with stopped_converged = 1 as soon as batches >= min_batches and
+ * converged >= (uint64_t)ceil((double)quantile * (double)pixels); otherwise at max_samples with
+ * stopped_converged = 0.  `passes` counts the passes it ran and `last` is the summary of its last
+ * update (with no pass to run: one update, which only re-summarises when nothing is unfolded).
+ * PT_E_INVALID: pass_spp < 1, quantile outside (0, 1], min_batches < 2, max_samples < 0 or beyond the
+ * accumulator's 2^30 - 1, an estimator of another accumulator.  Whatever it returns, the accumulator's
+ * image is the plain render's at that sample count. */
+typedef struct pt_noise pt_noise;
+typedef struct {
+    float tol;      /* a pixel is converged when its relative standard error is <= tol; > 0, finite */
+    float y_floor;  /* luminance below which the error is taken relative to y_floor; > 0, finite    */
+} pt_noise_params;
+void pt_noise_defaults(pt_noise_params* p);   /* {0.05f, 0.01f}: design choices, not measurements */
+typedef struct {
+    int64_t samples;      /* pt_accum_samples at this update                       */
+    int32_t batches;      /* passes folded so far                                  */
+    uint64_t pixels;      /* pixels of this shard                                  */
+    uint64_t converged;   /* of those, pixels with rel2 <= tol*tol                 */
+    uint64_t hist[64];    /* pixels per power-of-two bin of (float)rel2, see above */
+} pt_noise_summary;
+
+pt_noise* pt_noise_create(pt_accum* acc, int* err);
+int pt_noise_update(pt_noise* noise, const pt_noise_params* np, void* stream, pt_noise_summary* out);
+int pt_noise_read(pt_noise* noise, double* mu, double* m2);
+int pt_noise_map(pt_noise* noise, const pt_noise_params* np, float* rel2 /* host */);
+int pt_noise_map_device(pt_noise* noise, const pt_noise_params* np, float* d_rel2, void* stream);
+void pt_noise_destroy(pt_noise* noise);
+
+typedef struct {
+    int32_t pass_spp;       /* samples per pass, >= 1                                     */
+    int32_t max_samples;    /* stop at this total (pt_accum_samples) at the latest        */
+    int32_t min_batches;    /* >= 2: no stop before this many folded passes               */
+    float quantile;         /* in (0, 1]: the fraction of the pixels that must converge   */
+    pt_noise_params noise;
+} pt_converge_params;
+typedef struct {
+    int32_t passes;             /* passes this call ran                  */
+    int32_t stopped_converged;  /* 1: the quantile converged; 0: the cap */
+    pt_noise_summary last;
+} pt_converge_result;
+int pt_accum_add_until(pt_accum* acc, pt_noise* noise, const pt_converge_params* cp, float* d_out, void* stream,
+                       pt_converge_result* result);
 
 /* The reference's trace() (kernel.cu:112-161) for n rays given as rays[6n] = {o.xyz, d.xyz}
  * (host buffers): tri_out[i] = winning ORIGINAL triangle index or -1, t_out[i] = its closestT
