@@ -2,8 +2,6 @@
 CPU: the host API and the oracle's sphere math (analytic cases, brute force).  GPU: config C1
 (a Cornell box of spheres only, 128x128) and a mixed triangle + sphere scene, bit-exact against
 the oracle for both integrators and every traversal mode; pt_trace with spheres."""
-import math
-
 import numpy as np
 import pytest
 
@@ -11,6 +9,8 @@ from conftest import load_scene
 
 import cudapathtracer_amd as pt
 from cudapathtracer_amd import scenes
+
+import light_scenes
 
 MIXED = [((0.3, 0.45, -0.2), 0.3, (0.8, 0.7, 0.2), (0.0, 0.0, 0.0)),
          ((-0.5, 1.5, 0.4), 0.15, (0.0, 0.0, 0.0), (6.0, 5.0, 4.0)),
@@ -76,7 +76,8 @@ def test_oracle_sphere_intersection_cases():
 
 def test_oracle_trace_with_spheres_equals_bruteforce():
     """trace() with spheres = min over (triangle walk result, every sphere root) with strict <
-    (triangles first): checked against a float32 numpy restatement of the sphere test."""
+    (triangles first): checked against a float32 numpy restatement of the sphere test
+    (light_scenes.sphere_trace_f32)."""
     oracle, osc = _osc(mixed_scene())
     sc = mixed_scene()
     a = sc.arrays()
@@ -89,25 +90,9 @@ def test_oracle_trace_with_spheres_equals_bruteforce():
     nt = len(a["tris"])
     # triangles only: remove spheres
     tri0, t0 = oracle.trace_batch(oracle.OracleScene({**a, "spheres": a["spheres"][:0]}), o, d)
-    f = np.float32
+    bi, bt = light_scenes.sphere_trace_f32(a["spheres"], o, d, tri0, t0, nt)
     for i in range(n):
-        bt, bi = t0[i], tri0[i]
-        for k, sp in enumerate(a["spheres"]):
-            oc = o[i] - sp["pos"].astype(np.float32)
-            b = f(f(f(oc[0] * d[i][0]) + f(oc[1] * d[i][1])) + f(oc[2] * d[i][2]))
-            cc = f(f(f(f(oc[0] * oc[0]) + f(oc[1] * oc[1])) + f(oc[2] * oc[2])) - f(sp["rad"] * sp["rad"]))
-            disc = f(f(b * b) - cc)
-            if not disc >= 0:
-                continue
-            q = f(math.sqrt(disc))
-            ts = f(-b - q)
-            if not ts > 0:
-                ts = f(-b + q)
-                if not ts > 0:
-                    continue
-            if 0 < ts < bt:
-                bt, bi = ts, nt + k
-        assert tri[i] == bi and t[i] == bt, i
+        assert tri[i] == bi[i] and t[i] == bt[i], i
 
 
 @pytest.mark.gpu
