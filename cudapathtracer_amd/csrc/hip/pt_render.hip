@@ -19,13 +19,15 @@
 #include <vector>
 
 #include "../host/host_internal.h"
+#include "../host/render_plan.h"
 #include "pt_device.h"
+#include "pt_scene_pack.h"
 
 using namespace ptd;
 
 namespace {
 
-constexpr uint32_t kTile = 8;   // 8x8 = 64 pixels = one wave
+constexpr uint32_t kTile = pt::kTile;   // 8x8 = 64 pixels = one wave
 
 // A box is skipped when its entry lies beyond best_t * kCullRel (DESIGN.md "Traversal" 4)
 constexpr float kCullRel = 1.0f + 1.0f / 1024.0f;
@@ -43,7 +45,7 @@ struct Args {
     const uint32_t* seed_states;    // curand_init(seed, s0, 0) for s0 < 256: v0..v4 (kJumpEntryWords
                                     // words each; seed_table), with jump_bytes
     float* out;
-    unsigned long long* counters;   // [0] traced [1] reference [2] nodes [3] tris [4] samples
+    unsigned long long* counters;   // kCounterWords words, slots CNT_*
     uint32_t* tile_counter;
     uint32_t num_lights;
     float total_light_area;
@@ -83,7 +85,7 @@ struct Args {
     float acc_root[6];
     uint32_t* cold;                 // per-lane shading state of the wavefront kernel (ColdRec)
     const uint32_t* pix_states;     // per work unit u, word k at [k*nunits + u] (kUnitWords, init_pixel_states)
-    uint32_t npix;                  // pixel slots of this shard (ntiles_shard * 64)
+    uint32_t npix;                  // pixel slots of this shard (ntiles_shard * tile_w * tile_h)
     uint32_t nwhole;                // slots 0..nwhole-1 are whole-pixel units (unit u = slot u); the
     uint32_t ntail;                 // ntail = npix - nwhole last slots are split: the first nmid of them
     uint32_t nmid;                  // into chunks_mid sample chunks, the rest into `chunks`; units are
@@ -122,6 +124,18 @@ struct Args {
                                     // at [k * npix + q] (a wave's 64 slots: one 256-B row per word)
     double* acc_mean;               // per pixel slot q: the f64 running mean, channel k at [k * npix + q]
 };
+// Slots of Args::counters: the kernels add to them; pt_render_wait (pt_stats, PT_SECTION_DUMP) and
+// pt_trace_counts read them.
+enum : uint32_t {
+    CNT_TRACED = 0, CNT_REFERENCE, CNT_NODES, CNT_TRIS, CNT_SAMPLES, CNT_WALK_SLOTS, CNT_LEAF_STEPS, CNT_SHADE_SLOTS,
+    CNT_FALLBACKS, CNT_WALK_CYCLES, CNT_SHADE_CYCLES, CNT_TRACE_SLOTS, CNT_START_WAIT, CNT_TOP_VISITS,
+    CNT_ITERS = 14,                     // 6 classes of walk iterations
+    CNT_T_START = 20, CNT_T_DRAINED,    // wall-clock minima (atomicMin: they start as ~0, not 0)
+    CNT_T_LAST_EXIT, CNT_T_EXIT_SUM, CNT_WAVES, CNT_SPILL, CNT_LANE_END_SUM,
+    CNT_SECTIONS = 32,                  // kSections section counts, then kHist walk-length buckets
+    CNT_LANE_BINS = 64, CNT_WAVE_BINS = 80   // kTailBins each
+};
+constexpr int kCounterWords = 96;
 // Unit words of an accumulating pass: UW_N0 bit 30 marks a pixel's first unit of the pass (chunk 0, or the
 // whole pixel) -- `n == 1` no longer does; its sample numbers are the 30 bits below.
 constexpr uint32_t kUnitFirst = 0x40000000u;
@@ -221,13 +235,13 @@ struct Tracer {
                         ok = ref_tested(__float_as_uint(C.w), o, d, a->rnodes, a->rparent);
                     }
                     if (!ok) {
-                        atomicAdd(a->counters + 8, 1ull);   // (accel_fallbacks, as trace_rays counts them)
+                        atomicAdd(a->counters + CNT_FALLBACKS, 1ull);   // (accel_fallbacks, as trace_rays counts them)
                         trace_slow(o, d, a->root, a->nodes, a->tris_leaf, S.spill(), S.stride, a->cull_rel, a->cull_abs,
                                    &h.tri, &h.t, cnt.tri_counts);
                     }
                 }
                 } else {   // outside the Markstein preconditions: the exact slow walk
-                    atomicAdd(a->counters + 8, 1ull);
+                    atomicAdd(a->counters + CNT_FALLBACKS, 1ull);
                     trace_slow(o, d, a->root, a->nodes, a->tris_leaf, S.spill(), S.stride, a->cull_rel, a->cull_abs,
                                &h.tri, &h.t, cnt.tri_counts);
                 }
@@ -545,7 +559,7 @@ __device__ __forceinline__ uint32_t morton2(uint32_t x, uint32_t y)   // camera.
 // that * shard_count, row-major over the tile grid), 8x8 block ((q >> 6) mod tile_blocks) of the tile
 // (row-major), Morton order within the block -- 64 consecutive slots (a wave's lanes) are one 8x8
 // block.  False for a slot outside the image (partial tiles at the right / bottom edge).
-// (host and device: pt_shard_pixels exports the same mapping; T = Args or TileMap)
+// (host and device: pt_shard_pixels exports the same mapping; T = Args or pt::TileGrid)
 template <typename T>
 __host__ __device__ __forceinline__ bool unit_pixel(const T& a, uint32_t q, uint32_t* px, uint32_t* py)
 {
@@ -560,11 +574,6 @@ __host__ __device__ __forceinline__ bool unit_pixel(const T& a, uint32_t q, uint
     *py = (t / a.tiles_x) * a.tile_h + by * kTile + qy;
     return *px < (uint32_t)a.w && *py < (uint32_t)a.h;
 }
-// the tile-map fields of Args, for the host
-struct TileMap {
-    int32_t w, h, shard_index, shard_count;
-    uint32_t tiles_x, tile_w, tile_h, tile_bx, tile_blocks;
-};
 // index of pixel (px, py) in the output buffer (pt_params.pixel_order)
 __device__ __forceinline__ size_t out_pixel(const Args& a, uint32_t px, uint32_t py)
 {
@@ -630,10 +639,10 @@ __global__ __launch_bounds__(64) void render_tiles(Args a)
     unsigned long long c2 = 0, c3v = 0;
     if (kCount) { c2 = wave_sum(tr.cnt.nodes); c3v = wave_sum(tr.cnt.tris); }
     if (lane == 0) {
-        atomicAdd(a.counters + 0, c0);
-        atomicAdd(a.counters + 1, c1);
-        atomicAdd(a.counters + 4, c4);
-        if (kCount) { atomicAdd(a.counters + 2, c2); atomicAdd(a.counters + 3, c3v); }
+        atomicAdd(a.counters + CNT_TRACED, c0);
+        atomicAdd(a.counters + CNT_REFERENCE, c1);
+        atomicAdd(a.counters + CNT_SAMPLES, c4);
+        if (kCount) { atomicAdd(a.counters + CNT_NODES, c2); atomicAdd(a.counters + CNT_TRIS, c3v); }
     }
 }
 
@@ -733,11 +742,8 @@ __device__ __forceinline__ uint32_t dhi(double v) { return (uint32_t)__double2hi
 enum : uint32_t { UW_PXY = 6, UW_N0, UW_NEND, UW_TQ, UW_CD, kUnitWords = UW_CD + 3 };
 constexpr uint32_t kNoPixel = 0xffffffffu;   // UW_PXY of a slot outside the image
 constexpr uint32_t kNoUnit = 0xffffffffu;
-constexpr int kCounterWords = 96;   // counters[]: 0..63 as listed, 64..95 the tail bins
-constexpr uint32_t kQueues = 8;              // unit counters (Args::unit_queues > 1)
 constexpr uint32_t kQueueBlock = 64;         // units per block of a counter's class
 constexpr uint32_t kQueueStride = 32;        // words between the counters (one 128-B line each)
-constexpr uint32_t kMaxProbeEmitters = 4;    // last-bounce light probe: at most this many emissive triangles
 // LDS of a wavefront block after the counters: the probe's emitter count (16 B) and records, then the
 // staged BVH4 top nodes
 // then the NEE light records (lights[0..num_lights], the last being "nothing picked") when at most
@@ -783,7 +789,7 @@ __global__ __launch_bounds__(256) void init_pixel_states(Args a, uint32_t* __res
     const uint32_t q = blockIdx.x * 256u + threadIdx.x;
     if (blockIdx.x == 0) {   // this render's counters, unit counters and wall-clock minima (no memset launches)
         for (uint32_t k = threadIdx.x; k < (uint32_t)kCounterWords; k += 256u)
-            a.counters[k] = (k == 20u || k == 21u) ? ~0ull : 0ull;
+            a.counters[k] = (k == CNT_T_START || k == CNT_T_DRAINED) ? ~0ull : 0ull;
         for (uint32_t k = threadIdx.x; k < kQueueStride * (kQueues + 1); k += 256u) a.pixel_counter[k] = 0u;
         if (threadIdx.x < 4) a.tile_counter[threadIdx.x] = 0u;
     }
@@ -986,8 +992,10 @@ __device__ __forceinline__ void wave_count(unsigned long long* c, int lane)
 enum : int { SEC_PASS = 0, SEC_CHECK, SEC_SLOW, SEC_BOUNCE, SEC_EMIT, SEC_COSINE, SEC_LIGHT, SEC_SAMPLE_END,
              SEC_START, SEC_CAMERA, SEC_DEAD, SEC_BEGIN, SEC_REFILL, SEC_MEMO, SEC_RECORD, SEC_PROBE, kSections = 16 };
 constexpr int kHist = 16;   // counting variant: walk steps per ray, log2 buckets (counters[48 + b])
+static_assert(CNT_SECTIONS + kSections + kHist <= CNT_LANE_BINS, "counter slots");
 constexpr int kTailBins = 16;   // counting variant: lane end / wave exit times after the queue drained,
                                 // bin k = [10 us x 2^(k-1), 10 us x 2^k) of the 100-MHz wall clock (bin 0: < 10 us)
+static_assert(CNT_LANE_BINS + kTailBins == CNT_WAVE_BINS && CNT_WAVE_BINS + kTailBins == kCounterWords, "counter slots");
 __device__ __forceinline__ uint32_t tail_bin(unsigned long long ticks)
 {
     const unsigned long long q = ticks / 1000ull;
@@ -1446,9 +1454,9 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
             if (u >= a.nunits) {
                 if (kCount) {   // queue drained; this lane's end after it and since the start (binned at the end)
                     const unsigned long long now = wall_clock64();
-                    atomicMin(a.counters + 21, now);
-                    const unsigned long long d0 = __hip_atomic_load(a.counters + 21, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const unsigned long long s0 = __hip_atomic_load(a.counters + 20, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    atomicMin(a.counters + CNT_T_DRAINED, now);
+                    const unsigned long long d0 = __hip_atomic_load(a.counters + CNT_T_DRAINED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const unsigned long long s0 = __hip_atomic_load(a.counters + CNT_T_START, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     done_rel[0] = (uint32_t)min(now - min(now, d0), 0xffffffffull);
                     done_rel[1] = (uint32_t)min(now - min(now, s0), 0xffffffffull);
                 }
@@ -1571,9 +1579,9 @@ __device__ __forceinline__ uint32_t take_unit(const Args& a, int lane, uint64_t 
     }
     if (kCount && me && u >= a.nunits) {   // queue drained; this lane's end after it and since the start
         const unsigned long long now = wall_clock64();
-        atomicMin(a.counters + 21, now);
-        const unsigned long long d0 = __hip_atomic_load(a.counters + 21, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long s0 = __hip_atomic_load(a.counters + 20, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        atomicMin(a.counters + CNT_T_DRAINED, now);
+        const unsigned long long d0 = __hip_atomic_load(a.counters + CNT_T_DRAINED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned long long s0 = __hip_atomic_load(a.counters + CNT_T_START, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         done_rel[0] = (uint32_t)min(now - min(now, d0), 0xffffffffull);
         done_rel[1] = (uint32_t)min(now - min(now, s0), 0xffffffffull);
     }
@@ -2154,7 +2162,7 @@ __device__ __forceinline__ void wf_main(const Args& a)
     const int lane = threadIdx.x & 63;
     Counters cnt;
     if (kCount) cnt.tri_counts = a.tri_counts;
-    if (kCount && threadIdx.x == 0) atomicMin(a.counters + 20, (unsigned long long)wall_clock64());   // first start
+    if (kCount && threadIdx.x == 0) atomicMin(a.counters + CNT_T_START, (unsigned long long)wall_clock64());   // first start
     uint32_t walk_slots = 0, shade_slots = 0;   // counting variant: SIMD lane-slot usage
     uint32_t trace_slots = 0, steps = 0;        // counting variant: lanes tracing per iteration; steps of this walk
     uint32_t start_wait = 0;                    // counting variant: lanes without a ray when a walk phase starts
@@ -2289,47 +2297,49 @@ __device__ __forceinline__ void wf_main(const Args& a)
     }
     if (a.lane_times && lane == 0) a.lane_times[nlanes + nlanes / 64 + wave_id] = wall_clock64();
     if (kCount) {
-        if (lane == 0) { atomicAdd(a.counters + 9, walk_clk); atomicAdd(a.counters + 10, shade_clk); }
+        if (lane == 0) { atomicAdd(a.counters + CNT_WALK_CYCLES, walk_clk); atomicAdd(a.counters + CNT_SHADE_CYCLES, shade_clk); }
         if (lane == 0) {   // wave exit times (wall clock): last, the sum for the mean, and after the drain
             const unsigned long long t = wall_clock64();
-            atomicMax(a.counters + 22, t);
-            atomicAdd(a.counters + 23, t);
-            atomicAdd(a.counters + 24, 1ull);
-            const unsigned long long d0 = __hip_atomic_load(a.counters + 21, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            atomicAdd(a.counters + 80 + tail_bin(t - min(t, d0)), 1ull);
+            atomicMax(a.counters + CNT_T_LAST_EXIT, t);
+            atomicAdd(a.counters + CNT_T_EXIT_SUM, t);
+            atomicAdd(a.counters + CNT_WAVES, 1ull);
+            const unsigned long long d0 = __hip_atomic_load(a.counters + CNT_T_DRAINED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            atomicAdd(a.counters + CNT_WAVE_BINS + tail_bin(t - min(t, d0)), 1ull);
         }
         // lane ends after the drain (log2 bins: one atomic per occupied bin and wave), and their sum
         // since the kernel's start (the tail's idle lane-time = lanes x last exit - that sum)
         const uint32_t bin = tail_bin(done_rel[0]);
         for (uint32_t k = 0; k < (uint32_t)kTailBins; ++k) {
             const uint64_t m = __ballot(bin == k);
-            if (m && lane == 0) atomicAdd(a.counters + 64 + k, (unsigned long long)__popcll(m));
+            if (m && lane == 0) atomicAdd(a.counters + CNT_LANE_BINS + k, (unsigned long long)__popcll(m));
         }
         const unsigned long long dsum = wave_sum(done_rel[1]);
-        if (lane == 0) atomicAdd(a.counters + 26, dsum);
+        if (lane == 0) atomicAdd(a.counters + CNT_LANE_END_SUM, dsum);
         const unsigned long long c2 = wave_sum(cnt.nodes), c3v = wave_sum(cnt.tris), c5 = wave_sum(walk_slots);
         const unsigned long long c13 = wave_sum(cnt.top), c25 = wave_sum(cnt.spills);
         const unsigned long long c6 = wave_sum(cnt.leaf_steps), c7 = wave_sum(shade_slots);
         const unsigned long long c11 = wave_sum(trace_slots);
         if (lane == 0) {
-            atomicAdd(a.counters + 2, c2); atomicAdd(a.counters + 3, c3v); atomicAdd(a.counters + 5, c5);
-            atomicAdd(a.counters + 6, c6); atomicAdd(a.counters + 7, c7); atomicAdd(a.counters + 11, c11);
-            atomicAdd(a.counters + 12, (unsigned long long)start_wait);
-            atomicAdd(a.counters + 13, c13);
-            atomicAdd(a.counters + 25, c25);
-            for (int k = 0; k < 6; ++k) atomicAdd(a.counters + 14 + k, (unsigned long long)itc[k]);
+            atomicAdd(a.counters + CNT_NODES, c2); atomicAdd(a.counters + CNT_TRIS, c3v); atomicAdd(a.counters + CNT_WALK_SLOTS, c5);
+            atomicAdd(a.counters + CNT_LEAF_STEPS, c6); atomicAdd(a.counters + CNT_SHADE_SLOTS, c7); atomicAdd(a.counters + CNT_TRACE_SLOTS, c11);
+            atomicAdd(a.counters + CNT_START_WAIT, (unsigned long long)start_wait);
+            atomicAdd(a.counters + CNT_TOP_VISITS, c13);
+            atomicAdd(a.counters + CNT_SPILL, c25);
+            for (int k = 0; k < 6; ++k) atomicAdd(a.counters + CNT_ITERS + k, (unsigned long long)itc[k]);
         }
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        atomicAdd(a.counters + 0, lcnt[0]);
-        atomicAdd(a.counters + 1, lcnt[1]);
-        atomicAdd(a.counters + 4, lcnt[2]);
-        if (lcnt[3]) atomicAdd(a.counters + 8, lcnt[3]);
+        // (lcnt is the block's own LDS table -- 0 traced, 1 reference, 2 samples, 3 fallbacks, as shade_lane's
+        // wave_count(lcnt + k) fills it -- not Args::counters: its indices are not CNT_*)
+        atomicAdd(a.counters + CNT_TRACED, lcnt[0]);
+        atomicAdd(a.counters + CNT_REFERENCE, lcnt[1]);
+        atomicAdd(a.counters + CNT_SAMPLES, lcnt[2]);
+        if (lcnt[3]) atomicAdd(a.counters + CNT_FALLBACKS, lcnt[3]);
     }
     if (kCount && threadIdx.x < kSections + kHist) {   // section counts, then the histogram
         const uint32_t v = reinterpret_cast<const uint32_t*>(lcnt + 4)[threadIdx.x];
-        if (v) atomicAdd(a.counters + 32 + threadIdx.x, (unsigned long long)v);
+        if (v) atomicAdd(a.counters + CNT_SECTIONS + threadIdx.x, (unsigned long long)v);
     }
 }
 
@@ -2419,7 +2429,7 @@ __global__ __launch_bounds__(256) void trace_rays(Args a, const float* __restric
             const Hit h = trace_reference<kCount>(o, d, a.rnodes, a.tris_orig, wave_lds, lane, cnt);
             htri = h.tri; ht = h.t;
         } else if (!((a.scene_fast != 0u) && ray_fast(o, d))) {
-            atomicAdd(a.counters + 8, 1ull);
+            atomicAdd(a.counters + CNT_FALLBACKS, 1ull);
             trace_slow(o, d, a.root, a.nodes, a.tris_leaf, S.spill(), S.stride, a.cull_rel, a.cull_abs, &htri, &ht,
                        cnt.tri_counts);
         } else {
@@ -2435,7 +2445,7 @@ __global__ __launch_bounds__(256) void trace_rays(Args a, const float* __restric
                     ok = ref_tested(__float_as_uint(C.w), o, d, a.rnodes, a.rparent);
                 }
                 if (!ok) {
-                    atomicAdd(a.counters + 8, 1ull);
+                    atomicAdd(a.counters + CNT_FALLBACKS, 1ull);
                     trace_slow(o, d, a.root, a.nodes, a.tris_leaf, S.spill(), S.stride, a.cull_rel, a.cull_abs,
                                &htri, &ht, cnt.tri_counts);
                 }
@@ -2447,7 +2457,7 @@ __global__ __launch_bounds__(256) void trace_rays(Args a, const float* __restric
     }
     if (kCount) {
         const unsigned long long sp = wave_sum(cnt.spills);
-        if (lane == 0 && sp) atomicAdd(a.counters + 25, sp);
+        if (lane == 0 && sp) atomicAdd(a.counters + CNT_SPILL, sp);
     }
 }
 
@@ -2523,6 +2533,20 @@ __global__ __launch_bounds__(256) void primary_features(Args a, float4* __restri
         if (e_ != hipSuccess) return pt::fail(PT_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// A device buffer grown on demand (*have counts T's): freed and allocated anew when smaller than `need`.
+// The slot is null and 0 before the hipMalloc, so a failed grow leaves it consistent.
+template <typename T>
+int grow(T** buf, size_t* have, size_t need)
+{
+    if (*have >= need) return PT_OK;
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr;
+    *have = 0;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(buf), need * sizeof(T)));
+    *have = need;
+    return PT_OK;
+}
+
 template <typename T>
 int upload(T** dst, const std::vector<T>& src)
 {
@@ -2535,59 +2559,13 @@ int upload(T** dst, const std::vector<T>& src)
 
 }  // namespace
 
-// GF(2) jump tables J_k = A^(2^(67+k)), k = 0..31, rocRAND's bit-image layout.
-static void build_jump_tables(std::vector<uint32_t>& out)
-{
-    auto apply = [](const uint32_t* img, uint32_t v[5]) {
-        uint32_t r[5] = {0, 0, 0, 0, 0};
-        for (int b = 0; b < 160; ++b)
-            if ((v[b >> 5] >> (b & 31)) & 1u)
-                for (int w = 0; w < 5; ++w) r[w] ^= img[b * 5 + w];
-        memcpy(v, r, sizeof(r));
-    };
-    std::vector<uint32_t> m(800), tmp(800);
-    for (int b = 0; b < 160; ++b) {   // one XORWOW step on the 160-bit xorshift state
-        uint32_t v[5] = {0, 0, 0, 0, 0};
-        v[b >> 5] = 1u << (b & 31);
-        const uint32_t t = v[0] ^ (v[0] >> 2);
-        uint32_t nv[5] = {v[1], v[2], v[3], v[4], (v[4] ^ (v[4] << 4)) ^ (t ^ (t << 1))};
-        memcpy(&m[b * 5], nv, sizeof(nv));
-    }
-    auto square = [&]() {
-        for (int b = 0; b < 160; ++b) {
-            uint32_t v[5];
-            memcpy(v, &m[b * 5], sizeof(v));
-            apply(m.data(), v);
-            memcpy(&tmp[b * 5], v, sizeof(v));
-        }
-        m.swap(tmp);
-    };
-    for (int i = 0; i < 67; ++i) square();
-    out.resize(32 * 800);
-    for (int k = 0; k < 32; ++k) {
-        memcpy(&out[k * 800], m.data(), 800 * sizeof(uint32_t));
-        square();
-    }
-}
-
-// Byte-sliced form of the jump tables for rng_init: entry (k, j, x) = J_k * (x << 8j).
-static void build_jump_bytes(const std::vector<uint32_t>& img, std::vector<uint32_t>& out)
-{
-    out.assign((size_t)32 * 20 * 256 * kJumpEntryWords, 0u);
-    for (int k = 0; k < 32; ++k)
-        for (int j = 0; j < 20; ++j)
-            for (int x = 0; x < 256; ++x) {
-                uint32_t* e = &out[(((size_t)k * 20 + j) * 256 + x) * kJumpEntryWords];
-                for (int i = 0; i < 8; ++i)
-                    if ((x >> i) & 1)
-                        for (int w = 0; w < 5; ++w) e[w] ^= img[(size_t)k * 800 + (8 * j + i) * 5 + w];
-            }
-}
-
 void pt::sincos_det(float theta, float* s, float* c) { det_sincos(theta, s, c); }
 
-struct pt_ctx {
+struct pt_ctx : pt::SceneInfo {            // (the scene's scalars: pt_scene_pack.h)
     int device = 0;
+    int num_cus = 256;
+    pt::RenderKnobs knobs;                 // the PT_* knobs as they were at pt_create
+    // the packed scene's arrays on the device (pt::PackedScene has the same names)
     DNode* nodes = nullptr;
     RNode* rnodes = nullptr;
     DTri* tris_leaf = nullptr;
@@ -2597,18 +2575,18 @@ struct pt_ctx {
     DLight* lights = nullptr;
     uint32_t* jump = nullptr;
     float4* shade_m = nullptr;        // merged shading records (Args::shade_m), or none
+    DNode4* nodes4 = nullptr;
+    DTri* acc_tris = nullptr;
+    uint32_t* rparent = nullptr;
+    float4* hrec = nullptr;
+    float* tone_thr = nullptr;        // output step: the host libm's 255 code boundaries (+ t[0] = 0)
+    float4* spheres = nullptr;        // sphere primitives (center, radius)
+    DTri* emis = nullptr;             // last-bounce light probe: records of the emissive triangles
+    uint32_t* tri_counts = nullptr;   // PT_FLAG_COUNT: per-triangle test counts (num_tris entries, >= 1)
     uint32_t* jump_bytes = nullptr;   // byte-position jump matrices (built on the first wavefront render)
     hipEvent_t jump_ready = nullptr;  // recorded behind their build
-    bool use_jump_bytes = true;       // PT_JUMP_BYTES=0: per-bit jumps only
-    bool tile_fast4 = true;           // PT_TILE_FAST4=0: the tile kernel walks the reference BVH (culled)
-    float* scratch_out = nullptr;
-    size_t scratch_bytes = 0;
-    uint32_t num_lights = 0;
-    float total_light_area = 0;
-    float root[6];
-    int32_t depth = 0;
-    uint32_t num_tris = 0;
-    float scene_extent = 1.0f;
+    float* scratch_out = nullptr;     // pt_render: the image on the device
+    size_t scratch_floats = 0;
     void* pinned = nullptr;                    // pt_render: pinned staging buffer of the image copy-out
     size_t pinned_bytes = 0;
     // renders in flight (pt_render_device_async / pt_render_wait): a FIFO of kFlights slots, each with
@@ -2644,53 +2622,6 @@ struct pt_ctx {
     };
     Bufs rb[kFlights];
     int fl_head = 0, fl_n = 0;                 // oldest in-flight slot, number in flight
-    int num_cus = 256;
-    bool scene_fast = false;
-    uint32_t node_mask = 0;
-    uint32_t wf_threshold = 56;     // measured best at 5 waves/SIMD (C3: 24..64 swept)
-    uint32_t wf_queues = kQueues;   // unit counters (PT_WF_QUEUES=1: one; 8: the 1/8 shard +5.8%, C3 +1.2%)
-    uint32_t wf_root_first = 4;     // a new ray's first visits (root + up to 3 staged nodes) in the shading pass
-                                    // (PT_WF_ROOT_FIRST; C3 1/2/3/4/6: 5331/5417/5461/5509/5406)
-    uint32_t wf_waves_per_cu = 16;
-    int wf_min_waves = 5;           // register budget of the wavefront kernel (PT_WF_MIN_WAVES: 4/5/6)
-    int wf_chunks = 0;              // sample chunks per pixel, 0 = automatic (PT_WF_CHUNKS)
-    int wf_tail_chunks = 6;         // chunks of each tail pixel (PT_WF_TAIL_CHUNKS; 1 = no tail split)
-    double wf_tail_px = 1.5;        // tail pixels per resident lane (PT_WF_TAIL_PX; round 2 re-sweep after the
-                                    // shading-pass fetch merges: C3 0.75 -> 1.5 +4.7%, the 1/2 shard +8%)
-    int64_t wf_tail_npix = -1;      // explicit number of tail pixel slots (PT_WF_TAIL_NPIX), -1 = by wf_tail_px
-    int wf_mid_chunks = -1;         // split shards: chunks of all but the last pixels (PT_WF_MID_CHUNKS;
-                                    // -1 = automatic, 0 or 1 = one split for all)
-    double wf_fine_px = 0.5;        // ... the last pixels per resident lane (PT_WF_FINE_PX)
-    double wf_whole_px = 0.5;       // split shards with >= wf_whole_min pixels per lane: whole pixels per lane
-    double wf_whole_min = 1.25;     // first (PT_WF_WHOLE_PX, PT_WF_WHOLE_MIN)
-    int wf_fine_chunks = 0;         // ... and their chunks (PT_WF_FINE_CHUNKS; 0 = the automatic count)
-    double wf_fin_px = 0.2;         // final grade: the last pixels per resident lane (PT_WF_FIN_PX) ...
-    int wf_fin_chunks = 64;         // ... in this many chunks (PT_WF_FIN_CHUNKS; <= the fine count = off)
-                                    // (measured: 1/8 and 1/4 shards +3%, full frame and 1/2 neutral)
-    uint32_t wf_iters = 2;          // (PT_WF_ITERS)
-    uint32_t wf_top = kTopNodesMax; // BVH4 nodes staged in each block's LDS (PT_WF_TOP; 0 = none)
-    bool head_wf = true;            // integrator 1 on the wavefront kernel (PT_HEAD_WF=0: the tile kernel)
-    int head_min_waves = 5;         // its register budget (PT_HEAD_MIN_WAVES: 4 = 128 VGPRs, 5 = 96)
-    uint32_t top_nodes = 0;         // nodes of this scene's BVH4 that are LDS-staged (<= wf_top)
-    uint32_t n4 = 0;                // nodes of this scene's BVH4
-    bool wf_lds_tree = true;        // (PT_WF_LDS_TREE)
-    DNode4* nodes4 = nullptr;
-    DTri* acc_tris = nullptr;
-    uint32_t* rparent = nullptr;
-    float4* hrec = nullptr;
-    float* tone_thr = nullptr;        // output step: the host libm's 255 code boundaries (+ t[0] = 0)
-    bool tone_ok = false;
-    float4* spheres = nullptr;        // sphere primitives (center, radius)
-    uint32_t num_spheres = 0;
-    uint32_t sphere_mat_base = 0;
-    float acc_root[6];
-    int32_t acc4_depth = 0;
-    uint32_t node4_mask = 0;
-    uint32_t* tri_counts = nullptr;   // PT_FLAG_COUNT: per-triangle test counts (num_tris entries, >= 1)
-    DTri* emis = nullptr;             // last-bounce light probe: records of the emissive triangles
-    uint32_t num_emis = 0;            // (0 = probe off: spheres present, too many emitters, PT_NO_LIGHT_PROBE)
-    uint64_t scene_digest = 0;        // FNV-1a of the scene arrays (a checkpoint file names its scene by it)
-    uint32_t scene_spheres = 0;       // ... and the sphere count of that scene
     pt::DenoiseScratch denoise;       // pt_denoise*'s device scratch (pt_denoise.hip), grown on demand
 };
 
@@ -2699,7 +2630,6 @@ int pt::ctx_device(const pt_ctx* c) { return c->device; }
 // Per-lane HBM words the walks may need: the BVH4 ring's overflow (at most 3 pushes per level)
 // and trace_slow's full stack on the reference BVH.
 static size_t stack_words_per_lane(const pt_ctx* c);
-static int ensure_spill(pt_ctx::Bufs& B, size_t words);
 static bool alloc_bufs(pt_ctx::Bufs& B);
 
 extern "C" {
@@ -2716,18 +2646,28 @@ static bool create_flights(pt_ctx* c)
     return true;
 }
 
+// The packed scene's arrays on the device, and the per-triangle counters.
+static int upload_scene(pt_ctx* c, const pt::PackedScene& P)
+{
+    int rc = PT_OK;
+    if ((rc = upload(&c->nodes, P.nodes)) || (rc = upload(&c->rnodes, P.rnodes)) || (rc = upload(&c->tris_leaf, P.tris_leaf)) ||
+        (rc = upload(&c->tris_orig, P.tris_orig)) || (rc = upload(&c->shade, P.shade)) ||
+        (!P.shade_m.empty() && (rc = upload(&c->shade_m, P.shade_m))) || (rc = upload(&c->mats, P.mats)) ||
+        (rc = upload(&c->lights, P.lights)) || (rc = upload(&c->jump, P.jump)) || (rc = upload(&c->tone_thr, P.tone)) ||
+        (rc = upload(&c->spheres, P.spheres)) || (rc = upload(&c->nodes4, P.nodes4)) || (rc = upload(&c->acc_tris, P.acc_tris)) ||
+        (rc = upload(&c->rparent, P.rparent)) || (rc = upload(&c->hrec, P.hrec)) ||
+        (rc = upload(&c->tri_counts, std::vector<uint32_t>(std::max<uint32_t>(P.num_tris, 1u), 0u))) ||
+        (rc = upload(&c->emis, P.emis)))
+        return rc;
+    return PT_OK;
+}
+
 pt_ctx* pt_create(const pt_scene* sc, int device, int* err)
 {
     // PT_TIMING=1: host-side phase times on stderr (ingest-speed measurements)
-    const bool timing = getenv("PT_TIMING") != nullptr;
-    auto tstart = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!timing) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "pt_create: %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - tstart).count());
-        tstart = now;
-    };
+    pt::PhaseTimer timer{getenv("PT_TIMING") != nullptr};
     auto bail = [&](int code) -> pt_ctx* { if (err) *err = code; return nullptr; };
+    // the arguments
     if (!sc || (sc->num_tris == 0 && sc->num_spheres == 0) || (sc->num_tris > 0 && (!sc->verts || !sc->tris || !sc->bvh)) ||
         (sc->num_mats > 0 && !sc->mats) ||
         (sc->num_spheres > 0 && !sc->spheres) || (sc->num_lights > 0 && !sc->lights))
@@ -2738,6 +2678,7 @@ pt_ctx* pt_create(const pt_scene* sc, int device, int* err)
                              "(got %u tris, %u nodes, %u spheres)", sc->num_tris, sc->bvh_size, sc->num_spheres));
     if (sc->bvh_depth >= PT_MAX_BVH_DEPTH)
         return bail(pt::fail(PT_E_BVH_DEPTH, "Critical Error: BVH depth is too big (%d)", sc->bvh_depth));
+    // the device
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return bail(pt::fail(PT_E_NODEV, "pt_create: no HIP device"));
     if (device < 0 || device >= ndev) return bail(pt::fail(PT_E_NODEV, "pt_create: device %d out of range (%d)", device, ndev));
@@ -2746,428 +2687,18 @@ pt_ctx* pt_create(const pt_scene* sc, int device, int* err)
     if (hipGetDeviceProperties(&prop, device) != hipSuccess) return bail(pt::fail(PT_E_HIP, "hipGetDeviceProperties failed"));
     if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
         return bail(pt::fail(PT_E_NODEV, "pt_create: device %d is %s, this build targets gfx950", device, prop.gcnArchName));
-
-    const uint32_t nt = sc->num_tris, nn = sc->bvh_size;
-    for (uint32_t i = 0; i < nt; ++i) {
-        const pt_triangle& t = sc->tris[i];
-        if ((uint32_t)t.v0 >= sc->num_verts || (uint32_t)t.v1 >= sc->num_verts || (uint32_t)t.v2 >= sc->num_verts ||
-            (uint32_t)t.mat >= sc->num_mats)
-            return bail(pt::fail(PT_E_SCENE, "pt_create: triangle %u has an out-of-range vertex or material index", i));
-    }
-    for (uint32_t j = 0; j < sc->num_lights; ++j) {
-        const uint32_t e = sc->lights[j];
-        if ((e & PT_LIGHT_SPHERE) ? (e ^ PT_LIGHT_SPHERE) >= sc->num_spheres : e >= nt)
-            return bail(pt::fail(PT_E_SCENE, "pt_create: light %u has an out-of-range primitive (0x%x)", j, e));
-    }
-    for (uint32_t k = 0; k < sc->num_spheres; ++k)
-        if (!(sc->spheres[k].rad > 0.0f) || !std::isfinite(sc->spheres[k].rad))
-            return bail(pt::fail(PT_E_SCENE, "pt_create: sphere %u has radius %g", k, (double)sc->spheres[k].rad));
-    // validate the BVH: every reference must be in range, every triangle reachable once
-    lap("device query");
-    std::vector<uint32_t> leaf_rank(nt, 0xffffffffu);
-    std::vector<uint32_t> leaf_order;
-    leaf_order.reserve(nt);
-    if (nt > 0) {
-        std::vector<uint32_t> st;
-        st.push_back(0);
-        size_t visits = 0;
-        while (!st.empty()) {   // left-first DFS = the order trace() meets leaves
-            const uint32_t e = st.back();
-            st.pop_back();
-            if (++visits > 4ull * nt + 8) return bail(pt::fail(PT_E_SCENE, "pt_create: BVH is not a tree"));
-            if (e & PT_BVH_LEAF_FLAG) {
-                const uint32_t k = e ^ PT_BVH_LEAF_FLAG;
-                if (k >= nt || leaf_rank[k] != 0xffffffffu) return bail(pt::fail(PT_E_SCENE, "pt_create: bad BVH leaf %u", k));
-                leaf_rank[k] = (uint32_t)leaf_order.size();
-                leaf_order.push_back(k);
-            } else {
-                if (e >= nn) return bail(pt::fail(PT_E_SCENE, "pt_create: BVH child %u out of range", e));
-                st.push_back(sc->bvh[e].right);
-                st.push_back(sc->bvh[e].left);
-            }
-        }
-        if (leaf_order.size() != nt) return bail(pt::fail(PT_E_SCENE, "pt_create: BVH reaches %zu of %u triangles", leaf_order.size(), nt));
-    }
-
+    // the scene as the kernels read it
+    const pt::RenderKnobs knobs = pt::read_render_knobs(kQueues, kTopNodesMax);
+    pt::PackedScene P;
+    if (int rc = pt::pack_scene(*sc, knobs, &timer, &P)) return bail(rc);
     pt_ctx* c = new (std::nothrow) pt_ctx();
     if (!c) return bail(pt::fail(PT_E_OOM, "pt_create: out of host memory"));
+    static_cast<pt::SceneInfo&>(*c) = P;
     c->device = device;
     c->num_cus = prop.multiProcessorCount;
-    c->num_tris = nt;
-    {   // what the scene is, for pt_accum_save / pt_accum_load: every array the caller passed
-        uint64_t h = pt::kFnvBasis;
-        h = pt::fnv1a(sc->verts, (size_t)sc->num_verts * sizeof(pt_vec3), h);
-        h = pt::fnv1a(sc->tris, (size_t)nt * sizeof(pt_triangle), h);
-        h = pt::fnv1a(sc->mats, (size_t)sc->num_mats * sizeof(pt_material), h);
-        h = pt::fnv1a(sc->lights, (size_t)sc->num_lights * sizeof(uint32_t), h);
-        h = pt::fnv1a(&sc->total_light_area, sizeof(float), h);
-        h = pt::fnv1a(sc->bvh, (size_t)nn * sizeof(pt_bvh_node), h);
-        h = pt::fnv1a(sc->spheres, (size_t)sc->num_spheres * sizeof(pt_sphere), h);
-        c->scene_digest = h;
-        c->scene_spheres = sc->num_spheres;
-    }
-    c->depth = sc->bvh_depth;
-
-    std::vector<uint32_t> ref_parent(nt, 0u);
-    for (uint32_t i = 0; i < nn; ++i) {
-        if (sc->bvh[i].left & PT_BVH_LEAF_FLAG) ref_parent[sc->bvh[i].left ^ PT_BVH_LEAF_FLAG] = i;
-        if (sc->bvh[i].right & PT_BVH_LEAF_FLAG) ref_parent[sc->bvh[i].right ^ PT_BVH_LEAF_FLAG] = i;
-    }
-    auto tri_rec = [&](uint32_t k) {
-        const pt_triangle& t = sc->tris[k];
-        const pt_vec3 a = sc->verts[t.v0], b = sc->verts[t.v1], cc = sc->verts[t.v2];
-        DTri r;
-        const float e1x = b.x - a.x, e1y = b.y - a.y, e1z = b.z - a.z;   // modelLoader.h:58
-        const float e2x = cc.x - a.x, e2y = cc.y - a.y, e2z = cc.z - a.z; // modelLoader.h:59
-        r.a = make_float4(a.x, a.y, a.z, e1x);
-        r.b = make_float4(e1y, e1z, e2x, e2y);
-        const uint32_t words[3] = {k, leaf_rank[k], ref_parent[k]};
-        float f[3];
-        memcpy(f, words, sizeof(f));
-        r.c = make_float4(e2z, f[0], f[1], f[2]);
-        return r;
-    };
-    std::vector<DTri> tl(nt), to(nt);
-    for (uint32_t i = 0; i < nt; ++i) { to[i] = tri_rec(i); tl[i] = tri_rec(leaf_order[i]); }
-    std::vector<RNode> rn(nn);
-    std::vector<DNode> dn(nn);
-    auto box_of = [&](uint32_t ref, float* b) {   // box of a child; leaves carry no box
-        if (ref & PT_BVH_LEAF_FLAG) { for (int q = 0; q < 6; ++q) b[q] = 0.0f; return; }
-        const pt_bvh_node& x = sc->bvh[ref];
-        b[0] = x.lo.x; b[1] = x.lo.y; b[2] = x.lo.z; b[3] = x.hi.x; b[4] = x.hi.y; b[5] = x.hi.z;
-    };
-    auto remap = [&](uint32_t ref) {
-        return (ref & PT_BVH_LEAF_FLAG) ? (PT_BVH_LEAF_FLAG | leaf_rank[ref ^ PT_BVH_LEAF_FLAG]) : ref;
-    };
-    float lo_all[3] = {1e30f, 1e30f, 1e30f}, hi_all[3] = {-1e30f, -1e30f, -1e30f};
-    for (uint32_t i = 0; i < nn; ++i) {
-        const pt_bvh_node& x = sc->bvh[i];
-        memcpy(rn[i].lo, &x.lo, 12);
-        memcpy(rn[i].hi, &x.hi, 12);
-        rn[i].left = x.left;
-        rn[i].right = x.right;
-        float b0[6], b1[6];
-        box_of(x.left, b0);
-        box_of(x.right, b1);
-        dn[i].a = make_float4(b0[0], b0[1], b0[2], b0[3]);
-        dn[i].b = make_float4(b0[4], b0[5], b1[0], b1[1]);
-        dn[i].c = make_float4(b1[2], b1[3], b1[4], b1[5]);
-        dn[i].d = make_uint4(remap(x.left), remap(x.right), 0u, 0u);
-    }
-    if (nt > 0) {
-        const pt_bvh_node& r = sc->bvh[0];
-        c->root[0] = r.lo.x; c->root[1] = r.lo.y; c->root[2] = r.lo.z;
-        c->root[3] = r.hi.x; c->root[4] = r.hi.y; c->root[5] = r.hi.z;
-        for (int q = 0; q < 3; ++q) { lo_all[q] = c->root[q]; hi_all[q] = c->root[3 + q]; }
-    }
-    for (uint32_t k = 0; k < sc->num_spheres; ++k) {   // the scene extent covers the spheres too
-        const pt_sphere& sp = sc->spheres[k];
-        const float cc[3] = {sp.pos.x, sp.pos.y, sp.pos.z};
-        for (int q = 0; q < 3; ++q) {
-            lo_all[q] = std::fmin(lo_all[q], cc[q] - sp.rad);
-            hi_all[q] = std::fmax(hi_all[q], cc[q] + sp.rad);
-        }
-    }
-    {
-        float ext = 0.0f;
-        for (int q = 0; q < 3; ++q) {
-            const float e = std::fabs(hi_all[q]) > std::fabs(lo_all[q]) ? std::fabs(hi_all[q]) : std::fabs(lo_all[q]);
-            ext = ext > e ? ext : e;
-        }
-        c->scene_extent = (ext > 0.0f && std::isfinite(ext)) ? ext : 1.0f;
-    }
-    {
-        // Markstein-quotient precondition on the scene (pt_device.h div_mk): every vertex
-        // coordinate is 0 or has magnitude in [2^-50, 2^20].  Boxes are min/max of vertices.
-        bool ok = true;
-        for (uint32_t v = 0; v < sc->num_verts && ok; ++v) {
-            const float q[3] = {sc->verts[v].x, sc->verts[v].y, sc->verts[v].z};
-            for (int k = 0; k < 3; ++k) {
-                const float m = std::fabs(q[k]);
-                if (!(m == 0.0f || (m >= 0x1p-50f && m <= 0x1p20f))) ok = false;
-            }
-        }
-        c->scene_fast = ok;
-        uint32_t bits = 1;
-        while ((1u << bits) < nn) ++bits;
-        c->node_mask = (bits >= 31) ? 0x7fffffffu : ((1u << bits) - 1u);
-        if (const char* e = getenv("PT_WF_THRESHOLD")) c->wf_threshold = (uint32_t)atoi(e);
-        if (const char* e = getenv("PT_WF_ROOT_FIRST")) c->wf_root_first = (uint32_t)atoi(e);
-        if (const char* e = getenv("PT_WF_QUEUES")) c->wf_queues = (atoi(e) > 1) ? kQueues : 1u;
-        if (const char* e = getenv("PT_JUMP_BYTES")) c->use_jump_bytes = atoi(e) != 0;
-        if (const char* e = getenv("PT_TILE_FAST4")) c->tile_fast4 = atoi(e) != 0;
-        if (const char* e = getenv("PT_HEAD_WF")) c->head_wf = atoi(e) != 0;
-        if (const char* e = getenv("PT_HEAD_MIN_WAVES")) c->head_min_waves = (atoi(e) == 5) ? 5 : 4;
-        if (const char* e = getenv("PT_WF_MIN_WAVES")) {
-            const int v = atoi(e);
-            c->wf_min_waves = (v == 4 || v == 6) ? v : 5;
-        }
-        c->wf_waves_per_cu = 4u * (uint32_t)c->wf_min_waves;
-        if (const char* e = getenv("PT_WF_WAVES_PER_CU")) c->wf_waves_per_cu = (uint32_t)atoi(e);
-        if (const char* e = getenv("PT_WF_CHUNKS")) c->wf_chunks = atoi(e);
-        if (const char* e = getenv("PT_WF_TAIL_CHUNKS")) c->wf_tail_chunks = atoi(e);
-        if (const char* e = getenv("PT_WF_TAIL_PX")) c->wf_tail_px = std::max(0.0, atof(e));
-        if (const char* e = getenv("PT_WF_TAIL_NPIX")) c->wf_tail_npix = atoll(e);
-        if (const char* e = getenv("PT_WF_MID_CHUNKS")) c->wf_mid_chunks = atoi(e);
-        if (const char* e = getenv("PT_WF_FINE_PX")) c->wf_fine_px = std::max(0.0, atof(e));
-        if (const char* e = getenv("PT_WF_FINE_CHUNKS")) c->wf_fine_chunks = atoi(e);
-        if (const char* e = getenv("PT_WF_WHOLE_PX")) c->wf_whole_px = std::max(0.0, atof(e));
-        if (const char* e = getenv("PT_WF_WHOLE_MIN")) c->wf_whole_min = std::max(0.0, atof(e));
-        if (const char* e = getenv("PT_WF_FIN_PX")) c->wf_fin_px = std::max(0.0, atof(e));
-        if (const char* e = getenv("PT_WF_FIN_CHUNKS")) c->wf_fin_chunks = atoi(e);
-        if (const char* e = getenv("PT_WF_ITERS")) c->wf_iters = (uint32_t)std::max(1, atoi(e));
-        if (const char* e = getenv("PT_WF_TOP")) c->wf_top = std::min<uint32_t>((uint32_t)std::max(0, atoi(e)), kTopNodesMax);
-    }
-    // render-path BVH4 (accel_build.cpp): binned SAH binary BVH collapsed to 4 wide
-    std::vector<DNode4> an;
-    std::vector<DTri> at;
-    if (nt == 0) {   // spheres only: no triangle structures (kernels skip the walk)
-        for (int q = 0; q < 3; ++q) { c->acc_root[q] = INFINITY; c->acc_root[3 + q] = -INFINITY; }
-        c->acc4_depth = 0;
-        c->node4_mask = 1u;
-    } else {
-        pt::AccelBvh acc;
-        constexpr int kW = 4;
-        pt::Accel4 acc4;
-        lap("reference-BVH records");
-        int rc4 = pt::build_accel(*sc, &acc);
-        lap("SAH BVH build");
-        if (timing && rc4 == PT_OK) fprintf(stderr, "pt_create: render BVH SAH cost %.6g\n", pt::accel_sah_cost(acc));
-        if (rc4 == PT_OK) rc4 = pt::collapse_accel4(acc, &acc4);
-        lap("BVH4 collapse");
-        // the structural check (every node and slot reached once, <= 8 leaf triangles per node, nested
-        // boxes) is O(nodes): the walk's exactness argument and its 8-bit leaf masks rely on it
-        if (rc4 == PT_OK) rc4 = pt::validate_accel4(acc, acc4);
-        lap("BVH4 validate");
-        if (rc4 != PT_OK) { delete c; return bail(rc4); }
-        // Node order: the kTopNodesMax nodes most likely to be visited first (best-first by box
-        // surface area from the root: a connected top subtree, staged in LDS by the wavefront
-        // kernel), then the others in their DFS order.
-        const uint32_t n4 = (uint32_t)acc4.nodes.size();
-        std::vector<uint32_t> new_of(n4, ~0u), old_of;
-        old_of.reserve(n4);
-        {
-            std::vector<std::pair<float, uint32_t>> heap{{INFINITY, 0u}};
-            while (!heap.empty() && old_of.size() < kTopNodesMax) {
-                std::pop_heap(heap.begin(), heap.end());
-                const uint32_t o = heap.back().second;
-                heap.pop_back();
-                new_of[o] = (uint32_t)old_of.size();
-                old_of.push_back(o);
-                const auto& x = acc4.nodes[o];
-                for (int k = 0; k < kW; ++k) {
-                    if (x.child[k] == pt::kAccel4Empty || (x.child[k] & PT_BVH_LEAF_FLAG)) continue;
-                    const float b[6] = {x.lo[0][k], x.lo[1][k], x.lo[2][k], x.hi[0][k], x.hi[1][k], x.hi[2][k]};
-                    const float ex = b[3] - b[0], ey = b[4] - b[1], ez = b[5] - b[2];
-                    heap.push_back({ex * ey + ey * ez + ez * ex, x.child[k]});
-                    std::push_heap(heap.begin(), heap.end());
-                }
-            }
-            for (uint32_t o = 0; o < n4; ++o)
-                if (new_of[o] == ~0u) { new_of[o] = (uint32_t)old_of.size(); old_of.push_back(o); }
-        }
-        c->top_nodes = std::min(std::max(c->wf_top, 1u), n4);   // (>= 1: the wavefront walk reads the LDS top unconditionally)
-        c->n4 = n4;
-        if (const char* e = getenv("PT_WF_LDS_TREE")) c->wf_lds_tree = atoi(e) != 0;
-        // A tree the LDS top holds whole (small scenes: C2's Cornell box) is walked with no node fetch
-        // from memory, so a walk step is cheap: waves stay in the walk phase until 62 lanes wait to
-        // shade, and a new ray's first two visits (not four) run in the shading pass (C2: 6879 -> 7081
-        // Msamples/s, same box, profiles/r03_c2_knobs; the stand-in's defaults are unchanged).
-        if (n4 <= c->top_nodes) {
-            if (!getenv("PT_WF_THRESHOLD")) c->wf_threshold = 62;
-            if (!getenv("PT_WF_ROOT_FIRST")) c->wf_root_first = 2;
-        }
-        an.resize(n4);
-        // Triangle slots: the triangles of each node's leaf children (in node order) get consecutive
-        // slots, and each node lists its leaf children first -- the walk queues a node's entered
-        // leaves as one entry (first slot, 8-bit mask of slots).  A leaf child's word is
-        // kLeaf | the node's first leaf slot << kLeafBits | its slot bits relative to it.
-        // slot_leaf[s] = the binary BVH's leaf slot (one triangle) of render slot s.
-        std::vector<uint32_t> slot_leaf;
-        slot_leaf.reserve(nt);
-        for (size_t i = 0; i < n4; ++i) {
-            auto x0 = acc4.nodes[old_of[i]], x = x0;
-            auto is_leaf = [](uint32_t r) { return r != pt::kAccel4Empty && (r & PT_BVH_LEAF_FLAG); };
-            int order[kW], m = 0;
-            for (int k = 0; k < kW; ++k) if (is_leaf(x0.child[k])) order[m++] = k;
-            for (int k = 0; k < kW; ++k) if (!is_leaf(x0.child[k])) order[m++] = k;
-            const uint32_t base = (uint32_t)slot_leaf.size();
-            for (int k = 0; k < kW; ++k) {
-                const int q = order[k];
-                for (int ax = 0; ax < 3; ++ax) { x.lo[ax][k] = x0.lo[ax][q]; x.hi[ax][k] = x0.hi[ax][q]; }
-                x.child[k] = x0.child[q];
-                if (is_leaf(x.child[k])) {
-                    const uint32_t first = (uint32_t)slot_leaf.size() - base, cnt = pt::accel_leaf_count(x.child[k]);
-                    for (uint32_t j = 0; j < cnt; ++j) slot_leaf.push_back(pt::accel_leaf_slot(x.child[k]) + j);
-                    static_assert(pt::kAccel4LeafTris <= kLeafBits, "leaf slot mask width");
-                    if (first + cnt > kLeafBits || base >= (1u << (31 - kLeafBits))) {
-                        delete c;
-                        return bail(pt::fail(PT_E_SCENE, "pt_create: %u triangles exceed the render path's leaf slot range", nt));
-                    }
-                    x.child[k] = PT_BVH_LEAF_FLAG | (base << kLeafBits) | (((1u << cnt) - 1u) << first);
-                }
-            }
-            for (int k = 0; k < kW; ++k)
-                if (x.child[k] != pt::kAccel4Empty && !(x.child[k] & PT_BVH_LEAF_FLAG)) x.child[k] = new_of[x.child[k]];
-            an[i].lox = make_float4(x.lo[0][0], x.lo[0][1], x.lo[0][2], x.lo[0][3]);
-            an[i].loy = make_float4(x.lo[1][0], x.lo[1][1], x.lo[1][2], x.lo[1][3]);
-            an[i].loz = make_float4(x.lo[2][0], x.lo[2][1], x.lo[2][2], x.lo[2][3]);
-            an[i].hix = make_float4(x.hi[0][0], x.hi[0][1], x.hi[0][2], x.hi[0][3]);
-            an[i].hiy = make_float4(x.hi[1][0], x.hi[1][1], x.hi[1][2], x.hi[1][3]);
-            an[i].hiz = make_float4(x.hi[2][0], x.hi[2][1], x.hi[2][2], x.hi[2][3]);
-            an[i].child = make_uint4(x.child[0], x.child[1], x.child[2], x.child[3]);
-            an[i].pad = make_uint4(0u, 0u, 0u, 0u);
-        }
-        if (slot_leaf.size() != nt) { delete c; return bail(pt::fail(PT_E_SCENE, "pt_create: BVH4 reaches %zu of %u triangles", slot_leaf.size(), nt)); }
-        at.resize(nt);
-        for (uint32_t i = 0; i < nt; ++i) {   // permuted for tri_hit_pk: {v0.xy, e1.xy}, {e2.xy, v0.z, e1.z}
-            const DTri r = tri_rec(acc.leaf_order[slot_leaf[i]]);
-            at[i].a = make_float4(r.a.x, r.a.y, r.a.w, r.b.x);
-            at[i].b = make_float4(r.b.z, r.b.w, r.a.z, r.b.y);
-            at[i].c = r.c;
-        }
-        memcpy(c->acc_root, acc.root_box, sizeof(c->acc_root));
-        c->acc4_depth = acc4.depth;
-        uint32_t bits = 1;
-        while ((1u << bits) < (uint32_t)an.size()) ++bits;
-        c->node4_mask = (1u << bits) - 1u;
-    }
-    std::vector<uint32_t> rpar(nn, 0u);
-    for (uint32_t i = 0; i < nn; ++i) {
-        if (!(sc->bvh[i].left & PT_BVH_LEAF_FLAG)) rpar[sc->bvh[i].left] = i;
-        if (!(sc->bvh[i].right & PT_BVH_LEAF_FLAG)) rpar[sc->bvh[i].right] = i;
-    }
-    // per render-path slot: the reference parent's node of its triangle (into Args::hrec below)
-    std::vector<RNode> wb(std::max<size_t>(at.size(), 1));
-    for (size_t sl = 0; sl < at.size(); ++sl) {
-        uint32_t parent;
-        memcpy(&parent, &at[sl].c.w, 4);
-        wb[sl] = rn[parent];
-        wb[sl].left = parent;
-        wb[sl].right = 0u;
-    }
-    // per render-path slot: the winner check's box, parent and triangle id, and the shading normal and
-    // material (Args::hrec)
-    std::vector<float4> hr((size_t)3 * std::max<size_t>(at.size(), 1));
-    for (size_t sl = 0; sl < at.size(); ++sl) {
-        uint32_t tid;
-        memcpy(&tid, &at[sl].c.y, 4);
-        const RNode& b = wb[sl];
-        float fpar, ftid, fmat;
-        memcpy(&fpar, &b.left, 4);
-        memcpy(&ftid, &tid, 4);
-        memcpy(&fmat, &sc->tris[tid].mat, 4);
-        hr[3 * sl] = make_float4(b.lo[0], b.lo[1], b.lo[2], b.hi[0]);
-        hr[3 * sl + 1] = make_float4(b.hi[1], b.hi[2], fpar, ftid);
-        hr[3 * sl + 2] = make_float4(sc->tris[tid].norm.x, sc->tris[tid].norm.y, sc->tris[tid].norm.z, fmat);
-    }
-    // last-bounce light probe (shade_lane begin_trace): every triangle whose material has
-    // emission.r != 0 (the integrator's emission test, kernel.cu:453 -- not the caller's light list)
-    std::vector<DTri> em;
-    for (uint32_t i = 0; i < nt; ++i)
-        if (sc->mats[sc->tris[i].mat].emission[0] != 0) {
-            const DTri r = tri_rec(i);   // permuted for tri_hit_pk, as the render path's records
-            DTri q;
-            q.a = make_float4(r.a.x, r.a.y, r.a.w, r.b.x);
-            q.b = make_float4(r.b.z, r.b.w, r.a.z, r.b.y);
-            q.c = r.c;
-            em.push_back(q);
-        }
-    if (em.size() > kMaxProbeEmitters || sc->num_spheres > 0 || getenv("PT_NO_LIGHT_PROBE")) em.clear();
-    c->num_emis = (uint32_t)em.size();
-    std::vector<DShade> sh(nt);
-    for (uint32_t i = 0; i < nt; ++i) {
-        sh[i].nx = sc->tris[i].norm.x; sh[i].ny = sc->tris[i].norm.y; sh[i].nz = sc->tris[i].norm.z;
-        sh[i].mat = sc->tris[i].mat;
-    }
-    // the merged per-triangle shading record (Args::shade_m) when every material colour is a float
-    std::vector<float4> shm;
-    {
-        bool exact = nt > 0 && !getenv("PT_NO_SHADE_M");
-        for (uint32_t i = 0; i < sc->num_mats && exact; ++i)
-            for (int q = 0; q < 3; ++q)
-                exact = exact && (double)(float)sc->mats[i].albedo[q] == sc->mats[i].albedo[q] &&
-                        (double)(float)sc->mats[i].emission[q] == sc->mats[i].emission[q];
-        if (exact) {
-            shm.resize((size_t)3 * nt);
-            for (uint32_t i = 0; i < nt; ++i) {
-                const pt_material& m = sc->mats[sc->tris[i].mat];
-                shm[3 * (size_t)i] = make_float4(sc->tris[i].norm.x, sc->tris[i].norm.y, sc->tris[i].norm.z, (float)m.emission[0]);
-                shm[3 * (size_t)i + 1] = make_float4((float)m.albedo[0], (float)m.albedo[1], (float)m.albedo[2], (float)m.emission[1]);
-                float mbits;
-                memcpy(&mbits, &sc->tris[i].mat, 4);
-                shm[3 * (size_t)i + 2] = make_float4((float)m.emission[2], mbits, 0.0f, 0.0f);
-            }
-        }
-    }
-    // scene materials, then one per sphere (sphere.h diffuse / emm)
-    std::vector<DMat> mt(sc->num_mats + sc->num_spheres);
-    for (uint32_t i = 0; i < sc->num_mats; ++i) {
-        for (int q = 0; q < 3; ++q) { mt[i].albedo[q] = sc->mats[i].albedo[q]; mt[i].emission[q] = sc->mats[i].emission[q]; }
-    }
-    for (uint32_t k = 0; k < sc->num_spheres; ++k) {
-        DMat& m = mt[sc->num_mats + k];
-        for (int q = 0; q < 3; ++q) { m.albedo[q] = sc->spheres[k].diffuse[q]; m.emission[q] = sc->spheres[k].emission[q]; }
-    }
-    std::vector<float4> sp(sc->num_spheres);
-    for (uint32_t k = 0; k < sc->num_spheres; ++k)
-        sp[k] = make_float4(sc->spheres[k].pos.x, sc->spheres[k].pos.y, sc->spheres[k].pos.z, sc->spheres[k].rad);
-    c->num_spheres = sc->num_spheres;
-    c->sphere_mat_base = sc->num_mats;
-    std::vector<DLight> lt(sc->num_lights + 1);
-    auto light_rec = [&](uint32_t tri) {
-        const pt_triangle& t = sc->tris[tri];
-        const pt_vec3 a = sc->verts[t.v0], b = sc->verts[t.v1], cc = sc->verts[t.v2];
-        DLight L;
-        const float a1x = b.x - a.x, a1y = b.y - a.y, a1z = b.z - a.z;
-        const float a2x = cc.x - a.x, a2y = cc.y - a.y, a2z = cc.z - a.z;
-        // length(cross(a1, a2)) / 2, kernel.cu:477-478
-        const float cx = a1y * a2z - a1z * a2y, cy = a1z * a2x - a1x * a2z, cz = a1x * a2y - a1y * a2x;
-        L.area = sqrtf(cx * cx + cy * cy + cz * cz) / 2;
-        L.tri = (int32_t)tri;
-        L.v0[0] = a.x; L.v0[1] = a.y; L.v0[2] = a.z;
-        L.a1[0] = a1x; L.a1[1] = a1y; L.a1[2] = a1z;
-        L.a2[0] = a2x; L.a2[1] = a2y; L.a2[2] = a2z;
-        L.pad = 0.0f;
-        return L;
-    };
-    // sphere light (d8 policy): area 4*3.14159*r^2, center in v0, radius in a1[0], pad = 1
-    auto sphere_light = [&](uint32_t k) {
-        DLight L;
-        memset(&L, 0, sizeof(L));
-        const pt_sphere& q = sc->spheres[k];
-        L.area = pt::sphere_area(q.rad);
-        L.tri = (int32_t)(nt + k);
-        L.v0[0] = q.pos.x; L.v0[1] = q.pos.y; L.v0[2] = q.pos.z;
-        L.a1[0] = q.rad;
-        L.pad = 1.0f;
-        return L;
-    };
-    for (uint32_t j = 0; j < sc->num_lights; ++j) {
-        const uint32_t e = sc->lights[j];
-        lt[j] = (e & PT_LIGHT_SPHERE) ? sphere_light(e ^ PT_LIGHT_SPHERE) : light_rec(e);
-    }
-    lt[sc->num_lights] = (nt > 0) ? light_rec(0) : sphere_light(0);   // "nothing picked": primitive 0
-    c->num_lights = sc->num_lights;
-    c->total_light_area = sc->total_light_area;
-    std::vector<uint32_t> jump_img, jump;
-    build_jump_tables(jump_img);
-    build_jump_bytes(jump_img, jump);
-    std::vector<float> tone(256);
-    c->tone_ok = pt::tonemap_thresholds(tone.data());
-
-    // the BVH4 walk addresses nodes and triangle records by 32-bit byte offsets (pt_device.h
-    // walk4_step): larger structures take the exact reference-BVH walk for every ray
-    if ((uint64_t)an.size() * sizeof(an[0]) >= (1ull << 32) || (uint64_t)at.size() * sizeof(at[0]) >= (1ull << 32))
-        c->scene_fast = false;
-    int rc = PT_OK;
-    lap("records + jump/tone tables");
-    if ((rc = upload(&c->nodes, dn)) || (rc = upload(&c->rnodes, rn)) || (rc = upload(&c->tris_leaf, tl)) ||
-        (rc = upload(&c->tris_orig, to)) || (rc = upload(&c->shade, sh)) || (!shm.empty() && (rc = upload(&c->shade_m, shm))) || (rc = upload(&c->mats, mt)) ||
-        (rc = upload(&c->lights, lt)) || (rc = upload(&c->jump, jump)) || (rc = upload(&c->tone_thr, tone)) || (rc = upload(&c->spheres, sp)) ||
-        (rc = upload(&c->nodes4, an)) || (rc = upload(&c->acc_tris, at)) || (rc = upload(&c->rparent, rpar)) || (rc = upload(&c->hrec, hr)) ||
-        (rc = upload(&c->tri_counts, std::vector<uint32_t>(std::max<uint32_t>(nt, 1u), 0u))) ||
-        (rc = upload(&c->emis, em))) {
+    c->knobs = P.knobs;   // (with this scene's defaults of the knobs that were not set)
+    // its arrays and the first render's buffers on the device
+    if (int rc = upload_scene(c, P)) {
         pt_destroy(c);
         return bail(rc);
     }
@@ -3176,7 +2707,7 @@ pt_ctx* pt_create(const pt_scene* sc, int device, int* err)
         return bail(pt::fail(PT_E_HIP, "pt_create: device allocation failed"));
     }
     if (err) *err = PT_OK;
-    lap("uploads");
+    timer.lap("uploads");
     return c;
 }
 
@@ -3233,49 +2764,41 @@ static void write_lane_timing(const char* path, const std::vector<unsigned long 
     }
 }
 
-// What a render's parameters and camera must satisfy whatever the context (pt_render_device_async and
-// pt_accum_create share it).
-static int validate_render(const pt_params* p, const pt_camera* cam)
+// The scene half of Args: what every entry point's kernels read of the context's scene.  (Each entry sets its
+// own stack_words, node_mask and spill.)
+static void fill_scene_args(Args& a, const pt_ctx* c)
 {
-    if (p->width <= 0 || p->height <= 0 || p->width > 65535 || p->height > 65535)
-        return pt::fail(PT_E_INVALID, "pt_render: image size %dx%d out of range (1..65535)", p->width, p->height);
-    if (p->spp < 0) return pt::fail(PT_E_INVALID, "pt_render: spp < 0");
-    if (p->integrator != PT_INTEGRATOR_UNIDIR && p->integrator != PT_INTEGRATOR_HEAD)
-        return pt::fail(PT_E_INVALID, "pt_render: unknown integrator %d", p->integrator);
-    if (p->integrator == PT_INTEGRATOR_UNIDIR && (p->bounces < 1 || p->bounces > 64))
-        return pt::fail(PT_E_INVALID, "pt_render: bounces %d out of range (1..64)", p->bounces);
-    if (p->shard_count < 1 || p->shard_index < 0 || p->shard_index >= p->shard_count)
-        return pt::fail(PT_E_INVALID, "pt_render: shard %d of %d", p->shard_index, p->shard_count);
-    if (cam->pxl_width <= 0 || cam->pxl_height <= 0) return pt::fail(PT_E_INVALID, "pt_render: camera pixel size must be > 0");
-    if (p->pixel_order != PT_ORDER_SCANLINE && p->pixel_order != PT_ORDER_MORTON)
-        return pt::fail(PT_E_INVALID, "pt_render: unknown pixel order %d", p->pixel_order);
-    if (p->pixel_order == PT_ORDER_MORTON && !pt::morton_size_ok(p->width, p->height))
-        return pt::fail(PT_E_INVALID, "pt_render: Morton pixel order needs a square power-of-two image, not %dx%d "
-                        "(the reference's imgBuff indexing, kernel.cu:543,771)", p->width, p->height);
-    for (const int32_t v : {p->tile_w, p->tile_h})
-        if (v != 0 && (v < 8 || v > 256 || v % 8 != 0))
-            return pt::fail(PT_E_INVALID, "pt_render: tile size %dx%d (0 = 8, else multiples of 8 up to 256)", p->tile_w, p->tile_h);
-    {   // the padded tile grid (tiles x tile_w x tile_h slots) must fit the kernels' 32-bit unit indices
-        const uint64_t tw64 = p->tile_w ? (uint64_t)p->tile_w : 8u, th64 = p->tile_h ? (uint64_t)p->tile_h : 8u;
-        const uint64_t slots = (((uint64_t)p->width + tw64 - 1) / tw64) * (((uint64_t)p->height + th64 - 1) / th64) * tw64 * th64;
-        if (slots > 0xffffffffull)
-            return pt::fail(PT_E_INVALID, "pt_render: %dx%d in %llux%llu tiles pads to %llu pixel slots (limit 2^32-1)",
-                            p->width, p->height, (unsigned long long)tw64, (unsigned long long)th64, (unsigned long long)slots);
-    }
-    return PT_OK;
+    a.nodes = c->nodes; a.rnodes = c->rnodes; a.tris_leaf = c->tris_leaf; a.tris_orig = c->tris_orig;
+    a.shade = c->shade; a.mats = c->mats; a.lights = c->lights; a.jump = c->jump; a.shade_m = c->shade_m;
+    a.num_lights = c->num_lights; a.total_light_area = c->total_light_area;
+    a.spheres = c->spheres; a.num_spheres = c->num_spheres; a.num_tris = c->num_tris;
+    a.sphere_mat_base = c->sphere_mat_base;
+    a.emis = c->emis; a.num_emis = c->num_emis;
+    memcpy(a.root, c->root, sizeof(a.root));
+    memcpy(a.acc_root, c->acc_root, sizeof(a.acc_root));
+    a.cull_rel = kCullRel;
+    a.cull_abs = c->scene_extent * 1e-4f;
+    a.scene_fast = c->scene_fast ? 1u : 0u;
+    a.nodes4 = c->nodes4;
+    a.acc_tris = c->acc_tris;
+    a.rparent = c->rparent;
+    a.hrec = c->hrec;
 }
 
-// Whether a render of (p, cam) on this context takes the wavefront kernels (else render_tiles).
-static bool takes_wavefront(const pt_ctx* c, const pt_params* p, const pt_camera* cam)
+// The camera, the image and this shard's tile grid (validated parameters).
+static void fill_view_args(Args& a, const pt_params& p, const pt_camera& cam)
 {
-    // the render-path BVH's box margin assumes ray origins within ~2^6 of the scene extent
-    const float cam_ext = std::fmax(std::fabs(cam->pos.x), std::fmax(std::fabs(cam->pos.y), std::fabs(cam->pos.z)));
-    const bool near_cam = cam_ext <= 64.0f * c->scene_extent;
-    // integrator 1 takes the wavefront kernel too (PT_HEAD_WF=0: the tile kernel, for comparisons)
-    const bool head = p->integrator == PT_INTEGRATOR_HEAD;
-    return (p->integrator == PT_INTEGRATOR_UNIDIR || (head && c->head_wf)) && !(p->flags & PT_FLAG_REFERENCE_TRAVERSAL) &&
-           !(p->flags & PT_FLAG_REFERENCE_BVH) && near_cam &&
-           p->width < 65536 && p->height < 65536;   // (16-bit pixel coordinates per unit)
+    a.cam.pos[0] = cam.pos.x; a.cam.pos[1] = cam.pos.y; a.cam.pos[2] = cam.pos.z;
+    a.cam.dist = cam.dist_from_film; a.cam.focal = cam.focal_length; a.cam.radius = cam.radius;
+    a.cam.w = cam.pxl_width; a.cam.h = cam.pxl_height;
+    const pt::TileGrid g = pt::tile_grid(p);
+    a.w = g.w; a.h = g.h;
+    a.shard_index = g.shard_index; a.shard_count = g.shard_count;
+    a.tiles_x = g.tiles_x; a.ntiles_shard = g.ntiles_shard;
+    a.tile_w = g.tile_w; a.tile_h = g.tile_h;
+    a.tile_bx = g.tile_bx; a.tile_blocks = g.tile_blocks;
+    a.morton_out = (p.pixel_order == PT_ORDER_MORTON) ? 1u : 0u;
+    a.npix = g.npix;
 }
 
 // One render enqueued on `stream` in the context's next flight slot: the body of pt_render_device_async.
@@ -3288,7 +2811,7 @@ static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, f
     if (!c || !p || !cam || (!d_out && !acc)) return pt::fail(PT_E_INVALID, "pt_render: null argument");
     if (c->fl_n >= pt_ctx::kFlights)
         return pt::fail(PT_E_INVALID, "pt_render_device_async: %d renders in flight (pt_render_wait first)", c->fl_n);
-    if (int rc = validate_render(p, cam)) return rc;
+    if (int rc = pt::validate_render(p, cam)) return rc;
     // the per-triangle counts live in one context-wide buffer (pt_tri_counts reads it back): only one render
     // in flight may fill them
     if ((p->flags & PT_FLAG_COUNT) && (p->flags & PT_FLAG_TRI_COUNTS) && c->fl_n > 0)
@@ -3302,32 +2825,14 @@ static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, f
     pt_ctx::Flight& F = c->fl[slot];
     pt_ctx::Bufs& B = c->rb[slot];
     if (!alloc_bufs(B)) return pt::fail(PT_E_HIP, "pt_render: device allocation failed");
+    const pt::RenderKnobs& K = c->knobs;
 
     Args a;
     memset(&a, 0, sizeof(a));
-    a.nodes = c->nodes; a.rnodes = c->rnodes; a.tris_leaf = c->tris_leaf; a.tris_orig = c->tris_orig;
-    a.shade = c->shade; a.mats = c->mats; a.lights = c->lights; a.jump = c->jump; a.shade_m = c->shade_m;
+    fill_scene_args(a, c);
+    fill_view_args(a, *p, *cam);
     a.out = d_out; a.counters = B.counters; a.tile_counter = B.tile_counter;
-    a.num_lights = c->num_lights; a.total_light_area = c->total_light_area;
-    a.spheres = c->spheres; a.num_spheres = c->num_spheres; a.num_tris = c->num_tris;
-    a.sphere_mat_base = c->sphere_mat_base;
-    a.emis = c->emis; a.num_emis = c->num_emis;
-    memcpy(a.root, c->root, sizeof(a.root));
-    a.cam.pos[0] = cam->pos.x; a.cam.pos[1] = cam->pos.y; a.cam.pos[2] = cam->pos.z;
-    a.cam.dist = cam->dist_from_film; a.cam.focal = cam->focal_length; a.cam.radius = cam->radius;
-    a.cam.w = cam->pxl_width; a.cam.h = cam->pxl_height;
-    a.w = p->width; a.h = p->height; a.spp = p->spp; a.bounces = p->bounces; a.flags = p->flags; a.seed = p->seed;
-    a.shard_index = p->shard_index; a.shard_count = p->shard_count;
-    const uint32_t tw = p->tile_w ? (uint32_t)p->tile_w : kTile, th = p->tile_h ? (uint32_t)p->tile_h : kTile;
-    const uint32_t tx = (p->width + tw - 1) / tw, ty = (p->height + th - 1) / th;
-    const uint32_t ntiles = tx * ty;
-    a.tiles_x = tx;
-    a.tile_w = tw; a.tile_h = th;
-    a.tile_bx = tw / kTile; a.tile_blocks = (tw / kTile) * (th / kTile);
-    a.morton_out = (p->pixel_order == PT_ORDER_MORTON) ? 1u : 0u;
-    a.ntiles_shard = (ntiles > (uint32_t)p->shard_index) ? (ntiles - (uint32_t)p->shard_index + (uint32_t)p->shard_count - 1) / (uint32_t)p->shard_count : 0;
-    a.cull_rel = kCullRel;
-    a.cull_abs = c->scene_extent * 1e-4f;
+    a.spp = p->spp; a.bounces = p->bounces; a.flags = p->flags; a.seed = p->seed;
     const bool refwalk = (p->flags & PT_FLAG_REFERENCE_TRAVERSAL) != 0;
     const bool count = (p->flags & PT_FLAG_COUNT) != 0;
     const uint32_t levels = (uint32_t)c->depth + 2;
@@ -3336,25 +2841,16 @@ static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, f
     if (lds > 160 * 1024) return pt::fail(PT_E_BVH_DEPTH, "pt_render: BVH depth %d needs %zu B of LDS stack", c->depth, lds);
 
     a.pixel_counter = B.pixel_counter;
-    a.nunits = a.ntiles_shard * tw * th;
-    a.scene_fast = c->scene_fast ? 1u : 0u;
-    a.wf_threshold = c->wf_threshold;
-    a.root_first = c->wf_root_first;
-    a.unit_queues = c->wf_queues;
-    a.wf_iters = c->wf_iters;
+    a.nunits = a.npix;
+    a.wf_threshold = K.wf_threshold;
+    a.root_first = K.wf_root_first;
+    a.unit_queues = K.wf_queues;
+    a.wf_iters = K.wf_iters;
     a.node_mask = c->node_mask;
-    a.nodes4 = c->nodes4;
-    a.acc_tris = c->acc_tris;
-    a.rparent = c->rparent;
-    a.hrec = c->hrec;
-    memcpy(a.acc_root, c->acc_root, sizeof(a.acc_root));
-    // the render-path BVH's box margin assumes ray origins within ~2^6 of the scene extent
-    const float cam_ext = std::fmax(std::fabs(cam->pos.x), std::fmax(std::fabs(cam->pos.y), std::fabs(cam->pos.z)));
-    const bool near_cam = cam_ext <= 64.0f * c->scene_extent;
     const bool head = p->integrator == PT_INTEGRATOR_HEAD;
-    const bool wavefront = takes_wavefront(c, p, cam);
+    const bool wavefront = pt::takes_wavefront(p, cam, c->scene_extent, K.head_wf);
     if (acc) {   // (pt_accum_create refused these already: never a silent fall-back to another kernel)
-        if (!wavefront || count || c->wf_min_waves != 5 || c->head_min_waves != 5)
+        if (!wavefront || count || K.wf_min_waves != 5 || K.head_min_waves != 5)
             return pt::fail(PT_E_INVALID, "pt_accum_add: this mode has no accumulating kernel");
         if ((uint64_t)acc->n0 + (uint64_t)p->spp > kAccumMaxSamples)
             return pt::fail(PT_E_INVALID, "pt_accum_add: %u + %d samples exceed what a unit word carries (%u)", acc->n0, p->spp,
@@ -3365,7 +2861,7 @@ static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, f
     // (the wavefront path's init_pixel_states resets the counters itself: one launch less per frame)
     if (!(p->spp > 0 && a.ntiles_shard > 0 && wavefront)) {
         HIP_TRY(hipMemsetAsync(B.counters, 0, kCounterWords * sizeof(unsigned long long), stream));
-        HIP_TRY(hipMemsetAsync(B.counters + 20, 0xff, 2 * sizeof(unsigned long long), stream));   // (atomicMin slots)
+        HIP_TRY(hipMemsetAsync(B.counters + CNT_T_START, 0xff, 2 * sizeof(unsigned long long), stream));   // (atomicMin slots)
         HIP_TRY(hipMemsetAsync(B.tile_counter, 0, 16, stream));
         HIP_TRY(hipMemsetAsync(B.pixel_counter, 0, kQueueStride * (kQueues + 1) * 4, stream));
     }
@@ -3378,7 +2874,8 @@ static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, f
     if (grid > a.ntiles_shard * a.tile_blocks) grid = a.ntiles_shard > 0 ? a.ntiles_shard * a.tile_blocks : 1;
     // the tile kernel traces with the render-path BVH4 walk under the wavefront kernel's conditions
     // (PT_TILE_FAST4=0: the reference-BVH culled walk, as before)
-    a.tile_fast4 = (!refwalk && !(p->flags & PT_FLAG_REFERENCE_BVH) && near_cam && c->tile_fast4 && c->num_tris > 0) ? 1u : 0u;
+    a.tile_fast4 = (!refwalk && !(p->flags & PT_FLAG_REFERENCE_BVH) && pt::near_camera(cam, c->scene_extent) && K.tile_fast4 &&
+                    c->num_tris > 0) ? 1u : 0u;
     HIP_TRY(hipEventRecord(F.ev0, stream));
     bool kernel_events = false;   // ek0/ek1 recorded around the integration kernel (wavefront path)
     bool seeded_now = false;      // seed_table enqueued for p->seed by this render
@@ -3389,152 +2886,50 @@ static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, f
         Args b = a;
         b.stack_words = kRing * 64;
         b.node_mask = c->node4_mask;
-        b.top_nodes = c->top_nodes;
         b.head = head ? 1u : 0u;
-        const uint32_t wpc = (head && !count) ? 4u * (uint32_t)c->head_min_waves : c->wf_waves_per_cu;
-        const size_t lds_fixed = (size_t)kWaveLdsWords * 4 * 4 + 4 * sizeof(unsigned long long) + (kSections + kHist) * 4 +
-                                 kProbeLdsBytes + (head ? (size_t)kHeadLdsLightBytes : 0);
-        {   // as many top nodes as leave every block of a CU its LDS (granted in 1280-B granules): integrator 1's
-            // staged light normals cost it one node at 5 blocks per CU (97 -> 96), which kept it at 4 blocks
-            const uint32_t bpc = std::max(1u, wpc / 4u);
-            const size_t per_block = (size_t)(163840u / bpc) / 1280u * 1280u;
-            const uint32_t cap = per_block > lds_fixed ? (uint32_t)((per_block - lds_fixed) / kTopNodeBytes) : 1u;
-            if (b.top_nodes > 0) b.top_nodes = std::max(1u, std::min(b.top_nodes, cap));   // (0: no triangles, no BVH4)
-        }
-        const size_t lds_wf = lds_fixed + (size_t)b.top_nodes * kTopNodeBytes;
+        // the launch and the work units (render_plan.cpp)
+        pt::PlanInput in;
+        in.num_cus = c->num_cus; in.npix = a.npix; in.spp = p->spp; in.head = head; in.count = count;
+        in.top_nodes = c->top_nodes;
+        in.lds_fixed = (size_t)kWaveLdsWords * 4 * 4 + 4 * sizeof(unsigned long long) + (kSections + kHist) * 4 +
+                       kProbeLdsBytes + (head ? (size_t)kHeadLdsLightBytes : 0);
+        in.top_node_bytes = kTopNodeBytes;
+        pt::UnitPlan plan;
+        // (default budget: a quarter of the device memory free now, plus what lbuf already holds)
+        auto lbuf_budget = [&B](uint64_t* bytes) -> int {
+            size_t fr = 0, tot = 0;
+            HIP_TRY(hipMemGetInfo(&fr, &tot));
+            *bytes = ((uint64_t)fr + (uint64_t)B.lbuf_words * sizeof(double)) / 4;
+            return PT_OK;
+        };
+        if (int rc = pt::plan_units(in, K, lbuf_budget, &plan)) return rc;
+        const uint32_t blocks = plan.blocks, ntail = plan.ntail;
+        const uint32_t paths_per_block = 256u;
+        b.top_nodes = plan.top_nodes;
+        b.nwhole = plan.nwhole; b.ntail = plan.ntail; b.nmid = plan.nmid; b.chunks_mid = plan.chunks_mid;
+        b.chunks = plan.chunks; b.nfin = plan.nfin; b.chunks_fin = plan.chunks_fin; b.nunits = plan.nunits;
+        const size_t lds_wf = in.lds_fixed + (size_t)b.top_nodes * kTopNodeBytes;
         // the whole tree staged in LDS (small scenes: C2): integrator 0's walk steps read it there too
         // (PT_WF_LDS_TREE=0: memory loads, as for a tree larger than the top)
-        const bool lds_tree = c->wf_lds_tree && c->n4 > 0 && b.top_nodes >= c->n4;
+        const bool lds_tree = K.wf_lds_tree && c->n4 > 0 && b.top_nodes >= c->n4;
         // (C2: 7181 with the record's second fetch against 7267 by triangle id; C3 the other way)
         b.rec_shading = lds_tree ? 0u : 1u;
-        uint32_t blocks = (uint32_t)c->num_cus * (wpc / 4 ? wpc / 4 : 1);
-        // Work units: a pixel's samples run in sequence, so a unit lasts one pixel's time and the
-        // kernel's end waits for the last units started.  Whole pixels first; the last `ntail`
-        // pixel slots are split into sample chunks, so the final units are short.
-        // A shard with too few pixels to keep every resident lane busy is split entirely.
-        b.npix = a.ntiles_shard * tw * th;
-        const uint32_t paths_per_block = 256u;
-        const uint64_t lanes = (uint64_t)blocks * paths_per_block;   // concurrently running paths
-        uint32_t chunks = 1, ntail = 0, nmid = 0, chunks_mid = 1;
-        if (c->wf_tail_npix >= 0) {   // (tests: an explicit tail)
-            chunks = (uint32_t)(c->wf_chunks > 0 ? c->wf_chunks : c->wf_tail_chunks);
-            ntail = (uint32_t)std::min<int64_t>(b.npix, c->wf_tail_npix);
-        } else if (c->wf_chunks > 0) {
-            chunks = (uint32_t)c->wf_chunks;
-            ntail = b.npix;
-        } else if (2 * (uint64_t)b.npix < 5 * lanes) {
-            // ~16 fine units per lane, at most 8 chunks per pixel (round 2, after the shading pass got
-            // cheaper: the 1/8 C3 shard +5..6% with 8 chunks instead of 21 and 4 mid chunks instead of
-            // 6, profiles/r02_s4_units; the 1/4 shard alike with 8 or 11)
-            chunks = (uint32_t)std::min<uint64_t>((16 * lanes + b.npix - 1) / b.npix, 8);
-            // longer units first, the finer split for the last wf_fine_px pixels per lane
-            // (measured on C3 shards: 1/4 shard 3 mid chunks, 1/8 shard 6: +3..4% over one split)
-            const uint32_t nfine = (uint32_t)std::min<uint64_t>(b.npix, (uint64_t)(c->wf_fine_px * (double)lanes));
-            // whole pixels first for wf_whole_px of the lanes when the shard has at least wf_whole_min pixels
-            // per lane (a lane's whole pixel is then well within its share of the samples); the rest split
-            // (round 5, profiles/r05_whole: the 1/4 shard with 0.3 / 0.5 / 0.7 / 0.9 whole pixels per lane
-            // against none: C3 +3.4 / +5.0 / -0.6 / -12%, C4 +3.5 / +5.8 / +1.4%)
-            uint32_t nwhole = 0;
-            if ((double)b.npix >= c->wf_whole_min * (double)lanes)
-                nwhole = (uint32_t)std::min<uint64_t>(b.npix - nfine, (uint64_t)(c->wf_whole_px * (double)lanes));
-            ntail = b.npix - nwhole;
-            int mc = c->wf_mid_chunks;
-            if (mc < 0 && nfine < ntail)   // automatic: ~2.5 mid units per lane, at most 3 chunks
-                // (round 5, sample-major split radiance: 3 against 4 at the 1/8 shard, C3 +0.9%, C4 +0.8%,
-                // profiles/r05_mid)
-                mc = std::min(3, (int)std::ceil(2.5 * (double)lanes / (double)(ntail - nfine)));
-            if (mc > 1 && nfine < ntail) {
-                nmid = ntail - nfine;
-                chunks_mid = (uint32_t)std::min(mc, p->spp);
-                if (c->wf_fine_chunks > 0) chunks = (uint32_t)c->wf_fine_chunks;
-            }
-        } else if (c->wf_tail_chunks > 1) {
-            // (measured on C3: +6% with 0.5..1 tail pixel per lane in 4..8 chunks, 0.75 x 6 in round 1;
-            // 1.5 x 6 since the shading pass's fetches were merged)
-            chunks = (uint32_t)c->wf_tail_chunks;
-            ntail = (uint32_t)std::min<uint64_t>(b.npix, (uint64_t)(c->wf_tail_px * (double)lanes));
-        }
-        // (measured on C3 shards: whole pixels down to ~3 per lane; below that ~16 units per lane:
-        // 1/8 shard 20 chunks, 1/4 shard 10)
-        if (chunks > (uint32_t)p->spp) chunks = (uint32_t)p->spp;
-        // Split pixels keep their per-sample radiance (lbuf: 24 B per sample), so the split is
-        // capped at a memory budget (PT_LBUF_BUDGET_MB; default a quarter of the device memory
-        // free now, plus what lbuf already holds): beyond it the first tail slots become whole-pixel
-        // units instead (the split only shortens the kernel's tail; results are identical).
-        if (ntail > 0 && chunks > 1) {
-            uint64_t budget;
-            if (const char* e = getenv("PT_LBUF_BUDGET_MB")) {
-                budget = (uint64_t)(std::max(0.0, atof(e)) * (double)(1ull << 20));   // (fractional MB kept)
-            } else {
-                size_t fr = 0, tot = 0;
-                HIP_TRY(hipMemGetInfo(&fr, &tot));
-                budget = ((uint64_t)fr + (uint64_t)B.lbuf_words * sizeof(double)) / 4;
-            }
-            const uint64_t cap = budget / ((uint64_t)p->spp * 3 * sizeof(double));
-            if (ntail > cap) {
-                const uint32_t drop = ntail - (uint32_t)cap;   // taken from the front: mid grade first
-                nmid = nmid > drop ? nmid - drop : 0;
-                ntail = (uint32_t)cap;
-            }
-        }
-        // final grade: the queue's last units shorter still (the kernel ends when the units started
-        // last are done), carved from the end of the fine grade
-        uint32_t nfin = 0, chunks_fin = 1;
-        if (ntail > nmid && c->wf_fin_px > 0.0 && c->wf_fin_chunks > (int)chunks) {
-            nfin = (uint32_t)std::min<uint64_t>(ntail - nmid, (uint64_t)(c->wf_fin_px * (double)lanes));
-            chunks_fin = (uint32_t)std::min(c->wf_fin_chunks, p->spp);
-        }
-        if ((uint64_t)b.npix + (uint64_t)ntail * (std::max(std::max(chunks, chunks_mid), chunks_fin) - 1) > 0xffffffffull)
-            chunks = 1;
-        if (chunks <= 1 || ntail == 0) { chunks = 1; ntail = 0; nmid = 0; }
-        if (nmid == 0) chunks_mid = 1;
-        if (ntail == 0 || chunks_fin <= chunks) { nfin = 0; chunks_fin = 1; }
-        b.chunks = chunks;
-        b.ntail = ntail;
-        b.nmid = nmid;
-        b.chunks_mid = chunks_mid;
-        b.nfin = nfin;
-        b.chunks_fin = chunks_fin;
-        b.nwhole = b.npix - ntail;
-        b.nunits = b.nwhole + nmid * chunks_mid + (ntail - nmid - nfin) * chunks + nfin * chunks_fin;
-        const uint32_t need = (b.nunits + paths_per_block - 1) / paths_per_block;
-        if (blocks > need) blocks = need;
+        // the buffers the units need, grown on demand
         if (ntail > 0) {
-            const size_t lw = (size_t)ntail * (size_t)p->spp * 3;
-            if (B.lbuf_words < lw) {
-                if (B.lbuf) (void)hipFree(B.lbuf);
-                B.lbuf = nullptr;
-                B.lbuf_words = 0;
-                HIP_TRY(hipMalloc(reinterpret_cast<void**>(&B.lbuf), lw * sizeof(double)));
-                B.lbuf_words = lw;
-            }
+            if (int rc = grow(&B.lbuf, &B.lbuf_words, (size_t)ntail * (size_t)p->spp * 3)) return rc;
+            if (int rc = grow(&B.pmemo, &B.pmemo_words, (size_t)ntail * 2)) return rc;
             b.lbuf = B.lbuf;
-            const size_t mw = (size_t)ntail * 2;
-            if (B.pmemo_words < mw) {
-                if (B.pmemo) (void)hipFree(B.pmemo);
-                B.pmemo = nullptr;
-                B.pmemo_words = 0;
-                HIP_TRY(hipMalloc(reinterpret_cast<void**>(&B.pmemo), mw * 4));
-                B.pmemo_words = mw;
-            }
             b.pmemo = B.pmemo;
         }
         const size_t per_lane = stack_words_per_lane(c);
         const size_t rec_words = head ? (size_t)kHeadWords : (size_t)kColdWords;   // shading record per lane
-        if (int rc = ensure_spill(B, per_lane * (size_t)blocks * 256 + rec_words * (size_t)blocks * paths_per_block))
+        if (int rc = grow(&B.spill, &B.spill_words, per_lane * (size_t)blocks * 256 + rec_words * (size_t)blocks * paths_per_block))
             return rc;
         b.spill = B.spill;
         b.spill_stride = blocks * 256;
         b.cold_stride = blocks * paths_per_block;
         b.cold = B.spill + per_lane * (size_t)b.spill_stride;
-        const size_t sw = (size_t)kUnitWords * b.nunits;
-        if (B.pix_states_words < sw) {
-            if (B.pix_states) (void)hipFree(B.pix_states);
-            B.pix_states = nullptr;
-            B.pix_states_words = 0;
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&B.pix_states), sw * 4));
-            B.pix_states_words = sw;
-        }
+        if (int rc = grow(&B.pix_states, &B.pix_states_words, (size_t)kUnitWords * b.nunits)) return rc;
         b.pix_states = B.pix_states;
         // diagnostic: per-lane end / per-wave start and exit times (PT_LANE_TIMING=file appends a summary)
         const char* timing_path = getenv("PT_LANE_TIMING");
@@ -3546,7 +2941,7 @@ static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, f
             HIP_TRY(hipMemsetAsync(d_times, 0, times.size() * 8, stream));
             b.lane_times = d_times;
         }
-        if (c->use_jump_bytes) {
+        if (K.use_jump_bytes) {
             if (!c->jump_bytes) {   // once per context: 512 byte-sliced 160x160 GF(2) matrices (84 MB)
                 // (built into locals and published only once the build launched: a failure leaves the
                 // context without tables, so the next render tries again instead of seeding from garbage)
@@ -3595,15 +2990,15 @@ static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, f
         }
         else if (head) {
             if (count) hipLaunchKernelGGL((render_head_wf<true, 5>), dim3(blocks), dim3(256), lds_wf, stream, b);
-            else if (c->head_min_waves == 4) hipLaunchKernelGGL((render_head_wf<false, 4>), dim3(blocks), dim3(256), lds_wf, stream, b);
+            else if (K.head_min_waves == 4) hipLaunchKernelGGL((render_head_wf<false, 4>), dim3(blocks), dim3(256), lds_wf, stream, b);
             else hipLaunchKernelGGL((render_head_wf<false, 5>), dim3(blocks), dim3(256), lds_wf, stream, b);
         }
-        else if (count && c->wf_min_waves == 4) hipLaunchKernelGGL((render_unidir_wf<true, 4>), dim3(blocks), dim3(256), lds_wf, stream, b);
+        else if (count && K.wf_min_waves == 4) hipLaunchKernelGGL((render_unidir_wf<true, 4>), dim3(blocks), dim3(256), lds_wf, stream, b);
         else if (count && lds_tree) hipLaunchKernelGGL((render_unidir_wf<true, 5, true>), dim3(blocks), dim3(256), lds_wf, stream, b);
         else if (count) hipLaunchKernelGGL((render_unidir_wf<true, 5>), dim3(blocks), dim3(256), lds_wf, stream, b);
-        else if (c->wf_min_waves == 6) hipLaunchKernelGGL((render_unidir_wf<false, 6>), dim3(blocks), dim3(256), lds_wf, stream, b);
-        else if (c->wf_min_waves == 5 && lds_tree) hipLaunchKernelGGL((render_unidir_wf<false, 5, true>), dim3(blocks), dim3(256), lds_wf, stream, b);
-        else if (c->wf_min_waves == 5) hipLaunchKernelGGL((render_unidir_wf<false, 5>), dim3(blocks), dim3(256), lds_wf, stream, b);
+        else if (K.wf_min_waves == 6) hipLaunchKernelGGL((render_unidir_wf<false, 6>), dim3(blocks), dim3(256), lds_wf, stream, b);
+        else if (K.wf_min_waves == 5 && lds_tree) hipLaunchKernelGGL((render_unidir_wf<false, 5, true>), dim3(blocks), dim3(256), lds_wf, stream, b);
+        else if (K.wf_min_waves == 5) hipLaunchKernelGGL((render_unidir_wf<false, 5>), dim3(blocks), dim3(256), lds_wf, stream, b);
         else hipLaunchKernelGGL((render_unidir_wf<false, 4>), dim3(blocks), dim3(256), lds_wf, stream, b);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(F.ek1, stream));
@@ -3617,7 +3012,7 @@ static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, f
         }
     } else if (p->spp > 0 && a.ntiles_shard > 0) {
         if (a.tile_fast4) {   // the BVH4 walk's ring overflow and the slow walk's stack: one HBM column per lane
-            if (int rc = ensure_spill(B, stack_words_per_lane(c) * (size_t)grid * 64)) return rc;
+            if (int rc = grow(&B.spill, &B.spill_words, stack_words_per_lane(c) * (size_t)grid * 64)) return rc;
             a.spill = B.spill;
             a.spill_stride = grid * 64;
         }
@@ -3670,20 +3065,20 @@ int pt_render_wait(pt_ctx* c, pt_stats* st)
         if (const char* path = getenv("PT_SECTION_DUMP")) {   // counting runs: shading section profile
             if (FILE* f = fopen(path, "a")) {
                 fprintf(f, "sections");
-                for (int k = 0; k < kSections; ++k) fprintf(f, " %llu", cnt[32 + k]);
+                for (int k = 0; k < kSections; ++k) fprintf(f, " %llu", cnt[CNT_SECTIONS + k]);
                 fprintf(f, "\nwalk_hist");
-                for (int k = 0; k < kHist; ++k) fprintf(f, " %llu", cnt[32 + kSections + k]);
-                fprintf(f, "\ntrace_slots %llu walk_slots %llu nodes %llu leaf_steps %llu start_wait %llu top_visits %llu\n", cnt[11], cnt[5],
-                        cnt[2], cnt[6], cnt[12], cnt[13]);
-                fprintf(f, "wall_clock start %llu drained %llu last_exit %llu mean_exit %.1f waves %llu (ticks)\n", cnt[20], cnt[21],
-                        cnt[22], cnt[24] ? (double)cnt[23] / (double)cnt[24] : 0.0, cnt[24]);
+                for (int k = 0; k < kHist; ++k) fprintf(f, " %llu", cnt[CNT_SECTIONS + kSections + k]);
+                fprintf(f, "\ntrace_slots %llu walk_slots %llu nodes %llu leaf_steps %llu start_wait %llu top_visits %llu\n", cnt[CNT_TRACE_SLOTS], cnt[CNT_WALK_SLOTS],
+                        cnt[CNT_NODES], cnt[CNT_LEAF_STEPS], cnt[CNT_START_WAIT], cnt[CNT_TOP_VISITS]);
+                fprintf(f, "wall_clock start %llu drained %llu last_exit %llu mean_exit %.1f waves %llu (ticks)\n", cnt[CNT_T_START], cnt[CNT_T_DRAINED],
+                        cnt[CNT_T_LAST_EXIT], cnt[CNT_WAVES] ? (double)cnt[CNT_T_EXIT_SUM] / (double)cnt[CNT_WAVES] : 0.0, cnt[CNT_WAVES]);
                 fprintf(f, "lane_end_mean %.1f (ticks since start)\ntail_lane_end_log2_10us",
-                        cnt[24] ? (double)cnt[26] / (64.0 * (double)cnt[24]) : 0.0);
-                for (int k = 0; k < kTailBins; ++k) fprintf(f, " %llu", cnt[64 + k]);
+                        cnt[CNT_WAVES] ? (double)cnt[CNT_LANE_END_SUM] / (64.0 * (double)cnt[CNT_WAVES]) : 0.0);
+                for (int k = 0; k < kTailBins; ++k) fprintf(f, " %llu", cnt[CNT_LANE_BINS + k]);
                 fprintf(f, "\ntail_wave_exit_log2_10us");
-                for (int k = 0; k < kTailBins; ++k) fprintf(f, " %llu", cnt[80 + k]);
-                fprintf(f, "\niters_by_deep_lanes 0:%llu 1-4:%llu 5-8:%llu more:%llu no_leaf %llu neither %llu\n", cnt[14],
-                        cnt[15], cnt[16], cnt[17], cnt[18], cnt[19]);
+                for (int k = 0; k < kTailBins; ++k) fprintf(f, " %llu", cnt[CNT_WAVE_BINS + k]);
+                fprintf(f, "\niters_by_deep_lanes 0:%llu 1-4:%llu 5-8:%llu more:%llu no_leaf %llu neither %llu\n", cnt[CNT_ITERS],
+                        cnt[CNT_ITERS + 1], cnt[CNT_ITERS + 2], cnt[CNT_ITERS + 3], cnt[CNT_ITERS + 4], cnt[CNT_ITERS + 5]);
                 fclose(f);
             }
         }
@@ -3697,20 +3092,20 @@ int pt_render_wait(pt_ctx* c, pt_stats* st)
         st->kernel_ms = kms;
         st->work_units = F.units;
         st->split_pixels = F.split;
-        st->rays_traced = cnt[0];
-        st->rays_reference = cnt[1];
-        st->node_tests = cnt[2];
-        st->tri_tests = cnt[3];
-        st->samples = cnt[4];
-        st->walk_lane_slots = cnt[5];
-        st->leaf_steps = cnt[6];
-        st->shade_lane_slots = cnt[7];
-        st->accel_fallbacks = cnt[8];
-        st->walk_cycles = cnt[9];
-        st->shade_cycles = cnt[10];
-        st->spill_entries = cnt[25];
-        st->lds_node_tests = cnt[13];
-        const uint64_t shard_px = cnt[4] / (uint64_t)(F.spp > 0 ? F.spp : 1);
+        st->rays_traced = cnt[CNT_TRACED];
+        st->rays_reference = cnt[CNT_REFERENCE];
+        st->node_tests = cnt[CNT_NODES];
+        st->tri_tests = cnt[CNT_TRIS];
+        st->samples = cnt[CNT_SAMPLES];
+        st->walk_lane_slots = cnt[CNT_WALK_SLOTS];
+        st->leaf_steps = cnt[CNT_LEAF_STEPS];
+        st->shade_lane_slots = cnt[CNT_SHADE_SLOTS];
+        st->accel_fallbacks = cnt[CNT_FALLBACKS];
+        st->walk_cycles = cnt[CNT_WALK_CYCLES];
+        st->shade_cycles = cnt[CNT_SHADE_CYCLES];
+        st->spill_entries = cnt[CNT_SPILL];
+        st->lds_node_tests = cnt[CNT_TOP_VISITS];
+        const uint64_t shard_px = cnt[CNT_SAMPLES] / (uint64_t)(F.spp > 0 ? F.spp : 1);
         st->rays_nominal = shard_px * (uint64_t)F.spp * (uint64_t)(F.bounces + 1);
     }
     return PT_OK;
@@ -3730,14 +3125,15 @@ int pt_render_device(pt_ctx* c, const pt_params* p, const pt_camera* cam, float*
 int pt::accum_check(const pt_ctx* c, const pt_params* p, const pt_camera* cam)
 {
     if (int rc = validate_render(p, cam)) return rc;
+    const RenderKnobs& K = c->knobs;
     if (p->flags & ~(uint32_t)(PT_FLAG_NO_DEAD_PATH_SKIP | PT_FLAG_NO_PRIMARY_CACHE))
         return pt::fail(PT_E_INVALID, "pt_accum_create: flags 0x%x: only PT_FLAG_NO_DEAD_PATH_SKIP and PT_FLAG_NO_PRIMARY_CACHE "
                         "accumulate (the reference walks and the counting variants have no accumulating kernel)", p->flags);
-    if (!takes_wavefront(c, p, cam))
+    if (!takes_wavefront(p, cam, c->scene_extent, K.head_wf))
         return pt::fail(PT_E_INVALID, "pt_accum_create: this render would take the tile kernel (%s), which does not accumulate",
-                        (p->integrator == PT_INTEGRATOR_HEAD && !c->head_wf) ? "integrator 1 with PT_HEAD_WF=0"
+                        (p->integrator == PT_INTEGRATOR_HEAD && !K.head_wf) ? "integrator 1 with PT_HEAD_WF=0"
                                                                               : "camera beyond 64 scene extents");
-    if (c->wf_min_waves != 5 || c->head_min_waves != 5)
+    if (K.wf_min_waves != 5 || K.head_min_waves != 5)
         return pt::fail(PT_E_INVALID, "pt_accum_create: only the default-occupancy kernels accumulate (PT_WF_MIN_WAVES / "
                         "PT_HEAD_MIN_WAVES are set)");
     return PT_OK;
@@ -3812,13 +3208,7 @@ int pt_render(pt_ctx* c, const pt_params* p, const pt_camera* cam, float* out_rg
     if (p->width <= 0 || p->height <= 0) return pt::fail(PT_E_INVALID, "pt_render: bad image size");
     HIP_TRY(hipSetDevice(c->device));
     const size_t bytes = (size_t)p->width * (size_t)p->height * 3 * sizeof(float);
-    if (c->scratch_bytes < bytes) {
-        if (c->scratch_out) (void)hipFree(c->scratch_out);
-        c->scratch_out = nullptr;
-        c->scratch_bytes = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->scratch_out), bytes));
-        c->scratch_bytes = bytes;
-    }
+    if (int rc = grow(&c->scratch_out, &c->scratch_floats, bytes / sizeof(float))) return rc;
     HIP_TRY(hipMemsetAsync(c->scratch_out, 0, bytes, nullptr));
     int rc = pt_render_device(c, p, cam, c->scratch_out, nullptr, st);
     if (rc != PT_OK) return rc;
@@ -3832,17 +3222,6 @@ static size_t stack_words_per_lane(const pt_ctx* c)
     size_t per_lane = (size_t)(3 * c->acc4_depth + 4);
     if (per_lane < (size_t)(2 * (c->depth + 2))) per_lane = (size_t)(2 * (c->depth + 2));
     return per_lane;
-}
-
-static int ensure_spill(pt_ctx::Bufs& B, size_t words)
-{
-    if (B.spill_words >= words) return PT_OK;
-    if (B.spill) (void)hipFree(B.spill);
-    B.spill = nullptr;
-    B.spill_words = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&B.spill), words * 4));
-    B.spill_words = words;
-    return PT_OK;
 }
 
 static bool alloc_bufs(pt_ctx::Bufs& B)
@@ -3890,19 +3269,9 @@ extern "C" int pt_trace_counts(pt_ctx* c, uint32_t n, const float* rays, int32_t
     HIP_TRY(hipSetDevice(c->device));
     Args a;
     memset(&a, 0, sizeof(a));
-    a.nodes = c->nodes; a.rnodes = c->rnodes; a.tris_leaf = c->tris_leaf; a.tris_orig = c->tris_orig;
+    fill_scene_args(a, c);
     a.counters = c->rb[0].counters;
-    a.spheres = c->spheres; a.num_spheres = c->num_spheres; a.num_tris = c->num_tris;
-    a.sphere_mat_base = c->sphere_mat_base;
-    memcpy(a.root, c->root, sizeof(a.root));
-    memcpy(a.acc_root, c->acc_root, sizeof(a.acc_root));
-    a.cull_rel = kCullRel;
-    a.cull_abs = c->scene_extent * 1e-4f;
-    a.scene_fast = c->scene_fast ? 1u : 0u;
     a.node_mask = c->node4_mask;
-    a.nodes4 = c->nodes4;
-    a.acc_tris = c->acc_tris;
-    a.rparent = c->rparent;
     a.stack_words = (uint32_t)(c->depth + 2) * 64;
     if (a.stack_words < (uint32_t)kWaveLdsWords) a.stack_words = kWaveLdsWords;
     const size_t lds = (size_t)a.stack_words * 4 * 4;
@@ -3910,7 +3279,7 @@ extern "C" int pt_trace_counts(pt_ctx* c, uint32_t n, const float* rays, int32_t
     uint32_t blocks = (n + 255) / 256;
     const uint32_t cap = (uint32_t)c->num_cus * 8u;
     if (blocks > cap) blocks = cap;
-    if (int rc = ensure_spill(c->rb[0], stack_words_per_lane(c) * (size_t)blocks * 256)) return rc;
+    if (int rc = grow(&c->rb[0].spill, &c->rb[0].spill_words, stack_words_per_lane(c) * (size_t)blocks * 256)) return rc;
     a.spill = c->rb[0].spill;
     a.spill_stride = blocks * 256;
     float* d_rays = nullptr;
@@ -3945,7 +3314,7 @@ extern "C" int pt_trace_counts(pt_ctx* c, uint32_t n, const float* rays, int32_t
         }
         if (spill_entries) {
             unsigned long long v = 0;
-            HIP_TRY(hipMemcpy(&v, c->rb[0].counters + 25, sizeof(v), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(&v, c->rb[0].counters + CNT_SPILL, sizeof(v), hipMemcpyDeviceToHost));
             *spill_entries = v;
         }
         return PT_OK;
@@ -3966,7 +3335,7 @@ static int features_check(const pt_ctx* c, const pt_params* p, const pt_camera* 
         return pt::fail(PT_E_INVALID, "pt_render_features: %d asynchronous renders in flight (pt_render_wait first)", c->fl_n);
     *vp = *p;
     vp->spp = 0; vp->bounces = 1; vp->integrator = PT_INTEGRATOR_UNIDIR; vp->flags = 0; vp->seed = 0;
-    if (int rc = validate_render(vp, cam)) return rc;
+    if (int rc = pt::validate_render(vp, cam)) return rc;
     if ((uint64_t)c->num_tris + (uint64_t)c->num_spheres >= (uint64_t)PT_FEATURE_EMISSIVE)
         return pt::fail(PT_E_INVALID, "pt_render_features: %u triangles + %u spheres do not fit the 30 id bits of pt_feature.prim",
                         c->num_tris, c->num_spheres);
@@ -3986,40 +3355,16 @@ extern "C" int pt_render_features_device(pt_ctx* c, const pt_params* p_in, const
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
     Args a;
     memset(&a, 0, sizeof(a));
-    a.nodes = c->nodes; a.rnodes = c->rnodes; a.tris_leaf = c->tris_leaf; a.tris_orig = c->tris_orig;
-    a.shade = c->shade; a.mats = c->mats;
-    a.spheres = c->spheres; a.num_spheres = c->num_spheres; a.num_tris = c->num_tris;
-    a.sphere_mat_base = c->sphere_mat_base;
-    memcpy(a.root, c->root, sizeof(a.root));
-    memcpy(a.acc_root, c->acc_root, sizeof(a.acc_root));
-    a.cam.pos[0] = cam->pos.x; a.cam.pos[1] = cam->pos.y; a.cam.pos[2] = cam->pos.z;
-    a.cam.dist = cam->dist_from_film; a.cam.focal = cam->focal_length; a.cam.radius = cam->radius;
-    a.cam.w = cam->pxl_width; a.cam.h = cam->pxl_height;
-    a.w = p->width; a.h = p->height;
-    a.shard_index = p->shard_index; a.shard_count = p->shard_count;
-    const uint32_t tw = p->tile_w ? (uint32_t)p->tile_w : kTile, th = p->tile_h ? (uint32_t)p->tile_h : kTile;
-    const uint32_t tx = (p->width + tw - 1) / tw, ty = (p->height + th - 1) / th;
-    const uint32_t ntiles = tx * ty;
-    a.tiles_x = tx;
-    a.tile_w = tw; a.tile_h = th;
-    a.tile_bx = tw / kTile; a.tile_blocks = (tw / kTile) * (th / kTile);
-    a.morton_out = (p->pixel_order == PT_ORDER_MORTON) ? 1u : 0u;
-    a.ntiles_shard = (ntiles > (uint32_t)p->shard_index) ? (ntiles - (uint32_t)p->shard_index + (uint32_t)p->shard_count - 1) / (uint32_t)p->shard_count : 0;
-    a.npix = a.ntiles_shard * tw * th;
-    a.cull_rel = kCullRel;
-    a.cull_abs = c->scene_extent * 1e-4f;
-    a.scene_fast = c->scene_fast ? 1u : 0u;
+    fill_scene_args(a, c);
+    fill_view_args(a, *p, *cam);
     a.node_mask = c->node4_mask;
-    a.nodes4 = c->nodes4;
-    a.acc_tris = c->acc_tris;
-    a.rparent = c->rparent;
     a.stack_words = kWaveLdsWords;
     const size_t lds = (size_t)a.stack_words * 4 * 4;
     if (a.npix == 0) return PT_OK;
     uint32_t blocks = (uint32_t)(((uint64_t)a.npix + 255) / 256);
     const uint32_t cap = (uint32_t)c->num_cus * 8u;
     if (blocks > cap) blocks = cap;
-    if (int rc = ensure_spill(c->rb[0], stack_words_per_lane(c) * (size_t)blocks * 256)) return rc;
+    if (int rc = grow(&c->rb[0].spill, &c->rb[0].spill_words, stack_words_per_lane(c) * (size_t)blocks * 256)) return rc;
     a.spill = c->rb[0].spill;
     a.spill_stride = blocks * 256;
     hipLaunchKernelGGL(primary_features, dim3(blocks), dim3(256), lds, stream, a, reinterpret_cast<float4*>(d_feat));
@@ -4060,18 +3405,12 @@ extern "C" int pt_shard_pixels(int w, int h, int shard_index, int shard_count, i
         return pt::fail(PT_E_INVALID, "pt_shard_pixels: bad arguments");
     for (const int v : {tile_w, tile_h})
         if (v != 0 && (v < 8 || v > 256 || v % 8 != 0)) return pt::fail(PT_E_INVALID, "pt_shard_pixels: tile size %dx%d", tile_w, tile_h);
-    TileMap m;
-    m.w = w; m.h = h; m.shard_index = shard_index; m.shard_count = shard_count;
-    m.tile_w = tile_w ? (uint32_t)tile_w : kTile;
-    m.tile_h = tile_h ? (uint32_t)tile_h : kTile;
-    m.tiles_x = ((uint32_t)w + m.tile_w - 1) / m.tile_w;
-    const uint32_t ntiles = m.tiles_x * (((uint32_t)h + m.tile_h - 1) / m.tile_h);
-    m.tile_bx = m.tile_w / kTile;
-    m.tile_blocks = m.tile_bx * (m.tile_h / kTile);
-    const uint32_t nts = (ntiles > (uint32_t)shard_index) ? (ntiles - (uint32_t)shard_index + (uint32_t)shard_count - 1) / (uint32_t)shard_count : 0u;
-    const uint64_t slots = (uint64_t)nts * m.tile_w * m.tile_h;
-    if ((uint64_t)(((uint32_t)h + m.tile_h - 1) / m.tile_h) * m.tiles_x * m.tile_w * m.tile_h > 0xffffffffull)
-        return pt::fail(PT_E_INVALID, "pt_shard_pixels: %dx%d pads to more than 2^32-1 pixel slots", w, h);
+    pt_params p;
+    memset(&p, 0, sizeof(p));
+    p.width = w; p.height = h; p.shard_index = shard_index; p.shard_count = shard_count; p.tile_w = tile_w; p.tile_h = tile_h;
+    const pt::TileGrid m = pt::tile_grid(p);
+    if (!m.fits()) return pt::fail(PT_E_INVALID, "pt_shard_pixels: %dx%d pads to more than 2^32-1 pixel slots", w, h);
+    const uint64_t slots = m.npix;
     uint32_t n = 0;
     for (uint64_t q = 0; q < slots; ++q) {
         uint32_t px, py;
@@ -4088,17 +3427,8 @@ extern "C" int pt_shard_pixels(int w, int h, int shard_index, int shard_count, i
 
 int pt::shard_slots(const pt_params* p, std::vector<uint32_t>* pix)
 {
-    TileMap m;
-    m.w = p->width; m.h = p->height; m.shard_index = p->shard_index; m.shard_count = p->shard_count;
-    m.tile_w = p->tile_w ? (uint32_t)p->tile_w : kTile;
-    m.tile_h = p->tile_h ? (uint32_t)p->tile_h : kTile;
-    m.tiles_x = ((uint32_t)p->width + m.tile_w - 1) / m.tile_w;
-    const uint32_t ntiles = m.tiles_x * (((uint32_t)p->height + m.tile_h - 1) / m.tile_h);
-    m.tile_bx = m.tile_w / kTile;
-    m.tile_blocks = m.tile_bx * (m.tile_h / kTile);
-    const uint32_t nts = (ntiles > (uint32_t)p->shard_index)
-                             ? (ntiles - (uint32_t)p->shard_index + (uint32_t)p->shard_count - 1) / (uint32_t)p->shard_count : 0u;
-    const size_t slots = (size_t)nts * m.tile_w * m.tile_h;   // (= Args::npix of this shard's renders)
+    const pt::TileGrid m = pt::tile_grid(*p);
+    const size_t slots = m.npix;   // (= Args::npix of this shard's renders)
     pix->assign(slots, 0xffffffffu);
     for (size_t q = 0; q < slots; ++q) {
         uint32_t px, py;
