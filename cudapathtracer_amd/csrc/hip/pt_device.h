@@ -249,6 +249,23 @@ __device__ __forceinline__ bool ray_fast(V3 o, V3 d)
     return coord_ok(o.x) && coord_ok(o.y) && coord_ok(o.z) && dir_ok(d.x) && dir_ok(d.y) && dir_ok(d.z);
 }
 
+// The culled walks (the BVH4 walk and trace_slow) skip boxes, so they equal the reference's walk only for
+// rays whose every accepted hit lies in the boxes around its triangle.  The integrator's rays are such rays
+// (unit directions, origins in or near the scene); a caller's rays (pt_trace, pt_render_features) need not be:
+//  - a far origin: the conservative box test t = fma(plane, inv, -o*inv) errs by about |o| * 2^-24 per term in
+//    distance units, and the boxes' margin (accel_build.cpp: max(extent, 1) * 2^-16) covers that only up to
+//    |o_k| <= 64 extents, the rule near_camera() applies to whole renders;
+//  - a long direction: triIntersect's rejection of (near-)degenerate triangles, |a| < 0.00001, scales with |d|,
+//    so at |d| >> 1 a zero-area triangle passes it and "hits" at a t that lies outside its bounds; up to
+//    |d|^2 <= 1 + 2^-10 (a normalised direction, however sloppily) the rejection is the integrator's own.
+// Rays outside either bound take the reference's own walk (trace_reference), which skips nothing.
+constexpr float kDirLen2Max = 1.0f + 0x1p-10f;
+__device__ __forceinline__ bool ray_regular(V3 o, V3 d, float origin_max)
+{
+    const float m = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(o.x), __builtin_fabsf(o.y)), __builtin_fabsf(o.z));
+    return m <= origin_max && dot(d, d) <= kDirLen2Max;   // (false for an overflowing |d|^2)
+}
+
 // slab test of BVH.h:51-83; kMk selects the Markstein quotient (same bits as '/').
 template <bool kMk>
 __device__ __forceinline__ bool slab(V3 o, V3 d, V3 y, float lx, float ly, float lz, float hx, float hy, float hz,
@@ -968,17 +985,19 @@ struct Hit {
 
 // kernel.cu:112-161 trace(): the reference's exact walk -- left child first, every box the
 // line overlaps, strict 0 < t < closestT.  The stack lives in LDS (kStack entries per lane,
-// lane-interleaved: entry k of lane l at stack[k*64 + l]).
+// lane-interleaved: entry k of lane l at stack[k*64 + l]) -- or, for the batched entry points'
+// irregular rays (ray_regular), in the lane's HBM spill column: stack = its base, lane = 0,
+// stride = the column stride; the walk holds at most depth + 2 entries (stack_words_per_lane).
 template <bool kCount>
 __device__ __forceinline__ Hit trace_reference(V3 o, V3 d, const RNode* __restrict__ nodes, const DTri* __restrict__ tris,
-                                               uint32_t* stack, int lane, Counters& cnt)
+                                               uint32_t* stack, int lane, Counters& cnt, int stride = 64)
 {
     float closest = kMaxFloat;
     int32_t best = -1;
     int i = 0;
     stack[lane] = 0;
     while (i >= 0) {
-        const uint32_t e = stack[i * 64 + lane];
+        const uint32_t e = stack[i * stride + lane];
         if (e & kLeaf) {
             const uint32_t k = e ^ kLeaf;
             uint32_t id;
@@ -994,8 +1013,8 @@ __device__ __forceinline__ Hit trace_reference(V3 o, V3 d, const RNode* __restri
             float ti, to;
             // p = lo.xyz, hi.x ; q = hi.yz, left, right
             if (slab_ref(o, d, p.x, p.y, p.z, p.w, q.x, q.y, &ti, &to)) {
-                stack[i * 64 + lane] = __float_as_uint(q.w);
-                stack[(i + 1) * 64 + lane] = __float_as_uint(q.z);
+                stack[i * stride + lane] = __float_as_uint(q.w);
+                stack[(i + 1) * stride + lane] = __float_as_uint(q.z);
                 ++i;
             } else {
                 --i;

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -120,6 +121,9 @@ struct Args {
     // above are what the plain kernels' scalar loads were tuned with.)
     uint32_t accum;                 // 1: accumulating pass
     uint32_t acc_n0;                // samples every pixel of the shard has already (N)
+    float origin_max;               // trace_rays, primary_features: largest |o_k| of a regular ray (ray_regular):
+                                    // 64 scene extents, near_camera()'s rule per ray.  (It fills the 4 bytes of
+                                    // padding before acc_rng: no offset moves and the struct does not grow.)
     uint32_t* acc_rng;              // per pixel slot q: XORWOW after its last finished sample, word k (v0..v4, d)
                                     // at [k * npix + q] (a wave's 64 slots: one 256-B row per word)
     double* acc_mean;               // per pixel slot q: the f64 running mean, channel k at [k * npix + q]
@@ -135,6 +139,7 @@ enum : uint32_t {
     CNT_SECTIONS = 32,                  // kSections section counts, then kHist walk-length buckets
     CNT_LANE_BINS = 64, CNT_WAVE_BINS = 80   // kTailBins each
 };
+static_assert(offsetof(Args, origin_max) + 4 == offsetof(Args, acc_rng), "origin_max sits in Args' padding");
 constexpr int kCounterWords = 96;
 // Unit words of an accumulating pass: UW_N0 bit 30 marks a pixel's first unit of the pass (chunk 0, or the
 // whole pixel) -- `n == 1` no longer does; its sample numbers are the 30 bits below.
@@ -2400,7 +2405,8 @@ __global__ __launch_bounds__(256) void tonemap_codes(const float* __restrict__ r
 // ------------------------------------------------------------------ batched trace()
 // pt_trace: the reference's trace() (kernel.cu:112-161) for a batch of rays, one lane per ray,
 // on the same walk the wavefront kernel uses (BVH4 + winner check + exact slow path), or on the
-// reference BVH with the reference's own stack walk (kRef).
+// reference BVH with the reference's own stack walk (kRef).  A caller's rays need not be the
+// integrator's: those outside ray_regular() take the reference's walk too (pt_device.h).
 template <bool kRef, bool kCount>
 __global__ __launch_bounds__(256) void trace_rays(Args a, const float* __restrict__ rays, uint32_t n,
                                                   int32_t* __restrict__ tri_out, float* __restrict__ t_out)
@@ -2427,6 +2433,11 @@ __global__ __launch_bounds__(256) void trace_rays(Args a, const float* __restric
             // spheres only
         } else if (kRef) {
             const Hit h = trace_reference<kCount>(o, d, a.rnodes, a.tris_orig, wave_lds, lane, cnt);
+            htri = h.tri; ht = h.t;
+        } else if (!ray_regular(o, d, a.origin_max)) {
+            // a far origin or a long direction: the reference's walk, its stack in this lane's spill column
+            atomicAdd(a.counters + CNT_FALLBACKS, 1ull);
+            const Hit h = trace_reference<kCount>(o, d, a.rnodes, a.tris_orig, S.spill(), 0, cnt, (int)S.stride);
             htri = h.tri; ht = h.t;
         } else if (!((a.scene_fast != 0u) && ray_fast(o, d))) {
             atomicAdd(a.counters + CNT_FALLBACKS, 1ull);
@@ -2488,6 +2499,9 @@ __global__ __launch_bounds__(256) void primary_features(Args a, float4* __restri
         float ht = kMaxFloat;
         if (a.num_tris == 0) {
             // spheres only
+        } else if (!ray_regular(o, d, a.origin_max)) {   // (a far camera, as trace_rays<false, *> traces its rays)
+            const Hit h = trace_reference<false>(o, d, a.rnodes, a.tris_orig, S.spill(), 0, cnt, (int)S.stride);
+            htri = h.tri; ht = h.t;
         } else if (!((a.scene_fast != 0u) && ray_fast(o, d))) {
             trace_slow(o, d, a.root, a.nodes, a.tris_leaf, S.spill(), S.stride, a.cull_rel, a.cull_abs, &htri, &ht,
                        cnt.tri_counts);
@@ -2778,6 +2792,7 @@ static void fill_scene_args(Args& a, const pt_ctx* c)
     memcpy(a.acc_root, c->acc_root, sizeof(a.acc_root));
     a.cull_rel = kCullRel;
     a.cull_abs = c->scene_extent * 1e-4f;
+    a.origin_max = 64.0f * c->scene_extent;
     a.scene_fast = c->scene_fast ? 1u : 0u;
     a.nodes4 = c->nodes4;
     a.acc_tris = c->acc_tris;

@@ -388,7 +388,16 @@ int pt_accum_add_until(pt_accum* acc, pt_noise* noise, const pt_converge_params*
 /* The reference's trace() (kernel.cu:112-161) for n rays given as rays[6n] = {o.xyz, d.xyz}
  * (host buffers): tri_out[i] = winning ORIGINAL triangle index or -1, t_out[i] = its closestT
  * (MAX_FLOAT = 1e5 on a miss).  flags: 0 = the render path's walk, PT_FLAG_REFERENCE_BVH = the
- * reference's own stack walk on its BVH.  Bit-identical to the reference for both.  Blocking. */
+ * reference's own stack walk on its BVH.  Bit-identical to the reference for both, for every ray
+ * with finite components and a non-zero direction.  Blocking.
+ * With flags = 0 the walk is chosen per ray: the BVH4 walk for a regular ray inside the Markstein
+ * ranges (origin coordinates 0 or in [2^-50, 2^20], direction components 0 or in [2^-100, 2^45],
+ * and a scene whose coordinates all are 0 or in [2^-50, 2^20]); the exact culled walk on the
+ * reference BVH for a regular ray outside them; and the reference's own stack walk -- slower, it
+ * culls nothing -- for a ray that is not regular.  Regular: max |o_k| <= 64 * the scene's extent
+ * (its largest absolute coordinate) and d.x*d.x + d.y*d.y + d.z*d.z <= 1 + 2^-10 in float, i.e. an
+ * origin no farther out than a plain render's camera may be for the render path's own walk, and a
+ * direction no longer than a normalised one. */
 int pt_trace(pt_ctx* ctx, uint32_t n, const float* rays, int32_t* tri_out, float* t_out, uint32_t flags);
 
 /* trace() as above, plus diagnostics (either may be NULL):
@@ -425,7 +434,9 @@ int pt_tonemap(pt_ctx* ctx, const float* rgb, int width, int height, int32_t* co
  * refusal while asynchronous renders are in flight) and ignores spp, bounces, integrator, seed and flags.
  * The ray of pixel (x, y) is pt_camera_ray(cam, pt_morton_pxl_to_i(x, y), lens = 0, ...) -- a thin-lens
  * camera still gets its pinhole ray, the features are the sharp ones -- traced by the render path's own
- * walk (what pt_trace(flags = 0) runs: the reference's trace() bit for bit); hit ids as pt_trace's (the
+ * walk (what pt_trace(flags = 0) runs: the reference's trace() bit for bit, for a camera at any finite
+ * position -- one farther than 64 scene extents from the origin gets the slower walk pt_trace gives a
+ * ray from there); hit ids as pt_trace's (the
  * original triangle index, num_tris + i for sphere i).  A scene with num_tris + num_spheres >= 2^30 is
  * PT_E_INVALID (the id shares its word with PT_FEATURE_EMISSIVE).  Records are indexed like the image
  * (params->pixel_order).  _device: d_feat is a device buffer of W*H records, 16-byte aligned (PT_E_INVALID
