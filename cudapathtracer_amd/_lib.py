@@ -116,6 +116,11 @@ class ConvergeResult(C.Structure):
     _fields_ = [("passes", C.c_int32), ("stopped_converged", C.c_int32), ("last", NoiseSummary)]
 
 
+class AdaptiveResult(C.Structure):
+    _fields_ = [("passes", C.c_int32), ("stopped_converged", C.c_int32), ("last", NoiseSummary),
+                ("active", C.c_uint64), ("samples_total", C.c_uint64)]
+
+
 assert C.sizeof(Feature) == 48
 assert C.sizeof(NoiseSummary) == 32 + 64 * 8 and C.sizeof(ConvergeParams) == 24
 assert C.sizeof(Vec3) == 12 and C.sizeof(Triangle) == 28 and C.sizeof(Material) == 48
@@ -182,6 +187,13 @@ SIGNATURES = {
     "pt_noise_destroy": (None, [C.c_void_p]),
     "pt_accum_add_until": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ConvergeParams), C.c_void_p, C.c_void_p,
                                      C.POINTER(ConvergeResult)]),
+    "pt_accum_freeze": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pt_accum_counts": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pt_accum_active": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "pt_noise_freeze": (C.c_int, [C.c_void_p, C.POINTER(NoiseParams), C.c_void_p, C.POINTER(C.c_uint64),
+                                  C.POINTER(C.c_uint64)]),
+    "pt_accum_add_adaptive": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ConvergeParams), C.c_void_p, C.c_void_p,
+                                        C.POINTER(AdaptiveResult)]),
     "pt_denoise_defaults": (None, [C.POINTER(DenoiseParams)]),
     "pt_render_features_device": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.c_void_p, C.c_void_p]),
     "pt_render_features": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.c_void_p]),

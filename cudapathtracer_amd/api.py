@@ -522,6 +522,45 @@ class Accumulator:
         return dict(passes=int(res.passes), stopped_converged=bool(res.stopped_converged), samples=self.samples,
                     summary=res.last.as_dict())
 
+    def freeze(self, mask):
+        """Freeze the pixels where `mask` (shaped like the image without its channel axis) is non-zero: they are
+        never sampled again, and add() renders the others only (pt_accum_freeze).  Permanent; zeros change nothing."""
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if m.size != self.params.width * self.params.height:
+            raise ValueError("mask of %d entries for a %dx%d image" % (m.size, self.params.width, self.params.height))
+        L.check(L.lib().pt_accum_freeze(self._h, m.ctypes.data))
+
+    def counts(self):
+        """Every pixel's sample count, uint32, shaped like the image without its channel axis (outside the shard 0)."""
+        out = np.zeros(self._shape()[:-1], dtype=np.uint32)
+        L.check(L.lib().pt_accum_counts(self._h, out.ctypes.data))
+        return out
+
+    def active_pixels(self):
+        """The scanline ids y*W + x of the pixels still sampled, in work order (the device's active list)."""
+        n = C.c_uint64(0)
+        L.check(L.lib().pt_accum_active(self._h, None, 0, C.byref(n)))
+        out = np.zeros(int(n.value), dtype=np.uint32)
+        if out.size:
+            L.check(L.lib().pt_accum_active(self._h, out.ctypes.data, out.size, C.byref(n)))
+        return out
+
+    def add_adaptive(self, pass_spp, max_samples, tol=None, quantile=0.95, min_batches=2, y_floor=None, d_out_ptr=None,
+                     stream_ptr=None):
+        """add_until that freezes every pixel once its relative standard error is <= tol and samples only the rest
+        (pt_accum_add_adaptive).  Returns dict(passes, stopped_converged, samples, summary, active, samples_total)."""
+        est = self._noise if self._noise is not None else self.noise()
+        cp = L.ConvergeParams()
+        cp.pass_spp, cp.max_samples, cp.min_batches = int(pass_spp), int(max_samples), int(min_batches)
+        cp.quantile = float(quantile)
+        cp.noise = _noise_params(tol, y_floor)
+        res = L.AdaptiveResult()
+        L.check(L.lib().pt_accum_add_adaptive(self._h, est._h, C.byref(cp),
+                                              None if d_out_ptr is None else C.c_void_p(int(d_out_ptr)),
+                                              None if stream_ptr is None else C.c_void_p(int(stream_ptr)), C.byref(res)))
+        return dict(passes=int(res.passes), stopped_converged=bool(res.stopped_converged), samples=self.samples,
+                    summary=res.last.as_dict(), active=int(res.active), samples_total=int(res.samples_total))
+
 
 class NoiseEstimate:
     """Per-pixel noise estimate of an accumulator (pt_noise_*): batch means of the passes added since it was
@@ -563,6 +602,15 @@ class NoiseEstimate:
         L.check(L.lib().pt_noise_update(self._h, C.byref(np_), None if stream_ptr is None else C.c_void_p(int(stream_ptr)),
                                         C.byref(s)))
         return s.as_dict()
+
+    def freeze(self, tol=None, y_floor=None, stream_ptr=None):
+        """Freeze every active pixel whose relative standard error is <= tol, on the device (pt_noise_freeze).
+        Returns (newly_frozen, active)."""
+        np_ = _noise_params(tol, y_floor)
+        newly, active = C.c_uint64(0), C.c_uint64(0)
+        L.check(L.lib().pt_noise_freeze(self._h, C.byref(np_), None if stream_ptr is None else C.c_void_p(int(stream_ptr)),
+                                        C.byref(newly), C.byref(active)))
+        return int(newly.value), int(active.value)
 
     def read(self):
         """(mu, m2): the window's mean luminance and weighted sum of squared deviations, float64, shaped like the

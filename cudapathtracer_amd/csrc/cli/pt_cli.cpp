@@ -31,6 +31,12 @@
 //                                         starts a fresh estimator window at the resumed state
 // --error-map FILE.pfm                    with --pass-spp K: write the squared relative standard error of every
 //                                         pixel ((float)rel2 of pt_noise_map) as a grey PFM
+// --adaptive                              with --until-error: freeze every pixel once its error is <= TOL (after at least
+//                                         B passes) and sample only the others from then on (pt_noise_freeze; the
+//                                         loop of pt_accum_add_adaptive).  Not with --checkpoint: format version 1
+//                                         holds a single sample count
+// --count-map FILE.pfm                    with --pass-spp K: write every pixel's sample count (pt_accum_counts) as a
+//                                         grey PFM
 // --denoise [ITERS]                       filter the image with the edge-avoiding a-trous denoiser (pt_denoise,
 //                                         ITERS iterations, default 5) before the PPM / PFM is written -- also
 //                                         after every --pass-spp pass, after --resume and after the multi-GPU
@@ -68,9 +74,12 @@ struct Obj {
             "              [--tri-counts out.csv [--reference-walk]] [--morton] [--tile WxH]\n"
             "              [--checkpoint FILE] [--resume FILE] [--pass-spp K]\n"
             "              [--denoise [ITERS]] [--aov PREFIX]\n"
-            "              [--until-error TOL [--error-quantile Q] [--min-batches B]] [--error-map FILE.pfm]\n"
+            "              [--until-error TOL [--error-quantile Q] [--min-batches B] [--adaptive]] [--error-map FILE.pfm]\n"
+            "              [--count-map FILE.pfm]\n"
             "  --until-error TOL  with --pass-spp: stop once the fraction Q (default 0.95) of the pixels has a relative\n"
             "                     standard error <= TOL after at least B (default 2) passes; --spp is the cap\n"
+            "  --adaptive         with --until-error: freeze each pixel once its error is <= TOL and sample only the rest\n"
+            "  --count-map FILE   with --pass-spp: write the per-pixel sample counts as a grey PFM\n"
             "  --error-map FILE   with --pass-spp: write the per-pixel squared relative standard error as a grey PFM\n"
             "  --denoise [ITERS]  filter the image (edge-avoiding a-trous, ITERS iterations, default 5) before it is written\n"
             "  --aov PREFIX       write PREFIX_albedo.pfm, PREFIX_normal.pfm, PREFIX_position.pfm, PREFIX_depth.pfm\n");
@@ -126,8 +135,8 @@ int main(int argc, char** argv)
     pt_denoise_params dparams;
     pt_denoise_defaults(&dparams);
     std::string aov;
-    bool until_error = false;
-    std::string error_map;
+    bool until_error = false, adaptive = false;
+    std::string error_map, count_map;
     pt_converge_params conv{};
     conv.min_batches = 2; conv.quantile = 0.95f;
     pt_noise_defaults(&conv.noise);
@@ -179,6 +188,8 @@ int main(int argc, char** argv)
         else if (a == "--error-quantile") conv.quantile = strtof(next().c_str(), nullptr);
         else if (a == "--min-batches") conv.min_batches = atoi(next().c_str());
         else if (a == "--error-map") error_map = next();
+        else if (a == "--adaptive") adaptive = true;
+        else if (a == "--count-map") count_map = next();
         else if (a == "-h" || a == "--help") usage(nullptr);
         else usage(("unknown option " + a).c_str());
     }
@@ -197,6 +208,9 @@ int main(int argc, char** argv)
     if (!(conv.noise.tol > 0.0f)) usage("--until-error takes a tolerance > 0");
     if (!(conv.quantile > 0.0f && conv.quantile <= 1.0f)) usage("--error-quantile is in (0, 1]");
     if (conv.min_batches < 2) usage("--min-batches must be >= 2");
+    if (adaptive && !until_error) usage("--adaptive needs --until-error TOL (the tolerance pixels are frozen at)");
+    if (adaptive && !checkpoint.empty()) usage("--adaptive cannot write a --checkpoint (format version 1 holds a single sample count)");
+    if (!count_map.empty() && pass_spp < 1) usage("--count-map needs --pass-spp K");
     const bool accumulate = !checkpoint.empty() || !resume.empty() || pass_spp > 0;
     if (accumulate && gpus != 1) usage("--checkpoint / --resume / --pass-spp need --gpus 1 (one accumulator per shard)");
     if (accumulate && (!tri_csv.empty() || ref_walk)) usage("--tri-counts and --reference-walk do not accumulate");
@@ -323,6 +337,12 @@ int main(int argc, char** argv)
                     printf("converged %llu of %llu pixels (%.4f) at tolerance %g after %d batches\n", (unsigned long long)ns.converged,
                            (unsigned long long)ns.pixels, ns.pixels ? (double)ns.converged / (double)ns.pixels : 0.0,
                            (double)conv.noise.tol, ns.batches);
+                if (adaptive && ns.batches >= conv.min_batches) {   // pt_accum_add_adaptive's step: freeze what converged
+                    uint64_t newly = 0, active = 0;
+                    if (pt_noise_freeze(noise, &conv.noise, nullptr, &newly, &active) != PT_OK) return die("pt_noise_freeze");
+                    if (!quiet) printf("froze %llu pixels, %llu still sampled\n", (unsigned long long)newly, (unsigned long long)active);
+                    if (active == 0) converged = true;
+                }
             }
             if (pass_spp > 0 && left > step && !converged) {   // (the last pass's files are written below)
                 if (pt_accum_read(acc, img.data(), nullptr) != PT_OK) return die("pt_accum_read");
@@ -335,6 +355,18 @@ int main(int argc, char** argv)
         if (until_error)   // (printed with --quiet too: it is the run's result)
             printf("stopped at %lld samples: %s\n", (long long)pt_accum_samples(acc),
                    converged ? "converged" : "not converged (the sample cap)");
+        if (!count_map.empty()) {
+            const size_t npix = (size_t)p.width * p.height;
+            std::vector<uint32_t> cnt(npix);
+            std::vector<float> grey(npix * 3);
+            if (pt_accum_counts(acc, cnt.data()) != PT_OK) return die("pt_accum_counts");
+            for (int y = 0; y < p.height; ++y)
+                for (int x = 0; x < p.width; ++x) {
+                    const uint32_t v = cnt[p.pixel_order == PT_ORDER_MORTON ? (size_t)pt_morton_pxl_to_i(x, y) : (size_t)y * p.width + x];
+                    for (int k = 0; k < 3; ++k) grey[((size_t)y * p.width + x) * 3 + k] = (float)v;
+                }
+            if (pt_write_pfm(count_map.c_str(), grey.data(), p.width, p.height) != PT_OK) return die("--count-map");
+        }
         if (!error_map.empty()) {
             const size_t npix = (size_t)p.width * p.height;
             std::vector<float> rel2(npix), grey(npix * 3);

@@ -3,6 +3,9 @@
 // kernel.cu:527-553) as passes of the wavefront kernels over a per-pixel state kept on the device, and that
 // state's checkpoint file.  Host code over the HIP runtime (no kernels): the passes themselves are
 // pt::accum_pass (pt_render.hip).
+// Adaptive sampling (pt_accum_freeze, pt_noise_freeze): a frozen pixel is never sampled again.  Its slot of the
+// frozen_at plane holds the sample count it stopped at; the other pixels all have `samples`.  Once a pixel is
+// frozen a pass runs over the active list (pt_adaptive.hip), rebuilt only when the frozen set changed.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -97,12 +100,90 @@ struct pt_accum {
     uint32_t* d_rng = nullptr;        // 6 words per slot, word-major
     double* d_mean = nullptr;         // 3 doubles per slot, channel-major
     pt_noise* noise = nullptr;        // the live estimator attached to this accumulator (pt_noise.hip), if any
+    // adaptive sampling, allocated on first use (an accumulator that never freezes a pixel has none of it)
+    uint64_t pixels = 0;              // work slots inside the image
+    uint32_t* d_frozen_at = nullptr;  // per slot: pt::kSlotActive, or the count the pixel was frozen at (0 outside the image)
+    uint32_t* d_list = nullptr;       // the active slots, ascending (slots() entries)
+    uint32_t* d_scan = nullptr;       // the compaction's block totals
+    bool any_frozen = false;          // a pixel was frozen: passes run over the list from now on
+    bool list_valid = false;
+    uint32_t nactive = 0;             // entries of d_list (list_valid)
     size_t slots() const { return slot_pix.size(); }
 };
 
 pt::AccumView pt::accum_view(pt_accum* a)
 {
-    return pt::AccumView{a->ctx, &a->params, a->d_mean, &a->slot_pix, a->samples, &a->noise};
+    return pt::AccumView{a->ctx, &a->params, a->d_mean, &a->slot_pix, a->samples, &a->noise,
+                         a->any_frozen ? a->d_frozen_at : nullptr, a->pixels};
+}
+
+namespace {
+
+// The adaptive planes, allocated on first use: every pixel active, slots outside the image frozen at 0.
+int adaptive_alloc(pt_accum* a)
+{
+    if (a->d_frozen_at) return PT_OK;
+    const size_t n = a->slots() ? a->slots() : 1;
+    std::vector<uint32_t> init(n, 0u);
+    for (size_t q = 0; q < a->slots(); ++q)
+        if (a->slot_pix[q] != 0xffffffffu) init[q] = pt::kSlotActive;
+    ACC_HIP(hipSetDevice(pt::ctx_device(a->ctx)));
+    ACC_HIP(hipMalloc(reinterpret_cast<void**>(&a->d_frozen_at), n * sizeof(uint32_t)));
+    ACC_HIP(hipMalloc(reinterpret_cast<void**>(&a->d_list), n * sizeof(uint32_t)));
+    ACC_HIP(hipMalloc(reinterpret_cast<void**>(&a->d_scan), pt::adaptive_scan_words(n) * sizeof(uint32_t)));
+    ACC_HIP(hipMemcpy(a->d_frozen_at, init.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    a->list_valid = false;
+    return PT_OK;
+}
+
+// The active list of the frozen set as it stands (rebuilt only after a freeze).
+int active_list(pt_accum* a, void* stream)
+{
+    if (int rc = adaptive_alloc(a)) return rc;
+    if (a->list_valid) return PT_OK;
+    ACC_HIP(hipSetDevice(pt::ctx_device(a->ctx)));
+    if (int rc = pt::adaptive_compact(a->d_frozen_at, a->slots(), a->d_list, a->d_scan, stream, &a->nactive)) return rc;
+    a->list_valid = true;
+    return PT_OK;
+}
+
+// Every slot's sample count (0 outside the image).
+int fetch_counts(pt_accum* a, std::vector<uint32_t>* cnt)
+{
+    const size_t n = a->slots();
+    cnt->assign(n, 0u);
+    if (a->d_frozen_at && n) {
+        ACC_HIP(hipSetDevice(pt::ctx_device(a->ctx)));
+        ACC_HIP(hipMemcpy(cnt->data(), a->d_frozen_at, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    for (size_t q = 0; q < n; ++q) {
+        if (a->slot_pix[q] == 0xffffffffu) (*cnt)[q] = 0u;
+        else if (!a->d_frozen_at || (*cnt)[q] == pt::kSlotActive) (*cnt)[q] = (uint32_t)a->samples;
+    }
+    return PT_OK;
+}
+
+// The index of scanline pixel `pix` in the accumulator's pixel order.
+size_t order_index(const pt_accum* a, uint32_t pix)
+{
+    const uint32_t w = (uint32_t)a->params.width;
+    return a->params.pixel_order == PT_ORDER_MORTON ? (size_t)pt_morton_pxl_to_i(pix % w, pix / w) : (size_t)pix;
+}
+
+}  // namespace
+
+int pt::accum_freeze_plane(pt_accum* a, uint32_t** plane)
+{
+    if (int rc = adaptive_alloc(a)) return rc;
+    *plane = a->d_frozen_at;
+    return PT_OK;
+}
+
+void pt::accum_frozen(pt_accum* a, uint64_t newly_frozen)
+{
+    if (!newly_frozen) return;
+    a->any_frozen = true;
+    a->list_valid = false;
 }
 
 namespace {
@@ -122,6 +203,7 @@ pt_accum* make_accum(pt_ctx* c, const pt_params* p, const pt_camera* cam, int* c
     a->params.tile_w = p->tile_w; a->params.tile_h = p->tile_h;
     a->cam = *cam;
     pt::shard_slots(&a->params, &a->slot_pix);
+    for (const uint32_t pix : a->slot_pix) a->pixels += pix != 0xffffffffu;
     auto alloc = [&]() -> int {
         ACC_HIP(hipSetDevice(pt::ctx_device(c)));
         const size_t n = a->slots() ? a->slots() : 1;
@@ -195,7 +277,16 @@ int pt_accum_add(pt_accum* acc, int32_t spp, float* d_out, void* stream, pt_stat
     }
     pt_params p = acc->params;
     p.spp = spp;
-    const pt::AccumPass pass{(uint32_t)acc->samples, acc->d_rng, acc->d_mean};
+    pt::AccumPass pass{(uint32_t)acc->samples, acc->d_rng, acc->d_mean};
+    if (acc->any_frozen) {   // an adaptive pass: the active pixels only
+        if (int rc = active_list(acc, stream)) return rc;
+        if (acc->nactive == 0) {   // every pixel frozen: nothing to sample, the count stays
+            if (stats) memset(stats, 0, sizeof(*stats));
+            return PT_OK;
+        }
+        pass.active = acc->d_list;
+        pass.nactive = acc->nactive;
+    }
     if (int rc = pt::accum_pass(acc->ctx, &p, &acc->cam, pass, d_out, stream, stats)) return rc;
     acc->samples += spp;
     return PT_OK;
@@ -230,6 +321,108 @@ int pt_accum_add_until(pt_accum* acc, pt_noise* noise, const pt_converge_params*
     return PT_OK;
 }
 
+int pt_accum_freeze(pt_accum* acc, const uint8_t* mask)
+{
+    pt::clear_error();
+    if (!acc || !mask) return pt::fail(PT_E_INVALID, "pt_accum_freeze: null argument");
+    if (pt::ctx_in_flight(acc->ctx) > 0)
+        return pt::fail(PT_E_INVALID, "pt_accum_freeze: %d asynchronous renders in flight (pt_render_wait first)",
+                        pt::ctx_in_flight(acc->ctx));
+    const size_t n = acc->slots();
+    bool any = false;
+    for (size_t q = 0; q < n && !any; ++q)
+        any = acc->slot_pix[q] != 0xffffffffu && mask[order_index(acc, acc->slot_pix[q])] != 0;
+    if (!any) return PT_OK;   // (nothing of this shard named: the accumulator stays as it is)
+    if (int rc = adaptive_alloc(acc)) return rc;
+    std::vector<uint32_t> at(n);
+    ACC_HIP(hipSetDevice(pt::ctx_device(acc->ctx)));
+    ACC_HIP(hipMemcpy(at.data(), acc->d_frozen_at, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    uint64_t newly = 0;
+    for (size_t q = 0; q < n; ++q) {
+        if (acc->slot_pix[q] == 0xffffffffu || at[q] != pt::kSlotActive || !mask[order_index(acc, acc->slot_pix[q])]) continue;
+        at[q] = (uint32_t)acc->samples;
+        ++newly;
+    }
+    if (!newly) return PT_OK;
+    ACC_HIP(hipMemcpy(acc->d_frozen_at, at.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    pt::accum_frozen(acc, newly);
+    return PT_OK;
+}
+
+int pt_accum_counts(pt_accum* acc, uint32_t* out)
+{
+    pt::clear_error();
+    if (!acc || !out) return pt::fail(PT_E_INVALID, "pt_accum_counts: null argument");
+    std::vector<uint32_t> cnt;
+    if (int rc = fetch_counts(acc, &cnt)) return rc;
+    memset(out, 0, (size_t)acc->params.width * (size_t)acc->params.height * sizeof(uint32_t));
+    for (size_t q = 0; q < acc->slots(); ++q)
+        if (acc->slot_pix[q] != 0xffffffffu) out[order_index(acc, acc->slot_pix[q])] = cnt[q];
+    return PT_OK;
+}
+
+int pt_accum_active(pt_accum* acc, uint32_t* out, uint32_t cap, uint64_t* n_out)
+{
+    pt::clear_error();
+    if (!acc || !n_out) return pt::fail(PT_E_INVALID, "pt_accum_active: null argument");
+    if (pt::ctx_in_flight(acc->ctx) > 0)
+        return pt::fail(PT_E_INVALID, "pt_accum_active: %d asynchronous renders in flight (pt_render_wait first)",
+                        pt::ctx_in_flight(acc->ctx));
+    if (int rc = active_list(acc, nullptr)) return rc;
+    *n_out = acc->nactive;
+    if (!out) return PT_OK;
+    if (cap < acc->nactive) return pt::fail(PT_E_INVALID, "pt_accum_active: buffer of %u entries too small for %u", cap, acc->nactive);
+    std::vector<uint32_t> list(acc->nactive);
+    if (acc->nactive) ACC_HIP(hipMemcpy(list.data(), acc->d_list, list.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t u = 0; u < list.size(); ++u) {
+        if (list[u] >= acc->slots()) return pt::fail(PT_E_HIP, "pt_accum_active: the device list names slot %u of %zu", list[u], acc->slots());
+        out[u] = acc->slot_pix[list[u]];
+    }
+    return PT_OK;
+}
+
+int pt_accum_add_adaptive(pt_accum* acc, pt_noise* noise, const pt_converge_params* cp, float* d_out, void* stream,
+                          pt_adaptive_result* result)
+{
+    pt::clear_error();
+    if (!acc || !noise || !cp || !result) return pt::fail(PT_E_INVALID, "pt_accum_add_adaptive: null argument");
+    if (acc->noise != noise) return pt::fail(PT_E_INVALID, "pt_accum_add_adaptive: the estimator belongs to another accumulator");
+    if (cp->pass_spp < 1) return pt::fail(PT_E_INVALID, "pt_accum_add_adaptive: pass_spp %d < 1", cp->pass_spp);
+    if (!(cp->quantile > 0.0f && cp->quantile <= 1.0f)) return pt::fail(PT_E_INVALID, "pt_accum_add_adaptive: quantile must be in (0, 1]");
+    if (cp->min_batches < 2) return pt::fail(PT_E_INVALID, "pt_accum_add_adaptive: min_batches %d < 2", cp->min_batches);
+    if (cp->max_samples < 0 || (int64_t)cp->max_samples > (int64_t)pt::accum_max_samples())
+        return pt::fail(PT_E_INVALID, "pt_accum_add_adaptive: max_samples %d outside 0..%u", cp->max_samples, pt::accum_max_samples());
+    memset(result, 0, sizeof(*result));
+    uint64_t active = acc->pixels;
+    if (acc->any_frozen) {
+        if (int rc = active_list(acc, stream)) return rc;
+        active = acc->nactive;
+    }
+    while (acc->samples < (int64_t)cp->max_samples && active > 0) {
+        const int64_t left = (int64_t)cp->max_samples - acc->samples;
+        if (int rc = pt_accum_add(acc, left < cp->pass_spp ? (int32_t)left : cp->pass_spp, d_out, stream, nullptr)) return rc;
+        if (int rc = pt_noise_update(noise, &cp->noise, stream, &result->last)) return rc;
+        ++result->passes;
+        const pt_noise_summary& s = result->last;
+        if (s.batches < cp->min_batches) continue;
+        uint64_t newly = 0;
+        if (int rc = pt_noise_freeze(noise, &cp->noise, stream, &newly, &active)) return rc;
+        if (active == 0 || s.converged >= (uint64_t)ceil((double)cp->quantile * (double)s.pixels)) {
+            result->stopped_converged = 1;
+            break;
+        }
+    }
+    if (result->passes == 0) {
+        if (int rc = pt_noise_update(noise, &cp->noise, stream, &result->last)) return rc;
+        if (active == 0) result->stopped_converged = 1;
+    }
+    std::vector<uint32_t> cnt;
+    if (int rc = fetch_counts(acc, &cnt)) return rc;
+    result->active = active;
+    for (const uint32_t c : cnt) result->samples_total += c;
+    return PT_OK;
+}
+
 int pt_accum_read(pt_accum* acc, float* out_rgb, double* out_mean)
 {
     pt::clear_error();
@@ -254,6 +447,14 @@ int pt_accum_save(pt_accum* acc, const char* path)
     pt::clear_error();
     if (!acc || !path) return pt::fail(PT_E_INVALID, "pt_accum_save: null argument");
     if (!little_endian()) return pt::fail(PT_E_INVALID, "pt_accum_save: checkpoint files are little-endian; this host is not");
+    if (acc->any_frozen) {
+        std::vector<uint32_t> cnt;
+        if (int rc = fetch_counts(acc, &cnt)) return rc;
+        for (size_t q = 0; q < cnt.size(); ++q)
+            if (acc->slot_pix[q] != 0xffffffffu && (int64_t)cnt[q] != acc->samples)
+                return pt::fail(PT_E_INVALID, "pt_accum_save: the pixels' sample counts differ (frozen pixels stopped before %lld); "
+                                "checkpoint format version 1 holds a single sample count", (long long)acc->samples);
+    }
     std::vector<Record> rec;
     if (int rc = fetch_records(acc, &rec)) return rc;
     Header h;
@@ -334,6 +535,9 @@ void pt_accum_destroy(pt_accum* acc)
     (void)hipSetDevice(pt::ctx_device(acc->ctx));
     if (acc->d_rng) (void)hipFree(acc->d_rng);
     if (acc->d_mean) (void)hipFree(acc->d_mean);
+    if (acc->d_frozen_at) (void)hipFree(acc->d_frozen_at);
+    if (acc->d_list) (void)hipFree(acc->d_list);
+    if (acc->d_scan) (void)hipFree(acc->d_scan);
     delete acc;
 }
 

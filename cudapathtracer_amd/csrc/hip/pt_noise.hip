@@ -11,6 +11,12 @@
 //                        with one global atomic per non-zero bin into one of kSumCopies copies of a small
 //                        buffer, which the host adds up.  All integer: no reduction-order effects.
 //   noise_map            rel2 of every slot scattered to its pixel's index (scanline or Morton).
+// Adaptive sampling (the accumulator has frozen pixels: AccumView::frozen_at): the pixels' counts differ, so each
+// slot carries its own window weight and batch count (two u32 planes, allocated then: kPix instances of the two
+// kernels; an accumulator with no frozen pixel runs the scalar instances, unchanged), and
+//   noise_freeze         one sweep: rel2 from the planes, the test, the frozen_at store, and the counts of the
+//                        newly frozen and the still active pixels (per wave ballot + popcount, per block through
+//                        LDS, flushed into kSumCopies copies like the summary).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -52,6 +58,11 @@ struct NoiseArgs {
     double vden;            // (batches - 1) * W after the fold
     double y_floor, tol2;
     int32_t batches;        // after the fold
+    // per-pixel counts (kPix): the accumulator's frozen_at plane and this estimator's W_q / b_q planes
+    uint32_t* frozen_at;
+    uint32_t* pw;           // W_q
+    uint32_t* pb;           // b_q
+    uint32_t n_now;         // noise_freeze: the active pixels' sample count
 };
 
 // rel2 of a pixel with window mean mu and weighted square sum m2 (the header's "error")
@@ -59,6 +70,14 @@ __device__ __forceinline__ double noise_rel2(const NoiseArgs& a, double mu, doub
 {
     if (a.batches < 2) return __longlong_as_double(0x7ff0000000000000ll);
     const double var = m2 / a.vden;
+    const double den = (mu > a.y_floor) ? mu : a.y_floor;
+    return var / (den * den);
+}
+// ... with the pixel's own batch count and window weight
+__device__ __forceinline__ double noise_rel2_pix(const NoiseArgs& a, double mu, double m2, uint32_t b, uint32_t w)
+{
+    if (b < 2u) return __longlong_as_double(0x7ff0000000000000ll);
+    const double var = m2 / ((double)(b - 1u) * (double)w);
     const double den = (mu > a.y_floor) ? mu : a.y_floor;
     return var / (den * den);
 }
@@ -73,7 +92,7 @@ __device__ __forceinline__ int noise_bin(float r)
     return b < 1 ? 1 : (b > 62 ? 62 : b);
 }
 
-template <bool kFold>
+template <bool kFold, bool kPix = false>
 __global__ __launch_bounds__(kBlock) void noise_update(NoiseArgs a)
 {
     __shared__ uint32_t hist[64];
@@ -86,6 +105,41 @@ __global__ __launch_bounds__(kBlock) void noise_update(NoiseArgs a)
     for (size_t q = (size_t)blockIdx.x * kBlock + threadIdx.x; q < n; q += (size_t)gridDim.x * kBlock) {
         const bool pixel = a.dst[q] != kNoPixel;
         double mu = a.state[3 * n + q], m2 = a.state[4 * n + q];
+        if (kPix) {
+            // the pixel's count n_q: where it was frozen, or the active pixels' n1; it folds iff n_q > n0, with
+            // its own s = n_q - n0 and window weight (an active pixel: the scalar arithmetic, bit for bit)
+            uint32_t w = a.pw[q], nb = a.pb[q];
+            if (kFold) {
+                const uint32_t at = a.frozen_at[q];
+                const double nq = (at == pt::kSlotActive) ? a.n1 : (double)at;
+                if (nq > a.n0) {
+                    const double s = nq - a.n0;
+                    double b[3];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        const double m1 = a.mean[k * n + q];
+                        const double prev = a.state[k * n + q];
+                        b[k] = (m1 * nq - prev * a.n0) / s;
+                        a.state[k * n + q] = m1;
+                    }
+                    const double y = (0.2126 * b[0] + 0.7152 * b[1]) + 0.0722 * b[2];
+                    const double Wn = (double)w + s;
+                    const double d = y - mu;
+                    mu = mu + d * (s / Wn);
+                    m2 = m2 + (s * d) * (y - mu);
+                    a.state[3 * n + q] = mu;
+                    a.state[4 * n + q] = m2;
+                    w += (uint32_t)s;
+                    nb += 1u;
+                    a.pw[q] = w;
+                    a.pb[q] = nb;
+                }
+            }
+            const double rel2 = noise_rel2_pix(a, mu, m2, nb, w);
+            wave_conv += (uint32_t)__popcll(__ballot(pixel && rel2 <= a.tol2));
+            if (pixel) atomicAdd(&hist[noise_bin((float)rel2)], 1u);
+            continue;
+        }
         if (kFold) {
             double b[3];
 #pragma unroll
@@ -116,14 +170,52 @@ __global__ __launch_bounds__(kBlock) void noise_update(NoiseArgs a)
     }
 }
 
+template <bool kPix>
 __global__ __launch_bounds__(kBlock) void noise_map(NoiseArgs a)
 {
     const size_t n = a.n;
     for (size_t q = (size_t)blockIdx.x * kBlock + threadIdx.x; q < n; q += (size_t)gridDim.x * kBlock) {
         const uint32_t o = a.dst[q];
         if (o == kNoPixel) continue;
-        a.map[o] = (float)noise_rel2(a, a.state[3 * n + q], a.state[4 * n + q]);
+        const double mu = a.state[3 * n + q], m2 = a.state[4 * n + q];
+        a.map[o] = (float)(kPix ? noise_rel2_pix(a, mu, m2, a.pb[q], a.pw[q]) : noise_rel2(a, mu, m2));
     }
+}
+
+// Every slot's W_q / b_q from the scalars: until the first freeze all pixels fold in step.
+__global__ __launch_bounds__(kBlock) void noise_fill_pix(NoiseArgs a, uint32_t w, uint32_t b)
+{
+    const size_t n = a.n;
+    for (size_t q = (size_t)blockIdx.x * kBlock + threadIdx.x; q < n; q += (size_t)gridDim.x * kBlock) {
+        a.pw[q] = w;
+        a.pb[q] = b;
+    }
+}
+
+// pt_noise_freeze: every active pixel with rel2 <= tol2 is frozen at the active pixels' count.  sum[0]: newly
+// frozen, sum[1]: still active, in copy blockIdx.x % kSumCopies.
+__global__ __launch_bounds__(kBlock) void noise_freeze(NoiseArgs a)
+{
+    __shared__ uint32_t cnt[2];
+    if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const size_t n = a.n;
+    uint32_t wave_new = 0, wave_act = 0;   // (wave-uniform)
+    for (size_t q = (size_t)blockIdx.x * kBlock + threadIdx.x; q < n; q += (size_t)gridDim.x * kBlock) {
+        const bool active = a.dst[q] != kNoPixel && a.frozen_at[q] == pt::kSlotActive;
+        const double rel2 = noise_rel2_pix(a, a.state[3 * n + q], a.state[4 * n + q], a.pb[q], a.pw[q]);
+        const bool freeze = active && rel2 <= a.tol2;
+        if (freeze) a.frozen_at[q] = a.n_now;
+        wave_new += (uint32_t)__popcll(__ballot(freeze));
+        wave_act += (uint32_t)__popcll(__ballot(active && !freeze));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (wave_new) atomicAdd(&cnt[0], wave_new);
+        if (wave_act) atomicAdd(&cnt[1], wave_act);
+    }
+    __syncthreads();
+    unsigned long long* const sum = a.sum + (blockIdx.x % kSumCopies) * kSumWords;
+    if (threadIdx.x < 2 && cnt[threadIdx.x]) atomicAdd(&sum[threadIdx.x], (unsigned long long)cnt[threadIdx.x]);
 }
 
 bool params_ok(const pt_noise_params* np)
@@ -141,6 +233,8 @@ struct pt_noise {
     uint32_t* d_dst = nullptr;
     double* d_state = nullptr;          // 5 planes of slots() doubles
     unsigned long long* d_sum = nullptr;
+    uint32_t* d_pix = nullptr;          // W_q and b_q planes (2 x slots()), once the accumulator has frozen pixels
+    bool pix_live = false;              // the planes carry the state (else the scalars W and batches do)
     int64_t n0 = 0;                     // samples at the last fold (at first: n_start)
     double W = 0.0;                     // window weight: samples folded
     int32_t batches = 0;
@@ -182,7 +276,35 @@ NoiseArgs args_of(const pt_noise* z, const pt_noise_params* np)
     a.vden = (double)(z->batches - 1) * z->W;
     a.y_floor = (double)np->y_floor;
     a.tol2 = (double)np->tol * (double)np->tol;
+    a.frozen_at = const_cast<uint32_t*>(pt::accum_view(z->acc).frozen_at);
+    a.pw = z->d_pix;
+    a.pb = z->d_pix ? z->d_pix + z->slots() : nullptr;
     return a;
+}
+
+// Per-pixel counts from now on (the accumulator has frozen pixels, or pt_noise_freeze is about to freeze some):
+// the W_q / b_q planes, filled from the scalars that described every pixel until now.
+int go_per_pixel(pt_noise* z, hipStream_t stream)
+{
+    if (z->pix_live) return PT_OK;
+    const size_t n = z->slots() ? z->slots() : 1;
+    if (!z->d_pix) NS_HIP(hipMalloc(reinterpret_cast<void**>(&z->d_pix), 2 * n * sizeof(uint32_t)));
+    if (z->slots()) {
+        NoiseArgs a;
+        memset(&a, 0, sizeof(a));
+        a.n = z->slots();
+        a.pw = z->d_pix;
+        a.pb = z->d_pix + z->slots();
+        hipLaunchKernelGGL(noise_fill_pix, dim3(grid_of(z)), dim3(kBlock), 0, stream, a, (uint32_t)z->W, (uint32_t)z->batches);
+        NS_HIP(hipGetLastError());
+    }
+    z->pix_live = true;
+    return PT_OK;
+}
+// ... as soon as the accumulator has a frozen pixel (every entry point asks first)
+int follow_accum(pt_noise* z, hipStream_t stream)
+{
+    return pt::accum_view(z->acc).frozen_at ? go_per_pixel(z, stream) : PT_OK;
 }
 
 }  // namespace
@@ -250,6 +372,7 @@ int pt_noise_update(pt_noise* z, const pt_noise_params* np, void* stream_v, pt_n
     const int64_t n1 = pt::accum_view(z->acc).samples;
     const bool fold = n1 > z->n0;
     NS_HIP(hipSetDevice(pt::ctx_device(z->ctx)));
+    if (int rc = follow_accum(z, stream)) return rc;
     NoiseArgs a = args_of(z, np);
     if (fold) {
         const double s = (double)(n1 - z->n0), Wn = z->W + s;
@@ -262,7 +385,11 @@ int pt_noise_update(pt_noise* z, const pt_noise_params* np, void* stream_v, pt_n
     memset(part, 0, sizeof(part));
     if (z->slots()) {
         NS_HIP(hipMemsetAsync(z->d_sum, 0, sizeof(part), stream));
-        if (fold) hipLaunchKernelGGL((noise_update<true>), dim3(grid_of(z)), dim3(kBlock), 0, stream, a);
+        if (z->pix_live) {
+            if (fold) hipLaunchKernelGGL((noise_update<true, true>), dim3(grid_of(z)), dim3(kBlock), 0, stream, a);
+            else hipLaunchKernelGGL((noise_update<false, true>), dim3(grid_of(z)), dim3(kBlock), 0, stream, a);
+        }
+        else if (fold) hipLaunchKernelGGL((noise_update<true>), dim3(grid_of(z)), dim3(kBlock), 0, stream, a);
         else hipLaunchKernelGGL((noise_update<false>), dim3(grid_of(z)), dim3(kBlock), 0, stream, a);
         NS_HIP(hipGetLastError());
         NS_HIP(hipMemcpyAsync(part, z->d_sum, sizeof(part), hipMemcpyDeviceToHost, stream));
@@ -293,9 +420,11 @@ int pt_noise_map_device(pt_noise* z, const pt_noise_params* np, float* d_rel2, v
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
     NS_HIP(hipSetDevice(pt::ctx_device(z->ctx)));
     if (!z->slots()) return PT_OK;
+    if (int rc = follow_accum(z, stream)) return rc;
     NoiseArgs a = args_of(z, np);
     a.map = d_rel2;
-    hipLaunchKernelGGL(noise_map, dim3(grid_of(z)), dim3(kBlock), 0, stream, a);
+    if (z->pix_live) hipLaunchKernelGGL(noise_map<true>, dim3(grid_of(z)), dim3(kBlock), 0, stream, a);
+    else hipLaunchKernelGGL(noise_map<false>, dim3(grid_of(z)), dim3(kBlock), 0, stream, a);
     NS_HIP(hipGetLastError());
     NS_HIP(hipStreamSynchronize(stream));
     return PT_OK;
@@ -320,6 +449,40 @@ int pt_noise_map(pt_noise* z, const pt_noise_params* np, float* rel2)
     const int rc = run();
     if (d) (void)hipFree(d);
     return rc;
+}
+
+int pt_noise_freeze(pt_noise* z, const pt_noise_params* np, void* stream_v, uint64_t* newly_frozen, uint64_t* active)
+{
+    pt::clear_error();
+    if (!newly_frozen || !active) return pt::fail(PT_E_INVALID, "pt_noise_freeze: null argument");
+    if (int rc = check("pt_noise_freeze", z, np)) return rc;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+    NS_HIP(hipSetDevice(pt::ctx_device(z->ctx)));
+    const pt::AccumView v = pt::accum_view(z->acc);
+    *newly_frozen = 0;
+    *active = 0;
+    if (!z->slots()) return PT_OK;
+    uint32_t* plane = nullptr;
+    if (int rc = pt::accum_freeze_plane(z->acc, &plane)) return rc;
+    if (int rc = go_per_pixel(z, stream)) return rc;
+    NoiseArgs a = args_of(z, np);
+    a.frozen_at = plane;
+    a.n_now = (uint32_t)v.samples;
+    unsigned long long part[kSumCopies * kSumWords];
+    NS_HIP(hipMemsetAsync(z->d_sum, 0, sizeof(part), stream));
+    hipLaunchKernelGGL(noise_freeze, dim3(grid_of(z)), dim3(kBlock), 0, stream, a);
+    NS_HIP(hipGetLastError());
+    NS_HIP(hipMemcpyAsync(part, z->d_sum, sizeof(part), hipMemcpyDeviceToHost, stream));
+    NS_HIP(hipStreamSynchronize(stream));
+    for (int c = 0; c < kSumCopies; ++c) {
+        *newly_frozen += part[c * kSumWords];
+        *active += part[c * kSumWords + 1];
+    }
+    pt::accum_frozen(z->acc, *newly_frozen);
+    // (nothing frozen on an accumulator without frozen pixels: it stays on the scalar path, and the planes are
+    // filled again when they are next needed)
+    if (!pt::accum_view(z->acc).frozen_at) z->pix_live = false;
+    return PT_OK;
 }
 
 int pt_noise_read(pt_noise* z, double* mu, double* m2)
@@ -349,6 +512,7 @@ void pt_noise_destroy(pt_noise* z)
     if (z->d_dst) (void)hipFree(z->d_dst);
     if (z->d_state) (void)hipFree(z->d_state);
     if (z->d_sum) (void)hipFree(z->d_sum);
+    if (z->d_pix) (void)hipFree(z->d_pix);
     pt_noise** slot = pt::accum_view(z->acc).noise;
     if (*slot == z) *slot = nullptr;
     delete z;

@@ -782,6 +782,46 @@ __device__ __forceinline__ void replay_sample(Rng& rng, bool lens, int D)
     }
 }
 
+// The XORWOW state pixel slot q (Morton index idx) starts a render or a pass from: curand_init, or after
+// n_done samples of an accumulator the stream its last sample left (init_pixel_states, init_active_states).
+__device__ __forceinline__ void slot_stream(const Args& a, uint32_t q, uint32_t idx, uint32_t n_done, Rng& r)
+{
+    if (n_done != 0u) {
+        // a later pass of an accumulator: the stream continues where the pixel's last sample left it
+        const size_t P = a.npix;
+        r.v0 = a.acc_rng[q]; r.v1 = a.acc_rng[P + q]; r.v2 = a.acc_rng[2 * P + q];
+        r.v3 = a.acc_rng[3 * P + q]; r.v4 = a.acc_rng[4 * P + q]; r.d = a.acc_rng[5 * P + q];
+    } else if (a.jump_bytes) {
+        // curand_init(seed, idx, 0) = J(idx) v(seed): the jump matrices are powers of one matrix,
+        // so they commute and J(idx) = J(idx & 0xff0000) J(idx & 0xff00) J(idx & 0xff) -- the low
+        // byte's product is tabulated per render (seed_states), the next two bytes' per context
+        // (jump_bytes): 40 lookups instead of 20 per set bit of idx
+        uint32_t v[5];
+        const uint32_t* p0 = a.seed_states + (size_t)(idx & 255u) * kJumpEntryWords;
+        for (int k = 0; k < 5; ++k) v[k] = p0[k];
+        const uint32_t b1 = (idx >> 8) & 255u, b2 = (idx >> 16) & 255u;
+        constexpr size_t kMat = (size_t)20 * 256 * kJumpEntryWords;
+        if (b1) jump_apply(v, a.jump_bytes + (size_t)b1 * kMat);
+        if (b2) jump_apply(v, a.jump_bytes + (size_t)(256u + b2) * kMat);
+        for (int k = 24; k < 32; ++k)   // (images beyond 4096 x 4096: the remaining bits one by one)
+            if ((idx >> k) & 1u) jump_apply(v, a.jump + (size_t)k * kMat);
+        r.d = rng_seed_d(a.seed);
+        r.v0 = v[0]; r.v1 = v[1]; r.v2 = v[2]; r.v3 = v[3]; r.v4 = v[4];
+    } else {
+        rng_init(r, a.seed, idx, a.jump);
+    }
+}
+
+// This render's counters, unit counters and wall-clock minima, by the first block of the unit set-up kernel
+// (no memset launches).
+__device__ __forceinline__ void reset_render_counters(const Args& a)
+{
+    for (uint32_t k = threadIdx.x; k < (uint32_t)kCounterWords; k += 256u)
+        a.counters[k] = (k == CNT_T_START || k == CNT_T_DRAINED) ? ~0ull : 0ull;
+    for (uint32_t k = threadIdx.x; k < kQueueStride * (kQueues + 1); k += 256u) a.pixel_counter[k] = 0u;
+    if (threadIdx.x < 4) a.tile_counter[threadIdx.x] = 0u;
+}
+
 // setupCurand (kernel.cu:527-533) for the wavefront kernel: the XORWOW state of every work unit
 // of this shard -- curand_init of its pixel, fast-forwarded over the unit's earlier samples --
 // computed in parallel before the render, so that a lane starting a unit inside the state
@@ -792,12 +832,7 @@ __global__ __launch_bounds__(256) void init_pixel_states(Args a, uint32_t* __res
     // at the start of every chunk, with everything else a lane needs to start the unit (pixel,
     // sample range, pinhole camera ray): the refill in the render kernel is then a few loads
     const uint32_t q = blockIdx.x * 256u + threadIdx.x;
-    if (blockIdx.x == 0) {   // this render's counters, unit counters and wall-clock minima (no memset launches)
-        for (uint32_t k = threadIdx.x; k < (uint32_t)kCounterWords; k += 256u)
-            a.counters[k] = (k == CNT_T_START || k == CNT_T_DRAINED) ? ~0ull : 0ull;
-        for (uint32_t k = threadIdx.x; k < kQueueStride * (kQueues + 1); k += 256u) a.pixel_counter[k] = 0u;
-        if (threadIdx.x < 4) a.tile_counter[threadIdx.x] = 0u;
-    }
+    if (blockIdx.x == 0) reset_render_counters(a);
     if (q >= a.npix) return;
     const bool split = q >= a.nwhole;
     const uint32_t t = q - a.nwhole;   // split slot (row of the per-sample buffer)
@@ -825,30 +860,7 @@ __global__ __launch_bounds__(256) void init_pixel_states(Args a, uint32_t* __res
     const uint32_t idx = morton2(px, py);
     Rng r;
     const uint32_t n_done = a.accum ? a.acc_n0 : 0u;   // samples the pixel has before this render
-    if (n_done != 0u) {
-        // a later pass of an accumulator: the stream continues where the pixel's last sample left it
-        const size_t P = a.npix;
-        r.v0 = a.acc_rng[q]; r.v1 = a.acc_rng[P + q]; r.v2 = a.acc_rng[2 * P + q];
-        r.v3 = a.acc_rng[3 * P + q]; r.v4 = a.acc_rng[4 * P + q]; r.d = a.acc_rng[5 * P + q];
-    } else if (a.jump_bytes) {
-        // curand_init(seed, idx, 0) = J(idx) v(seed): the jump matrices are powers of one matrix,
-        // so they commute and J(idx) = J(idx & 0xff0000) J(idx & 0xff00) J(idx & 0xff) -- the low
-        // byte's product is tabulated per render (seed_states), the next two bytes' per context
-        // (jump_bytes): 40 lookups instead of 20 per set bit of idx
-        uint32_t v[5];
-        const uint32_t* p0 = a.seed_states + (size_t)(idx & 255u) * kJumpEntryWords;
-        for (int k = 0; k < 5; ++k) v[k] = p0[k];
-        const uint32_t b1 = (idx >> 8) & 255u, b2 = (idx >> 16) & 255u;
-        constexpr size_t kMat = (size_t)20 * 256 * kJumpEntryWords;
-        if (b1) jump_apply(v, a.jump_bytes + (size_t)b1 * kMat);
-        if (b2) jump_apply(v, a.jump_bytes + (size_t)(256u + b2) * kMat);
-        for (int k = 24; k < 32; ++k)   // (images beyond 4096 x 4096: the remaining bits one by one)
-            if ((idx >> k) & 1u) jump_apply(v, a.jump + (size_t)k * kMat);
-        r.d = rng_seed_d(a.seed);
-        r.v0 = v[0]; r.v1 = v[1]; r.v2 = v[2]; r.v3 = v[3]; r.v4 = v[4];
-    } else {
-        rng_init(r, a.seed, idx, a.jump);
-    }
+    slot_stream(a, q, idx, n_done, r);
     const bool lens = (idx == 0) || (a.cam.radius != 0.0f);
     V3 o, d = v3(0.0f, 0.0f, 0.0f);
     if (!lens) camera_ray(a.cam, px, py, false, 0.0f, 0.0f, &o, &d);   // the pixel's pinhole ray
@@ -877,6 +889,43 @@ __global__ __launch_bounds__(256) void init_pixel_states(Args a, uint32_t* __res
         st[(UW_CD + 1) * N + u] = __float_as_uint(d.y);
         st[(UW_CD + 2) * N + u] = __float_as_uint(d.z);
     }
+}
+
+// The unit set-up of an adaptive pass (pt_accum_add once a pixel is frozen): one lane per entry u of the active
+// list, unit u = the whole pixel of slot q = list[u] -- the words init_pixel_states writes for a whole-pixel
+// accumulating unit, whose UW_TQ names the slot: the row (stride npix, the shard's slot count) the integration
+// kernels load the unit's mean from and store its mean and stream to.  nunits = nwhole = the list's length.
+__global__ __launch_bounds__(256) void init_active_states(Args a, uint32_t* __restrict__ st, const uint32_t* __restrict__ list)
+{
+    const uint32_t u = blockIdx.x * 256u + threadIdx.x;
+    if (blockIdx.x == 0) reset_render_counters(a);
+    const size_t N = a.nunits;
+    if (u >= a.nunits) return;
+    const uint32_t q = list[u];
+    uint32_t px, py;
+    if (q >= a.npix || !unit_pixel(a, q, &px, &py)) {   // (the list holds slots of the image only)
+        st[UW_PXY * N + u] = kNoPixel;
+        return;
+    }
+    const uint32_t idx = morton2(px, py);
+    Rng r;
+    slot_stream(a, q, idx, a.acc_n0, r);
+    const bool lens = (idx == 0) || (a.cam.radius != 0.0f);
+    V3 o, d = v3(0.0f, 0.0f, 0.0f);
+    if (!lens) camera_ray(a.cam, px, py, false, 0.0f, 0.0f, &o, &d);   // the pixel's pinhole ray
+    st[u] = r.v0;
+    st[N + u] = r.v1;
+    st[2 * N + u] = r.v2;
+    st[3 * N + u] = r.v3;
+    st[4 * N + u] = r.v4;
+    st[5 * N + u] = r.d;
+    st[UW_PXY * N + u] = px | (py << 16);
+    st[UW_N0 * N + u] = (a.acc_n0 + 1u) | (lens ? 0x80000000u : 0u) | kUnitFirst;
+    st[UW_NEND * N + u] = a.acc_n0 + (uint32_t)a.spp;
+    st[UW_TQ * N + u] = q;
+    st[UW_CD * N + u] = __float_as_uint(d.x);
+    st[(UW_CD + 1) * N + u] = __float_as_uint(d.y);
+    st[(UW_CD + 2) * N + u] = __float_as_uint(d.z);
 }
 
 // The per-render table of init_pixel_states: curand_init(seed, s0, 0) for the 256 low bytes s0.
@@ -2917,7 +2966,17 @@ static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, f
             *bytes = ((uint64_t)fr + (uint64_t)B.lbuf_words * sizeof(double)) / 4;
             return PT_OK;
         };
+        if (acc && acc->active) in.npix = acc->nactive;   // (the launch is sized by the units it has)
         if (int rc = pt::plan_units(in, K, lbuf_budget, &plan)) return rc;
+        if (acc && acc->active) {
+            // an adaptive pass: unit u = the whole pixel of slot active[u], no sample-chunk split (npix stays the
+            // shard's slot count: the stride of the accumulator's planes)
+            if (acc->nactive == 0 || acc->nactive > a.npix) return pt::fail(PT_E_INVALID, "pt_accum_add: active list of %u slots", acc->nactive);
+            plan.nwhole = plan.nunits = acc->nactive;
+            plan.ntail = plan.nmid = plan.nfin = 0;
+            plan.chunks = plan.chunks_mid = plan.chunks_fin = 1;
+            plan.blocks = std::min(plan.blocks, (acc->nactive + 255u) / 256u);
+        }
         const uint32_t blocks = plan.blocks, ntail = plan.ntail;
         const uint32_t paths_per_block = 256u;
         b.top_nodes = plan.top_nodes;
@@ -2988,7 +3047,10 @@ static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, f
             b.jump_bytes = c->jump_bytes;
             b.seed_states = B.seed_states;
         }
-        hipLaunchKernelGGL(init_pixel_states, dim3((b.npix + 255) / 256), dim3(256), 0, stream, b, B.pix_states);
+        if (acc && acc->active)
+            hipLaunchKernelGGL(init_active_states, dim3((b.nunits + 255) / 256), dim3(256), 0, stream, b, B.pix_states, acc->active);
+        else
+            hipLaunchKernelGGL(init_pixel_states, dim3((b.npix + 255) / 256), dim3(256), 0, stream, b, B.pix_states);
         // A render queued on another stream while one is in flight: its seeding pre-pass runs beside the
         // earlier render's last waves (its own buffers), but the integration kernel waits until the earlier
         // render is complete (finalisation included), so a persistent grid never takes the CU slots an

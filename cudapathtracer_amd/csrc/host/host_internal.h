@@ -37,14 +37,18 @@ inline uint64_t fnv1a(const void* p, size_t n, uint64_t h = kFnvBasis)
 // (pt_render.hip).  The state is device memory of the context's device, in the shard's work-slot order:
 // rng[k * slots + q] (k = v0..v4, d) and mean[k * slots + q] (k = r, g, b) of slot q.
 struct AccumPass {
-    uint32_t n0;      // samples every pixel has before this pass
+    uint32_t n0;      // samples every pixel (an adaptive pass: every active pixel) has before this pass
     uint32_t* rng;
     double* mean;
+    // an adaptive pass (pt_accum.cpp, once a pixel is frozen): only the work slots active[0..nactive-1] (device,
+    // ascending) are sampled, one whole-pixel unit each; null: every pixel of the shard, as planned by plan_units
+    const uint32_t* active = nullptr;
+    uint32_t nactive = 0;
 };
 // Validates (params, cam) as pt_render_device_async does and refuses every mode without an accumulating
 // kernel (render_tiles, the counting variants, non-default occupancy).
 int accum_check(const pt_ctx* c, const pt_params* p, const pt_camera* cam);
-// p->spp more samples of every pixel, blocking; d_out (device, W*H*3) may be null.
+// p->spp more samples of every pixel (of every active pixel), blocking; d_out (device, W*H*3) may be null.
 int accum_pass(pt_ctx* c, const pt_params* p, const pt_camera* cam, const AccumPass& acc, float* d_out, void* stream,
                pt_stats* stats);
 // Work slot q of the shard -> scanline pixel id y*W + x, or 0xffffffff for a slot outside the image.
@@ -63,8 +67,23 @@ struct AccumView {
     const std::vector<uint32_t>* slot_pix;   // work slot -> scanline pixel id, 0xffffffff outside the image
     int64_t samples;
     pt_noise** noise;
+    // adaptive sampling: null until the accumulator has a frozen pixel; then per work slot the sample count the
+    // pixel was frozen at, kSlotActive for a pixel still sampled (its count is `samples`), 0 outside the image
+    const uint32_t* frozen_at;               // device
+    uint64_t pixels;                         // work slots inside the image
 };
 AccumView accum_view(pt_accum* acc);
+constexpr uint32_t kSlotActive = 0xffffffffu;
+// The frozen_at plane for a device sweep that freezes pixels (pt_noise_freeze), allocated on first use; the sweep
+// reports how many pixels it froze with accum_frozen (which drops the accumulator's active list).
+int accum_freeze_plane(pt_accum* acc, uint32_t** plane);
+void accum_frozen(pt_accum* acc, uint64_t newly_frozen);
+// ---- the active list (pt_adaptive.hip): ordered compaction of the slots with frozen_at == kSlotActive into
+// list[0..*count-1] (ascending), on the device; block_tot: scratch of adaptive_scan_words(slots) words.
+// Blocking: only *count comes back.
+size_t adaptive_scan_words(size_t slots);
+int adaptive_compact(const uint32_t* frozen_at, size_t slots, uint32_t* list, uint32_t* block_tot, void* stream,
+                     uint32_t* count);
 
 // ---- the denoiser (pt_denoise.hip) keeps its device scratch in the render context (pt_render.hip), which
 // frees it in pt_destroy

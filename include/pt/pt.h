@@ -18,6 +18,8 @@
  *        pt_accum_*      <- the progressive loop's state between launches (kernel.cu:527-553, 702-737)
  *        pt_noise_* / pt_accum_add_until  (no counterpart in the reference) per-pixel noise estimates of an
  *                           accumulator from batch means, and a loop that adds passes until the image converged
+ *        pt_accum_freeze / pt_noise_freeze / pt_accum_add_adaptive  (no counterpart) adaptive sampling: converged
+ *                           pixels are frozen and the passes sample only the rest
  *        pt_render_features / pt_denoise  (no counterpart in the reference) per-pixel first-hit feature
  *                           buffers and an edge-avoiding a-trous filter: a preview from a few samples per pixel
  *        pt_destroy      <- cudaFree (kernel.cu:782-783)
@@ -384,6 +386,77 @@ typedef struct {
 } pt_converge_result;
 int pt_accum_add_until(pt_accum* acc, pt_noise* noise, const pt_converge_params* cp, float* d_out, void* stream,
                        pt_converge_result* result);
+
+/* ------------------------------------------------- adaptive sampling: freeze converged pixels
+ * pt_accum_add_until stops all or nothing; until then every pass samples every pixel.  A pixel of an
+ * accumulator can instead be FROZEN: it is never sampled again, and pt_accum_add renders the others only.
+ * Pixels are independent (each has its own XORWOW stream, seeded by its Morton index), so a pixel with n
+ * samples holds exactly the f64 mean a plain render has after n samples, in every bit, whatever was frozen
+ * around it and whenever.  Freezing is permanent (no unfreeze): every ACTIVE (not frozen) pixel therefore
+ * has exactly pt_accum_samples samples, which stays the largest count in the image, and a frozen pixel has
+ * the count it was frozen at.
+ * Stopping a pixel on its own estimated error biases the image slightly (a pixel whose samples happened to
+ * agree stops early), as with every adaptive sampler; nothing here corrects for it.
+ *
+ * pt_accum_freeze  mask: HOST buffer, W*H bytes in params->pixel_order; non-zero freezes the pixel at the
+ *                  current count, zero changes nothing (it never unfreezes); pixels outside the shard are
+ *                  ignored.  Legal at 0 samples: such a pixel stays at mean 0 with count 0.  Blocking.
+ * pt_accum_counts  out: HOST buffer, W*H uint32 in pixel_order: each pixel's sample count, 0 outside the shard.
+ * pt_accum_active  the active pixels' scanline ids y*W + x in work order: pt_shard_pixels' order with the
+ *                  frozen pixels removed.  out = NULL: only *n_out; cap < *n_out is PT_E_INVALID.  The list
+ *                  is the one the passes use, built on the device (an ordered compaction of the frozen
+ *                  flags, rebuilt only when the frozen set changed); this call reads it back.
+ * pt_accum_add     on an accumulator that never had a pixel frozen: unchanged, the same launches.  Once a
+ *                  pixel is frozen: spp more samples of the active pixels only, each one whole-pixel work
+ *                  unit; stats->samples = active * spp; d_out receives the active pixels' new means and
+ *                  frozen pixels keep what the buffer held.  With no active pixel: a no-op (zero stats,
+ *                  pt_accum_samples unchanged).
+ * pt_accum_read    unchanged: every pixel's mean, at its own count.
+ * pt_accum_save    with unequal counts PT_E_INVALID: format version 1 holds a single sample count.
+ *
+ * The estimator with per-pixel counts.  Once the accumulator has a frozen pixel, each pixel q carries its
+ * own window weight W_q and batch count b_q (two uint32 planes, allocated then, both starting from the
+ * scalar W and batches, which described every pixel until that moment).  With n_q the pixel's count (the
+ * count it was frozen at, or n1 = pt_accum_samples for an active pixel) and n0 the scalar count at the
+ * last fold, pt_noise_update at n1 > n0 folds pixel q iff n_q > n0:
+ *             s    = n_q - n0
+ *             b[k] = (m1[k]*n_q - prev[k]*n0) / s
+ *             y    = (0.2126*b[0] + 0.7152*b[1]) + 0.0722*b[2]
+ *             Wn   = W_q + s;   d = y - mu;   mu' = mu + d*(s/Wn);   m2' = m2 + (s*d)*(y - mu');   prev = m1
+ *           then W_q = Wn, b_q += 1; afterwards n0 = n1 and the scalars W, batches advance as before (they
+ *           remain the active pixels' values; the summary's `batches` is the scalar).
+ *   error   b_q >= 2:  var = m2 / ((b_q-1) * W_q);  den = max(y_floor, mu);  rel2 = var / (den*den);
+ *           b_q < 2:   rel2 = +inf.
+ * For an active pixel this is the arithmetic above bit for bit; a frozen pixel's state stops at its last
+ * fold (a pixel frozen between two passes that one update folds together folds once more, with its own
+ * shorter s).  Summary, histogram, map and pt_noise_read are as before, over all pixels of the shard.  An
+ * estimator of an accumulator without frozen pixels runs the scalar sweep, unchanged.
+ *
+ * pt_noise_freeze freezes every active pixel with rel2 <= (double)tol*(double)tol at the current count, in
+ * one sweep on the device (the error map never reaches the host); *newly_frozen and *active (the pixels
+ * still active afterwards) come back.  Blocking; PT_E_INVALID as for pt_noise_update.
+ *
+ * pt_accum_add_adaptive (argument checks as pt_accum_add_until): while pt_accum_samples < max_samples and
+ * a pixel is active it calls pt_accum_add(min(pass_spp, max_samples - samples)), pt_noise_update and, once
+ * batches >= min_batches, pt_noise_freeze; it stops with stopped_converged = 1 when (batches >=
+ * min_batches and) that update's converged >= (uint64_t)ceil((double)quantile * (double)pixels), or when
+ * no pixel is active; otherwise at max_samples with stopped_converged = 0.  `last` is the summary of the
+ * last update (taken before that pass's freeze), `active` the pixels still active, `samples_total` the sum
+ * of the per-pixel counts (what the loop and everything before it sampled in this shard).  With no pass to
+ * run: one update, as pt_accum_add_until. */
+typedef struct {
+    int32_t passes;             /* passes this call ran                              */
+    int32_t stopped_converged;  /* 1: the quantile converged or nothing is active    */
+    pt_noise_summary last;
+    uint64_t active;            /* pixels still sampled                              */
+    uint64_t samples_total;     /* sum of the per-pixel sample counts                */
+} pt_adaptive_result;
+int pt_accum_freeze(pt_accum* acc, const uint8_t* mask);
+int pt_accum_counts(pt_accum* acc, uint32_t* out);
+int pt_accum_active(pt_accum* acc, uint32_t* out, uint32_t cap, uint64_t* n_out);
+int pt_noise_freeze(pt_noise* noise, const pt_noise_params* np, void* stream, uint64_t* newly_frozen, uint64_t* active);
+int pt_accum_add_adaptive(pt_accum* acc, pt_noise* noise, const pt_converge_params* cp, float* d_out, void* stream,
+                          pt_adaptive_result* result);
 
 /* The reference's trace() (kernel.cu:112-161) for n rays given as rays[6n] = {o.xyz, d.xyz}
  * (host buffers): tri_out[i] = winning ORIGINAL triangle index or -1, t_out[i] = its closestT

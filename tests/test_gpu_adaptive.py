@@ -1,0 +1,471 @@
+"""Adaptive sampling on the GPU (pt_accum_freeze / _counts / _active, pt_noise_freeze, pt_accum_add_adaptive): a pixel
+with n samples holds exactly the oracle's f64 value after n samples, in every bit, whatever was frozen around it and
+whenever; the device's active list is the shard's work order with the frozen pixels removed; the estimator with
+per-pixel counts equals tests/adaptive_ref.py in every bit; and the loop equals both the spelled-out Python loop and
+the restatement's simulation on oracle images.  All comparisons are of bytes."""
+import numpy as np
+import pytest
+
+from conftest import load_scene
+
+import cudapathtracer_amd as pt
+from cudapathtracer_amd import shard
+
+import adaptive_ref
+import noise_ref
+from adaptive_ref import BOUNCES, LOOP, LOOP_SHAPES, SEED
+
+pytestmark = pytest.mark.gpu
+
+CAM = dict(pos=(0.0, 1.0, 3.0), dist_from_film=1.0, focal_length=3.0)
+SHAPES = [(24, 16), (20, 13)]            # 20x13: partial 8x8 blocks, slots outside the image
+TOLS = (0.05, 0.25, 1.0)
+
+
+def _cam(w, h, radius=0.0):
+    return pt.make_camera(width=w, height=h, radius=radius, **CAM)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).tobytes()
+
+
+@pytest.fixture(scope="module")
+def cb():
+    s = load_scene("cornell_blob")
+    with pt.Renderer(s, 0) as r:
+        yield s, r
+
+
+_ORACLE = {}
+
+
+def _oracle(key, scene, w, h, n, integ, radius=0.0, bounces=BOUNCES):
+    """The oracle's f64 image after n samples of every pixel, once per configuration."""
+    k = (key, w, h, n, integ, radius, bounces)
+    if k not in _ORACLE:
+        import oracle
+        if ("scene", key) not in _ORACLE:
+            _ORACLE[("scene", key)] = oracle.OracleScene(scene.arrays())
+        ocam = oracle.camera(CAM["pos"], 1.0, 3.0, radius, w, h)
+        _ORACLE[k] = oracle.render(_ORACLE[("scene", key)], ocam, w, h, n, bounces, integ, SEED)[0]
+    return _ORACLE[k]
+
+
+def _checker(w, h):
+    yy, xx = np.mgrid[0:h, 0:w]
+    return (xx + yy) % 2 == 0
+
+
+class Sched:
+    """An accumulator driven by adds and freezes, with the counts the schedule implies kept alongside."""
+
+    def __init__(self, acc, w, h, shard_index=0, shard_count=1):
+        self.acc, self.w, self.h = acc, w, h
+        self.order = shard.shard_pixels(w, h, shard_index, shard_count, 8, 8)
+        self.mine = np.zeros(w * h, dtype=bool)
+        self.mine[self.order] = True
+        self.mine = self.mine.reshape(h, w)
+        self.frozen = np.zeros((h, w), dtype=bool)
+        self.counts = np.zeros((h, w), dtype=np.uint32)
+
+    def add(self, k, **kw):
+        active = int((self.mine & ~self.frozen).sum())
+        before = self.acc.samples
+        st = self.acc.add(k, **kw)
+        assert st["samples"] == active * k
+        assert self.acc.samples == (before + k if active else before)
+        self.counts[self.mine & ~self.frozen] = self.acc.samples
+        return st
+
+    def freeze(self, mask):
+        self.acc.freeze(mask)
+        self.frozen |= np.asarray(mask, dtype=bool) & self.mine
+
+    def check_counts_and_list(self):
+        assert _bits(self.acc.counts()) == _bits(self.counts)
+        flat = self.frozen.reshape(-1)
+        want = self.order[~flat[self.order]].astype(np.uint32)
+        assert _bits(self.acc.active_pixels()) == _bits(want)
+
+    def check_image(self, render):
+        """render(n) -> the oracle's image after n samples: every pixel at its own count."""
+        want = adaptive_ref.compose(render, self.counts)
+        assert _bits(self.acc.mean64()) == _bits(want)
+        assert _bits(self.acc.image()) == _bits(want.astype(np.float32))
+
+
+# ---------------------------------------------------------------- 1. freeze schedules against the oracle
+@pytest.mark.parametrize("integ", [0, 1])
+@pytest.mark.parametrize("w,h", SHAPES)
+def test_schedule_against_the_oracle(cb, w, h, integ):
+    s, r = cb
+    with r.accumulator(_cam(w, h), w, h, bounces=BOUNCES, integrator=integ, seed=SEED) as acc:
+        sc = Sched(acc, w, h)
+        sc.add(2)
+        sc.freeze(_checker(w, h))
+        sc.check_counts_and_list()
+        sc.add(3)
+        left = np.zeros((h, w), dtype=bool)
+        left[:, : w // 2] = True
+        sc.freeze(left)                                   # (names frozen pixels again: they keep their count)
+        sc.check_counts_and_list()
+        sc.add(4)
+        sc.check_counts_and_list()
+        assert sorted(np.unique(sc.counts)) == [2, 5, 9] and acc.samples == 9
+        sc.check_image(lambda n: _oracle("cb", s, w, h, n, integ))
+
+
+@pytest.mark.parametrize("integ", [0, 1])
+def test_lens_camera(cb, integ):
+    s, r = cb
+    w, h = 24, 16
+    with r.accumulator(_cam(w, h, 0.05), w, h, bounces=BOUNCES, integrator=integ, seed=SEED) as acc:
+        sc = Sched(acc, w, h)
+        sc.add(2)
+        sc.freeze(_checker(w, h))
+        sc.add(3)
+        sc.check_counts_and_list()
+        sc.check_image(lambda n: _oracle("cb", s, w, h, n, integ, radius=0.05))
+
+
+@pytest.mark.parametrize("integ", [0, 1])
+def test_sphere_scene(integ):
+    s = load_scene("cornell")
+    s.add_sphere((0.3, 0.5, 0.2), 0.25, (0.7, 0.7, 0.7), (4.0, 3.0, 2.0))
+    w, h = 24, 16
+    with pt.Renderer(s, 0) as r, r.accumulator(_cam(w, h), w, h, bounces=BOUNCES, integrator=integ, seed=SEED) as acc:
+        sc = Sched(acc, w, h)
+        sc.add(2)
+        sc.freeze(~_checker(w, h))
+        sc.add(3)
+        sc.check_counts_and_list()
+        sc.check_image(lambda n: _oracle("cornell_sphere", s, w, h, n, integ))
+
+
+def test_morton_pixel_order(cb):
+    s, r = cb
+    w = h = 16
+    idx = np.array([[pt.morton_pxl_to_i(x, y) for x in range(w)] for y in range(h)])
+    mask = _checker(w, h)
+    mask[8:, 8:] = True
+    mmask = np.zeros(w * h, dtype=bool)
+    mmask[idx] = mask
+    with r.accumulator(_cam(w, h), w, h, bounces=BOUNCES, seed=SEED, pixel_order=pt.PT_ORDER_MORTON) as acc:
+        acc.add(2)
+        acc.freeze(mmask)
+        st = acc.add(3)
+        assert st["samples"] == int((~mask).sum()) * 3
+        counts = np.where(mask, 2, 5).astype(np.uint32)
+        assert _bits(acc.counts()[idx]) == _bits(counts)
+        order = shard.shard_pixels(w, h, 0, 1, 8, 8)
+        assert _bits(acc.active_pixels()) == _bits(order[~mask.reshape(-1)[order]].astype(np.uint32))
+        want = adaptive_ref.compose(lambda n: _oracle("cb", s, w, h, n, 0), counts)
+        assert _bits(acc.mean64()[idx]) == _bits(want)
+
+
+@pytest.mark.parametrize("integ", [0, 1])
+def test_shards_union_is_the_unsharded_run(cb, integ):
+    s, r = cb
+    w, h = 24, 16
+    mask = _checker(w, h)
+    total = np.zeros((h, w, 3), dtype=np.float64)
+    counts = np.zeros((h, w), dtype=np.uint32)
+    for i in range(2):
+        with r.accumulator(_cam(w, h), w, h, bounces=BOUNCES, integrator=integ, seed=SEED, shard_index=i, shard_count=2,
+                           tile=8) as acc:
+            sc = Sched(acc, w, h, i, 2)
+            sc.add(2)
+            sc.freeze(mask)                               # the whole image's mask: pixels of the other shard are ignored
+            sc.add(3)
+            sc.check_counts_and_list()
+            assert 0 < sc.mine.sum() < w * h and not acc.mean64()[~sc.mine].any() and not acc.counts()[~sc.mine].any()
+            total += acc.mean64()
+            counts += acc.counts()
+    with r.accumulator(_cam(w, h), w, h, bounces=BOUNCES, integrator=integ, seed=SEED) as acc:
+        acc.add(2)
+        acc.freeze(mask)
+        acc.add(3)
+        assert _bits(acc.mean64()) == _bits(total) and _bits(acc.counts()) == _bits(counts)
+    assert _bits(total) == _bits(adaptive_ref.compose(lambda n: _oracle("cb", s, w, h, n, integ), counts))
+
+
+# ---------------------------------------------------------------- 2. masks where the list can go wrong
+def _mask_of(kind, w, h):
+    m = np.zeros((h, w), dtype=bool)
+    if kind == "checker":
+        return _checker(w, h)
+    if kind == "one_active":
+        m[:] = True
+        m[h // 2, w // 3] = False
+        return m
+    if kind == "65_active":                                # one wave of a pass and one lane of the next
+        m[:] = True
+        flat = m.reshape(-1)
+        flat[np.arange(w * h)[3::(w * h) // 65][:65]] = False
+        assert int((~m).sum()) == 65
+        return m
+    if kind == "blocks":                                   # an 8x8 block all frozen, one all active, a checkerboard elsewhere
+        m = _checker(w, h)
+        m[0:8, 0:8] = True
+        m[8:16, 8:16] = False
+        return m
+    raise AssertionError(kind)
+
+
+@pytest.mark.parametrize("kind", ["checker", "one_active", "65_active", "blocks"])
+@pytest.mark.parametrize("w,h", SHAPES)
+def test_masks(cb, w, h, kind):
+    s, r = cb
+    with r.accumulator(_cam(w, h), w, h, bounces=BOUNCES, seed=SEED) as acc:
+        sc = Sched(acc, w, h)
+        sc.add(2)
+        sc.freeze(_mask_of(kind, w, h))
+        sc.check_counts_and_list()
+        sc.add(3)
+        sc.check_counts_and_list()
+        sc.check_image(lambda n: _oracle("cb", s, w, h, n, 0))
+
+
+@pytest.mark.parametrize("w,h", SHAPES)
+def test_all_frozen_all_zero_and_a_freeze_at_zero_samples(cb, w, h):
+    s, r = cb
+    render = lambda n: _oracle("cb", s, w, h, n, 0)        # noqa: E731
+    with r.accumulator(_cam(w, h), w, h, bounces=BOUNCES, seed=SEED) as acc:   # all frozen: the add is a no-op
+        sc = Sched(acc, w, h)
+        sc.add(2)
+        sc.freeze(np.ones((h, w), dtype=bool))
+        st = sc.add(3)
+        assert st["samples"] == 0 and st["rays_traced"] == 0 and acc.samples == 2 and acc.active_pixels().size == 0
+        sc.check_counts_and_list()
+        sc.check_image(render)
+    with r.accumulator(_cam(w, h), w, h, bounces=BOUNCES, seed=SEED) as acc:   # an all-zero mask: the plain accumulator
+        sc = Sched(acc, w, h)
+        sc.add(2)
+        sc.freeze(np.zeros((h, w), dtype=bool))
+        sc.add(3)
+        sc.check_counts_and_list()
+        plain, _ = r.render(_cam(w, h), w, h, 5, bounces=BOUNCES, seed=SEED)
+        assert _bits(acc.image()) == _bits(plain)
+        sc.check_image(render)
+    with r.accumulator(_cam(w, h), w, h, bounces=BOUNCES, seed=SEED) as acc:   # frozen at 0 samples: mean 0, count 0
+        sc = Sched(acc, w, h)
+        sc.freeze(_checker(w, h))
+        sc.add(2)                                          # (the active pixels' first samples: the curand_init path)
+        sc.add(3)
+        sc.check_counts_and_list()
+        assert not acc.mean64()[_checker(w, h)].any() and sorted(np.unique(sc.counts)) == [0, 5]
+        sc.check_image(render)
+
+
+# ---------------------------------------------------------------- 3. the list across blocks
+@pytest.mark.parametrize("w,h", [(256, 256), (264, 256)])
+def test_active_list_across_256_blocks(cb, w, h):
+    """256x256: 65536 slots, 256 blocks of the compaction, so the scan of the block totals runs over a full round of
+    256; 264x256: 264 blocks, a second round that starts from the first one's carry.  A seeded pseudo-random mask of
+    about half the pixels; 1 + 1 samples at bounces 1, against plain renders."""
+    s, r = cb
+    mask = np.random.default_rng(20241019).random((h, w)) < 0.5
+    one, _ = r.render(_cam(w, h), w, h, 1, bounces=1, seed=SEED)
+    two, _ = r.render(_cam(w, h), w, h, 2, bounces=1, seed=SEED)
+    with r.accumulator(_cam(w, h), w, h, bounces=1, seed=SEED) as acc:
+        sc = Sched(acc, w, h)
+        sc.add(1)
+        sc.freeze(mask)
+        sc.check_counts_and_list()
+        st = sc.add(1)
+        assert 0.45 * w * h < st["samples"] < 0.55 * w * h
+        sc.check_counts_and_list()
+        assert _bits(acc.image()) == _bits(np.where(mask[..., None], one, two))
+
+
+# ---------------------------------------------------------------- 4. the device output buffer
+def test_device_output_keeps_frozen_pixels(cb):
+    import torch
+    s, r = cb
+    w, h = 20, 13
+    mask = _checker(w, h)
+    with r.accumulator(_cam(w, h), w, h, bounces=BOUNCES, seed=SEED) as acc:
+        buf = torch.full((h, w, 3), -1.0, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        acc.add(2, d_out_ptr=buf.data_ptr())
+        first = buf.cpu().numpy()
+        assert _bits(first) == _bits(acc.image())
+        acc.freeze(mask)
+        st = acc.add(3, d_out_ptr=buf.data_ptr())
+        assert st["samples"] == int((~mask).sum()) * 3
+        got = buf.cpu().numpy()
+        assert _bits(got[mask]) == _bits(first[mask])                      # frozen: the bytes they had
+        assert _bits(got) == _bits(acc.image()) and (got[~mask] != first[~mask]).any()
+
+
+# ---------------------------------------------------------------- 5. the estimator with per-pixel counts
+def _check_est(est, ref, acc):
+    mu, m2 = est.read()
+    assert _bits(mu) == _bits(ref.mu) and _bits(m2) == _bits(ref.m2)
+    for tol in TOLS:
+        s = est.update(tol=tol)
+        want = ref.summary(tol)
+        assert s["samples"] == acc.samples and {k: s[k] for k in want} == want, (tol, s, want)
+    assert _bits(est.error_map()) == _bits(ref.error_map())
+    mu2, m22 = est.read()
+    assert _bits(mu2) == _bits(mu) and _bits(m22) == _bits(m2)             # (re-summarising folds nothing)
+
+
+def _fold(est, ref, acc):
+    est.update()
+    assert ref.update(acc.samples, acc.counts(), acc.mean64())
+    _check_est(est, ref, acc)
+
+
+@pytest.mark.parametrize("integ", [0, 1])
+@pytest.mark.parametrize("w,h", SHAPES)
+def test_estimator_over_a_mixed_schedule(cb, w, h, integ):
+    s, r = cb
+    with r.accumulator(_cam(w, h), w, h, bounces=BOUNCES, integrator=integ, seed=SEED) as acc, acc.noise() as est:
+        sc = Sched(acc, w, h)
+        ref = adaptive_ref.AdaptiveRef(0, acc.mean64())
+        for k in (2, 3, 4):
+            sc.add(k)
+            _fold(est, ref, acc)
+        # a device freeze: what the restatement calls converged, among the active pixels
+        want = ref.converged(0.25)
+        newly, active = est.freeze(tol=0.25)
+        assert 0 < newly == int(want.sum()) < w * h and active == w * h - newly
+        sc.frozen |= want
+        sc.check_counts_and_list()
+        _check_est(est, ref, acc)                                          # (a freeze changes nothing of the state)
+        sc.add(2)
+        _fold(est, ref, acc)
+        # a host freeze between two adds, one update after both
+        half = np.zeros((h, w), dtype=bool)
+        half[: h // 2] = True
+        sc.add(3)
+        sc.freeze(half)
+        sc.add(1)
+        sc.check_counts_and_list()
+        _fold(est, ref, acc)
+        # (frozen at 9: three batches; frozen at 14: the fold at 11 and this one, with s = 3; active: s = 4)
+        assert sorted(np.unique(ref.bq)) == [3, 5] and sorted(np.unique(ref.Wq)) == [9, 14, 15]
+        assert sorted(np.unique(sc.counts)) == [9, 14, 15]
+        # and a second device freeze, which must not count the frozen pixels as newly frozen
+        want = ref.converged(0.25) & ~sc.frozen
+        newly, active = est.freeze(tol=0.25)
+        assert newly == int(want.sum()) and active == int((~(sc.frozen | want)).sum())
+        sc.frozen |= want
+        sc.add(2)
+        sc.check_counts_and_list()
+        if active:                                         # (with nothing left to sample the add was a no-op)
+            _fold(est, ref, acc)
+        sc.check_image(lambda n: _oracle("cb", s, w, h, n, integ))
+
+
+def test_estimator_attached_after_a_freeze(cb):
+    s, r = cb
+    w, h = 20, 13
+    with r.accumulator(_cam(w, h), w, h, bounces=BOUNCES, seed=SEED) as acc:
+        sc = Sched(acc, w, h)
+        sc.add(3)
+        sc.freeze(_checker(w, h))
+        with acc.noise() as est:
+            ref = adaptive_ref.AdaptiveRef(3, acc.mean64())
+            _check_est(est, ref, acc)
+            for k in (2, 4, 1):
+                sc.add(k)
+                _fold(est, ref, acc)
+            assert not ref.bq[_checker(w, h)].any() and np.isposinf(est.error_map()[_checker(w, h)]).all()
+            newly, active = est.freeze(tol=1.0)
+            assert newly == int((ref.converged(1.0) & ~sc.frozen).sum()) and active == int((~sc.frozen).sum()) - newly
+
+
+def test_estimator_without_frozen_pixels_is_unchanged(cb):
+    """A device freeze that freezes nothing leaves the accumulator and the estimator on their plain paths."""
+    s, r = cb
+    w, h = 24, 16
+    with r.accumulator(_cam(w, h), w, h, bounces=BOUNCES, seed=SEED) as acc, acc.noise() as est:
+        ref = noise_ref.NoiseRef(0, acc.mean64())
+        acc.add(2)
+        est.update()
+        ref.update(acc.samples, acc.mean64())
+        assert est.freeze(tol=1.0) == (0, w * h)           # one batch: every error is +inf, nothing converges
+        for k in (3, 4):
+            st = acc.add(k)
+            assert st["samples"] == w * h * k and st["split_pixels"] > 0       # the planned units, not the list's
+            ref.update(acc.samples, acc.mean64())
+            for tol in TOLS:
+                got, want = est.update(tol=tol), ref.summary(tol)
+                assert {k_: got[k_] for k_ in want} == want
+            assert [_bits(a) for a in est.read()] == [_bits(ref.mu), _bits(ref.m2)]
+        assert (acc.counts() == 9).all() and acc.active_pixels().size == w * h
+        assert _bits(acc.mean64()) == _bits(_oracle("cb", s, w, h, 9, 0))
+
+
+# ---------------------------------------------------------------- 6. the loop
+@pytest.mark.parametrize("integ", [0, 1])
+@pytest.mark.parametrize("w,h", LOOP_SHAPES)
+def test_add_adaptive(cb, w, h, integ):
+    s, r = cb
+    kw = dict(tol=LOOP["tol"], quantile=LOOP["quantile"], min_batches=LOOP["min_batches"])
+    with r.accumulator(_cam(w, h), w, h, bounces=BOUNCES, integrator=integ, seed=SEED) as acc:
+        res = acc.add_adaptive(LOOP["pass_spp"], LOOP["cap"], **kw)
+        counts, mean, state = acc.counts(), acc.mean64(), acc._noise.read()
+        emap = acc._noise.error_map()
+    # the restatement's simulation on oracle images
+    sim = adaptive_ref.simulate(lambda n: _oracle("cb", s, w, h, n, integ), (h, w), **LOOP)
+    assert _bits(counts) == _bits(sim["counts"]) and res["samples_total"] == sim["samples_total"] == int(counts.sum())
+    assert res["samples_total"] <= 0.6 * w * h * LOOP["cap"]
+    assert res["stopped_converged"] is False and res["passes"] == sim["passes"] == 8 and res["samples"] == LOOP["cap"]
+    assert 0 < res["active"] == sim["active"] <= int((counts == LOOP["cap"]).sum())   # (some froze at the cap)
+    want = sim["summary"]
+    assert {k: res["summary"][k] for k in want} == want
+    assert _bits(mean) == _bits(adaptive_ref.compose(lambda n: _oracle("cb", s, w, h, n, integ), counts))
+    assert _bits(state[0]) == _bits(sim["est"].mu) and _bits(state[1]) == _bits(sim["est"].m2)
+    assert _bits(emap) == _bits(sim["est"].error_map())
+    # the loop spelled out
+    with r.accumulator(_cam(w, h), w, h, bounces=BOUNCES, integrator=integ, seed=SEED) as acc, acc.noise() as est:
+        active, passes = w * h, 0
+        while acc.samples < LOOP["cap"] and active > 0:
+            acc.add(min(LOOP["pass_spp"], LOOP["cap"] - acc.samples))
+            summ = est.update(tol=LOOP["tol"])
+            passes += 1
+            if summ["batches"] >= LOOP["min_batches"]:
+                _, active = est.freeze(tol=LOOP["tol"])
+        assert passes == res["passes"] and active == res["active"] and summ == res["summary"]
+        assert _bits(acc.counts()) == _bits(counts) and _bits(acc.mean64()) == _bits(mean)
+        assert [_bits(a) for a in est.read()] == [_bits(a) for a in state]
+
+
+def test_add_adaptive_until_everything_is_frozen(cb):
+    s, r = cb
+    w, h = 20, 13
+    with r.accumulator(_cam(w, h), w, h, bounces=BOUNCES, seed=SEED) as acc:
+        res = acc.add_adaptive(4, 32, tol=1e3, quantile=1.0)
+        assert res["active"] == 0 and res["stopped_converged"] is True and res["passes"] == 2
+        assert res["samples"] == acc.samples == 8 and res["samples_total"] == 8 * w * h
+        assert (acc.counts() == 8).all() and acc.active_pixels().size == 0
+        assert _bits(acc.mean64()) == _bits(_oracle("cb", s, w, h, 8, 0))
+        again = acc.add_adaptive(4, 32, tol=1e3, quantile=1.0)            # nothing active: no pass
+        assert again["passes"] == 0 and again["stopped_converged"] is True and acc.samples == 8
+        for kw in (dict(quantile=0.0), dict(quantile=1.5), dict(min_batches=1)):
+            with pytest.raises(pt.PtError) as e:
+                acc.add_adaptive(4, 40, tol=0.05, **kw)
+            assert e.value.code == pt.PT_E_INVALID and "pt_accum_add_adaptive" in str(e.value)
+
+
+# ---------------------------------------------------------------- 7. checkpoints
+def test_save_refuses_unequal_counts(cb, tmp_path):
+    s, r = cb
+    w, h = 24, 16
+    f = str(tmp_path / "a.ptacc")
+    with r.accumulator(_cam(w, h), w, h, bounces=BOUNCES, seed=SEED) as acc:
+        acc.add(2)
+        acc.freeze(_checker(w, h))
+        acc.save(f)                                        # frozen pixels, but every count is 2: saved as before
+        with r.load_accumulator(f) as again:
+            assert again.samples == 2 and _bits(again.mean64()) == _bits(acc.mean64())
+            again.add(3)
+            assert _bits(again.mean64()) == _bits(_oracle("cb", s, w, h, 5, 0))
+        acc.add(3)
+        with pytest.raises(pt.PtError) as e:
+            acc.save(f)
+        assert e.value.code == pt.PT_E_INVALID and "format version 1 holds a single sample count" in str(e.value)
