@@ -94,6 +94,10 @@ class DenoiseParams(C.Structure):
                 ("sigma_color", C.c_float), ("flags", C.c_uint32)]
 
 
+class DenoiseGuidedParams(C.Structure):
+    _fields_ = [("base", DenoiseParams), ("sigma_luma", C.c_float)]
+
+
 class NoiseParams(C.Structure):
     _fields_ = [("tol", C.c_float), ("y_floor", C.c_float)]
 
@@ -121,7 +125,7 @@ class AdaptiveResult(C.Structure):
                 ("active", C.c_uint64), ("samples_total", C.c_uint64)]
 
 
-assert C.sizeof(Feature) == 48
+assert C.sizeof(Feature) == 48 and C.sizeof(DenoiseGuidedParams) == 24
 assert C.sizeof(NoiseSummary) == 32 + 64 * 8 and C.sizeof(ConvergeParams) == 24
 assert C.sizeof(Vec3) == 12 and C.sizeof(Triangle) == 28 and C.sizeof(Material) == 48
 assert C.sizeof(BvhNode) == 32 and C.sizeof(Camera) == 32
@@ -184,6 +188,8 @@ SIGNATURES = {
     "pt_noise_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pt_noise_map": (C.c_int, [C.c_void_p, C.POINTER(NoiseParams), C.c_void_p]),
     "pt_noise_map_device": (C.c_int, [C.c_void_p, C.POINTER(NoiseParams), C.c_void_p, C.c_void_p]),
+    "pt_noise_variance": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pt_noise_variance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pt_noise_destroy": (None, [C.c_void_p]),
     "pt_accum_add_until": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ConvergeParams), C.c_void_p, C.c_void_p,
                                      C.POINTER(ConvergeResult)]),
@@ -201,6 +207,11 @@ SIGNATURES = {
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "pt_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                              C.c_void_p]),
+    "pt_denoise_guided_defaults": (None, [C.POINTER(DenoiseGuidedParams)]),
+    "pt_denoise_guided_device": (C.c_int, [C.c_void_p, C.POINTER(DenoiseGuidedParams), C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_denoise_guided": (C.c_int, [C.c_void_p, C.POINTER(DenoiseGuidedParams), C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "pt_destroy": (None, [C.c_void_p]),
 }
 

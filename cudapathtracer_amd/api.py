@@ -39,6 +39,15 @@ def denoise_defaults():
     return {k: getattr(dp, k) for k, _ in dp._fields_}
 
 
+def denoise_guided_defaults():
+    """pt_denoise_guided_defaults as a dict: pt_denoise's fields and sigma_luma."""
+    gp = L.DenoiseGuidedParams()
+    L.lib().pt_denoise_guided_defaults(C.byref(gp))
+    d = {k: getattr(gp.base, k) for k, _ in gp.base._fields_}
+    d["sigma_luma"] = gp.sigma_luma
+    return d
+
+
 def noise_defaults():
     """pt_noise_defaults as a dict (tol, y_floor)."""
     np_ = L.NoiseParams()
@@ -378,6 +387,46 @@ class Renderer:
                                           C.c_void_p(int(d_out_ptr)),
                                           None if stream_ptr is None else C.c_void_p(int(stream_ptr))))
 
+    @staticmethod
+    def denoise_guided_params(iterations=5, normal_power_log2=5, sigma_depth=0.02, sigma_color=0.0, demodulate=True,
+                              sigma_luma=2.0):
+        gp = L.DenoiseGuidedParams()
+        gp.base = Renderer.denoise_params(iterations, normal_power_log2, sigma_depth, sigma_color, demodulate)
+        gp.sigma_luma = float(sigma_luma)
+        return gp
+
+    def denoise_guided(self, img, features, var, iterations=5, normal_power_log2=5, sigma_depth=0.02, sigma_color=0.0,
+                       demodulate=True, pixel_order=0, sigma_luma=2.0):
+        """The variance-guided a-trous filter (pt_denoise_guided): denoise() with a weight on the luminance
+        difference measured against `var`, the variance of each pixel's mean luminance (NoiseEstimate.variance(), or
+        any array shaped like the image without its channel axis; inf or NaN = unknown).  Where the estimate says a
+        pixel has converged the filter leaves it alone."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        feat = np.ascontiguousarray(features, dtype=FEATURE)
+        var = np.ascontiguousarray(var, dtype=np.float32)
+        if pixel_order == L.PT_ORDER_MORTON:
+            n = img.size // 3
+            w = h = int(round(n ** 0.5))
+        else:
+            h, w = img.shape[:2]
+        if feat.size != w * h or img.size != w * h * 3 or var.size != w * h:
+            raise ValueError("denoise_guided: image, features and variance differ in size")
+        gp = self.denoise_guided_params(iterations, normal_power_log2, sigma_depth, sigma_color, demodulate, sigma_luma)
+        out = np.empty_like(img)
+        L.check(L.lib().pt_denoise_guided(self._h, C.byref(gp), w, h, int(pixel_order), img.ctypes.data, feat.ctypes.data,
+                                          var.ctypes.data, out.ctypes.data))
+        return out
+
+    def denoise_guided_device(self, d_in_ptr, d_feat_ptr, d_var_ptr, d_out_ptr, width, height, iterations=5,
+                              normal_power_log2=5, sigma_depth=0.02, sigma_color=0.0, demodulate=True, pixel_order=0,
+                              sigma_luma=2.0, stream_ptr=None):
+        """pt_denoise_guided_device on raw device pointers (d_out_ptr may equal d_in_ptr); blocking."""
+        gp = self.denoise_guided_params(iterations, normal_power_log2, sigma_depth, sigma_color, demodulate, sigma_luma)
+        L.check(L.lib().pt_denoise_guided_device(self._h, C.byref(gp), int(width), int(height), int(pixel_order),
+                                                 C.c_void_p(int(d_in_ptr)), C.c_void_p(int(d_feat_ptr)),
+                                                 C.c_void_p(int(d_var_ptr)), C.c_void_p(int(d_out_ptr)),
+                                                 None if stream_ptr is None else C.c_void_p(int(stream_ptr))))
+
     def tonemap(self, img):
         """Output step on the GPU: (H, W, 3) float32 mean image -> int32 codes equal to
         pt_tonemap_u8 (kernel.cu:763-778) per channel."""
@@ -626,6 +675,20 @@ class NoiseEstimate:
         out = np.zeros(self._shape(), dtype=np.float32)
         L.check(L.lib().pt_noise_map(self._h, C.byref(np_), out.ctypes.data))
         return out
+
+
+    def variance(self):
+        """The estimated variance of every pixel's mean luminance over all of its samples, float32 (pt_noise_variance:
+        inf before two batches; pixels outside the shard 0): what Renderer.denoise_guided takes.  Reads the state of
+        the last update()."""
+        out = np.zeros(self._shape(), dtype=np.float32)
+        L.check(L.lib().pt_noise_variance(self._h, out.ctypes.data))
+        return out
+
+    def variance_device(self, d_var_ptr, stream_ptr=None):
+        """variance() into a device buffer of W*H float32; pixels outside the shard are left untouched."""
+        L.check(L.lib().pt_noise_variance_device(self._h, C.c_void_p(int(d_var_ptr)),
+                                                 None if stream_ptr is None else C.c_void_p(int(stream_ptr))))
 
 
 class Group:

@@ -41,6 +41,12 @@
 //                                         ITERS iterations, default 5) before the PPM / PFM is written -- also
 //                                         after every --pass-spp pass, after --resume and after the multi-GPU
 //                                         reduce (features and filter then run for the whole frame on GPU 0)
+// --denoise-guided [ITERS]                with an estimator (--until-error, with or without --adaptive; --error-map and
+//   [--sigma-luma S]                      --variance-map attach one too): filter the FINAL image with the
+//                                         variance-guided denoiser (pt_denoise_guided, sigma_luma S, default 2) and the
+//                                         estimator's variance map; the files written after earlier passes are unfiltered
+// --variance-map FILE.pfm                 with --pass-spp K: write the variance of every pixel's mean luminance
+//                                         (pt_noise_variance) as a grey PFM
 // --aov PREFIX                            write the primary-hit feature buffers as PREFIX_albedo.pfm,
 //                                         PREFIX_normal.pfm, PREFIX_position.pfm and PREFIX_depth.pfm (depth
 //                                         replicated to 3 channels)
@@ -75,13 +81,16 @@ struct Obj {
             "              [--checkpoint FILE] [--resume FILE] [--pass-spp K]\n"
             "              [--denoise [ITERS]] [--aov PREFIX]\n"
             "              [--until-error TOL [--error-quantile Q] [--min-batches B] [--adaptive]] [--error-map FILE.pfm]\n"
-            "              [--count-map FILE.pfm]\n"
+            "              [--count-map FILE.pfm] [--denoise-guided [ITERS] [--sigma-luma S]] [--variance-map FILE.pfm]\n"
             "  --until-error TOL  with --pass-spp: stop once the fraction Q (default 0.95) of the pixels has a relative\n"
             "                     standard error <= TOL after at least B (default 2) passes; --spp is the cap\n"
             "  --adaptive         with --until-error: freeze each pixel once its error is <= TOL and sample only the rest\n"
             "  --count-map FILE   with --pass-spp: write the per-pixel sample counts as a grey PFM\n"
             "  --error-map FILE   with --pass-spp: write the per-pixel squared relative standard error as a grey PFM\n"
             "  --denoise [ITERS]  filter the image (edge-avoiding a-trous, ITERS iterations, default 5) before it is written\n"
+            "  --denoise-guided [ITERS]  with --until-error: filter the final image guided by the estimator's variance map\n"
+            "  --sigma-luma S     the guided filter's luminance tolerance in standard errors (default 2)\n"
+            "  --variance-map FILE  with --pass-spp: write the variance of every pixel's mean luminance as a grey PFM\n"
             "  --aov PREFIX       write PREFIX_albedo.pfm, PREFIX_normal.pfm, PREFIX_position.pfm, PREFIX_depth.pfm\n");
     exit(2);
 }
@@ -134,6 +143,10 @@ int main(int argc, char** argv)
     bool denoise = false;
     pt_denoise_params dparams;
     pt_denoise_defaults(&dparams);
+    bool guided = false;
+    pt_denoise_guided_params gparams;
+    pt_denoise_guided_defaults(&gparams);
+    std::string variance_map;
     std::string aov;
     bool until_error = false, adaptive = false;
     std::string error_map, count_map;
@@ -183,6 +196,13 @@ int main(int argc, char** argv)
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') dparams.iterations = atoi(argv[++i]);
             if (dparams.iterations > 8) usage("--denoise takes 0..8 iterations");
         }
+        else if (a == "--denoise-guided") {
+            guided = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') gparams.base.iterations = atoi(argv[++i]);
+            if (gparams.base.iterations > 8) usage("--denoise-guided takes 0..8 iterations");
+        }
+        else if (a == "--sigma-luma") gparams.sigma_luma = strtof(next().c_str(), nullptr);
+        else if (a == "--variance-map") variance_map = next();
         else if (a == "--aov") aov = next();
         else if (a == "--until-error") { until_error = true; conv.noise.tol = strtof(next().c_str(), nullptr); }
         else if (a == "--error-quantile") conv.quantile = strtof(next().c_str(), nullptr);
@@ -202,9 +222,12 @@ int main(int argc, char** argv)
     if (ref_walk) p.flags |= PT_FLAG_REFERENCE_TRAVERSAL | PT_FLAG_NO_PRIMARY_CACHE | PT_FLAG_NO_DEAD_PATH_SKIP;
     cam.pxl_width = p.width;
     cam.pxl_height = p.height;
-    const bool estimate = until_error || !error_map.empty();
-    if (estimate && gpus != 1) usage("--until-error / --error-map need --gpus 1 (one estimator per accumulator)");
-    if (estimate && pass_spp < 1) usage("--until-error / --error-map need --pass-spp K (the passes are the batches)");
+    const bool estimate = until_error || !error_map.empty() || !variance_map.empty();
+    if (guided && !estimate) usage("--denoise-guided needs an estimator: --until-error TOL with --pass-spp K");
+    if (guided && denoise) usage("--denoise and --denoise-guided: choose one");
+    if (!(gparams.sigma_luma > 0.0f) || !std::isfinite(gparams.sigma_luma)) usage("--sigma-luma must be finite and > 0");
+    if (estimate && gpus != 1) usage("--until-error / --error-map / --variance-map need --gpus 1 (one estimator per accumulator)");
+    if (estimate && pass_spp < 1) usage("--until-error / --error-map / --variance-map need --pass-spp K (the passes are the batches)");
     if (!(conv.noise.tol > 0.0f)) usage("--until-error takes a tolerance > 0");
     if (!(conv.quantile > 0.0f && conv.quantile <= 1.0f)) usage("--error-quantile is in (0, 1]");
     if (conv.min_batches < 2) usage("--min-batches must be >= 2");
@@ -271,6 +294,7 @@ int main(int argc, char** argv)
     std::vector<float> img(n, 0.0f);
     // --denoise / --aov: the whole frame's primary-hit features, once, on the first context
     std::vector<pt_feature> feat;
+    std::vector<float> var;   // --denoise-guided / --variance-map: the estimator's variance map, once the passes are done
     auto features = [&]() -> bool {
         if (!feat.empty()) return true;
         feat.resize((size_t)p.width * p.height);
@@ -284,6 +308,12 @@ int main(int argc, char** argv)
             if (!features()) return "pt_render_features";
             if (pt_denoise(ctx[0], &dparams, p.width, p.height, p.pixel_order, img.data(), feat.data(), img.data()) != PT_OK)
                 return "pt_denoise";
+        }
+        if (guided && !var.empty()) {
+            if (!features()) return "pt_render_features";
+            if (pt_denoise_guided(ctx[0], &gparams, p.width, p.height, p.pixel_order, img.data(), feat.data(), var.data(), img.data()) !=
+                PT_OK)
+                return "pt_denoise_guided";
         }
         if (p.pixel_order == PT_ORDER_MORTON) {
             // the buffer as the reference holds it (imgBuff[mortonPxltoI(x,y)]): the PPM loop of
@@ -377,6 +407,20 @@ int main(int argc, char** argv)
                     for (int k = 0; k < 3; ++k) grey[((size_t)y * p.width + x) * 3 + k] = v;
                 }
             if (pt_write_pfm(error_map.c_str(), grey.data(), p.width, p.height) != PT_OK) return die("--error-map");
+        }
+        if (guided || !variance_map.empty()) {
+            const size_t npix = (size_t)p.width * p.height;
+            var.resize(npix);
+            if (pt_noise_variance(noise, var.data()) != PT_OK) return die("pt_noise_variance");
+            if (!variance_map.empty()) {
+                std::vector<float> grey(npix * 3);
+                for (int y = 0; y < p.height; ++y)
+                    for (int x = 0; x < p.width; ++x) {
+                        const float v = var[p.pixel_order == PT_ORDER_MORTON ? (size_t)pt_morton_pxl_to_i(x, y) : (size_t)y * p.width + x];
+                        for (int k = 0; k < 3; ++k) grey[((size_t)y * p.width + x) * 3 + k] = v;
+                    }
+                if (pt_write_pfm(variance_map.c_str(), grey.data(), p.width, p.height) != PT_OK) return die("--variance-map");
+            }
         }
         pt_noise_destroy(noise);
         pt_accum_destroy(acc);

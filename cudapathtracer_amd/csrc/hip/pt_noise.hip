@@ -5,12 +5,14 @@
 // contraction, IEEE division); tests/noise_ref.py restates it in numpy and the kernels agree with it in every bit.
 //
 // State: five f64 planes per work slot, in the accumulator's slot order (like its mean): prev[3], mu, m2.
-// Two kernels, lanes on consecutive slots, so every plane access is a coalesced 8-B-per-lane row:
+// Three kernels, lanes on consecutive slots, so every plane access is a coalesced 8-B-per-lane row:
 //   noise_update<kFold>  one sweep: (kFold) folds the newest pass into the state, then rel2, the converged
 //                        count (per wave: ballot + popcount) and a 64-bin LDS histogram per block, flushed
 //                        with one global atomic per non-zero bin into one of kSumCopies copies of a small
 //                        buffer, which the host adds up.  All integer: no reduction-order effects.
 //   noise_map            rel2 of every slot scattered to its pixel's index (scanline or Morton).
+//   noise_variance       the variance of the mean of all of the pixel's samples, scattered the same way: what the
+//                        variance-guided denoiser (pt_denoise_guided) takes.
 // Adaptive sampling (the accumulator has frozen pixels: AccumView::frozen_at): the pixels' counts differ, so each
 // slot carries its own window weight and batch count (two u32 planes, allocated then: kPix instances of the two
 // kernels; an accumulator with no frozen pixel runs the scalar instances, unchanged), and
@@ -182,6 +184,29 @@ __global__ __launch_bounds__(kBlock) void noise_map(NoiseArgs a)
     }
 }
 
+// pt_noise_variance: the variance of the mean of all n_q samples, m2 / ((b - 1) * n_q), scattered like noise_map.
+// Scalar instance: a.batches and a.vden = (batches - 1) * samples; kPix: b_q from the plane, n_q the count the
+// pixel was frozen at or a.n_now.
+template <bool kPix>
+__global__ __launch_bounds__(kBlock) void noise_variance(NoiseArgs a)
+{
+    const size_t n = a.n;
+    for (size_t q = (size_t)blockIdx.x * kBlock + threadIdx.x; q < n; q += (size_t)gridDim.x * kBlock) {
+        const uint32_t o = a.dst[q];
+        if (o == kNoPixel) continue;
+        const double m2 = a.state[4 * n + q];
+        double v = __longlong_as_double(0x7ff0000000000000ll);
+        if (kPix) {
+            const uint32_t b = a.pb[q], at = a.frozen_at[q];
+            const uint32_t nq = (at == pt::kSlotActive) ? a.n_now : at;
+            if (b >= 2u) v = m2 / ((double)(b - 1u) * (double)nq);
+        } else if (a.batches >= 2) {
+            v = m2 / a.vden;
+        }
+        a.map[o] = (float)v;
+    }
+}
+
 // Every slot's W_q / b_q from the scalars: until the first freeze all pixels fold in step.
 __global__ __launch_bounds__(kBlock) void noise_fill_pix(NoiseArgs a, uint32_t w, uint32_t b)
 {
@@ -247,6 +272,14 @@ int check(const char* who, const pt_noise* z, const pt_noise_params* np)
 {
     if (!z || !np) return pt::fail(PT_E_INVALID, "%s: null argument", who);
     if (!params_ok(np)) return pt::fail(PT_E_INVALID, "%s: tol and y_floor must be finite and > 0", who);
+    if (pt::ctx_in_flight(z->ctx) > 0)
+        return pt::fail(PT_E_INVALID, "%s: %d asynchronous renders in flight (pt_render_wait first)", who, pt::ctx_in_flight(z->ctx));
+    return PT_OK;
+}
+
+int check_variance(const char* who, const pt_noise* z, const float* var)
+{
+    if (!z || !var) return pt::fail(PT_E_INVALID, "%s: null argument", who);
     if (pt::ctx_in_flight(z->ctx) > 0)
         return pt::fail(PT_E_INVALID, "%s: %d asynchronous renders in flight (pt_render_wait first)", who, pt::ctx_in_flight(z->ctx));
     return PT_OK;
@@ -444,6 +477,48 @@ int pt_noise_map(pt_noise* z, const pt_noise_params* np, float* rel2)
         NS_HIP(hipMemset(d, 0, bytes));
         if (int rc = pt_noise_map_device(z, np, d, nullptr)) return rc;
         NS_HIP(hipMemcpy(rel2, d, bytes, hipMemcpyDeviceToHost));
+        return PT_OK;
+    };
+    const int rc = run();
+    if (d) (void)hipFree(d);
+    return rc;
+}
+
+int pt_noise_variance_device(pt_noise* z, float* d_var, void* stream_v)
+{
+    pt::clear_error();
+    if (int rc = check_variance("pt_noise_variance_device", z, d_var)) return rc;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+    NS_HIP(hipSetDevice(pt::ctx_device(z->ctx)));
+    if (!z->slots()) return PT_OK;
+    if (int rc = follow_accum(z, stream)) return rc;
+    pt_noise_params np;
+    pt_noise_defaults(&np);   // (unused by the kernel: the variance has no floor and no tolerance)
+    NoiseArgs a = args_of(z, &np);
+    const int64_t samples = pt::accum_view(z->acc).samples;
+    a.map = d_var;
+    a.vden = (double)(z->batches - 1) * (double)samples;
+    a.n_now = (uint32_t)samples;
+    if (z->pix_live) hipLaunchKernelGGL(noise_variance<true>, dim3(grid_of(z)), dim3(kBlock), 0, stream, a);
+    else hipLaunchKernelGGL(noise_variance<false>, dim3(grid_of(z)), dim3(kBlock), 0, stream, a);
+    NS_HIP(hipGetLastError());
+    NS_HIP(hipStreamSynchronize(stream));
+    return PT_OK;
+}
+
+int pt_noise_variance(pt_noise* z, float* var)
+{
+    pt::clear_error();
+    if (int rc = check_variance("pt_noise_variance", z, var)) return rc;
+    const pt_params* p = pt::accum_view(z->acc).params;
+    const size_t bytes = (size_t)p->width * (size_t)p->height * sizeof(float);
+    NS_HIP(hipSetDevice(pt::ctx_device(z->ctx)));
+    float* d = nullptr;
+    auto run = [&]() -> int {
+        NS_HIP(hipMalloc(reinterpret_cast<void**>(&d), bytes));
+        NS_HIP(hipMemset(d, 0, bytes));
+        if (int rc = pt_noise_variance_device(z, d, nullptr)) return rc;
+        NS_HIP(hipMemcpy(var, d, bytes, hipMemcpyDeviceToHost));
         return PT_OK;
     };
     const int rc = run();

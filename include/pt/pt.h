@@ -22,6 +22,8 @@
  *                           pixels are frozen and the passes sample only the rest
  *        pt_render_features / pt_denoise  (no counterpart in the reference) per-pixel first-hit feature
  *                           buffers and an edge-avoiding a-trous filter: a preview from a few samples per pixel
+ *        pt_noise_variance / pt_denoise_guided  (no counterpart) the estimator's variance map and an a-trous filter
+ *                           guided by it, which leaves converged pixels alone: its result converges to the render
  *        pt_destroy      <- cudaFree (kernel.cu:782-783)
  *        pt_last_error   <- checkError (kernel.cu:37-42), but returned instead of printed
  *
@@ -458,6 +460,23 @@ int pt_noise_freeze(pt_noise* noise, const pt_noise_params* np, void* stream, ui
 int pt_accum_add_adaptive(pt_accum* acc, pt_noise* noise, const pt_converge_params* cp, float* d_out, void* stream,
                           pt_adaptive_result* result);
 
+/* ------------------------------------------------- the variance map of the image's mean
+ * What the variance-guided denoiser (pt_denoise_guided, below) takes: per pixel q the estimated variance of the
+ * mean luminance of ALL of the pixel's n_q samples, in f64 with every operation rounded on its own as above:
+ *   b_q >= 2:  v = m2 / ((double)(b_q - 1) * (double)n_q);  the map holds (float)v
+ *   b_q <  2:  the map holds +inf.
+ * n_q is the pixel's sample count: pt_accum_samples for an active pixel, the count it was frozen at for a frozen
+ * one.  b_q and m2 are the scalar batches and the pixel's m2, or the per-pixel values once the accumulator has a
+ * frozen pixel.  This is the window variance m2 / ((b-1) * W) scaled by W / n: the variance of the mean of all n
+ * samples if they are independent, so an estimator attached late (or after a resume) does not overstate the noise
+ * of the image; it equals the window variance when the window started at 0 samples.
+ * Indexing is pt_noise_map's: the accumulator's pixel_order; pt_noise_variance (host buffer, W*H) writes pixels
+ * outside the shard as 0, pt_noise_variance_device (device buffer on `stream`) leaves them untouched.  Both block
+ * and fold nothing: they read the state as of the last pt_noise_update.  PT_E_INVALID: null arguments,
+ * asynchronous renders in flight. */
+int pt_noise_variance(pt_noise* noise, float* var /* host, W*H */);
+int pt_noise_variance_device(pt_noise* noise, float* d_var, void* stream);
+
 /* The reference's trace() (kernel.cu:112-161) for n rays given as rays[6n] = {o.xyz, d.xyz}
  * (host buffers): tri_out[i] = winning ORIGINAL triangle index or -1, t_out[i] = its closestT
  * (MAX_FLOAT = 1e5 on a miss).  flags: 0 = the render path's walk, PT_FLAG_REFERENCE_BVH = the
@@ -568,6 +587,49 @@ int pt_denoise_device(pt_ctx* ctx, const pt_denoise_params* dp, int width, int h
                       const float* d_in, const pt_feature* d_feat, float* d_out, void* stream);
 int pt_denoise(pt_ctx* ctx, const pt_denoise_params* dp, int width, int height, int pixel_order,
                const float* in, const pt_feature* feat, float* out /* host */);
+
+/* ------------------------------------------------- the variance-guided denoiser
+ * pt_denoise is guided by geometry alone: it smooths a pixel as hard after 128 samples as after 4, so its bias
+ * is fixed and past some sample count it makes the image worse.  pt_denoise_guided adds a weight
+ * on the luminance difference, measured against the pixel's own estimated noise: where the estimate says the
+ * pixel has converged the filter leaves it alone, and the result converges to the render.
+ *
+ * `var` is W*H fp32 in pixel_order: the variance of each pixel's mean luminance, as pt_noise_variance returns
+ * it; any caller-made array is allowed.  Everything else is pt_denoise's (out may equal in; blocking; refused
+ * while asynchronous renders are in flight; the scratch is 72 B per pixel here, pt_denoise's stays 64 B).
+ * PT_E_INVALID: as pt_denoise, plus a null var and a sigma_luma that is not finite or <= 0.
+ *
+ * The arithmetic is pt_denoise's (all f32, every operation rounded on its own, no contraction, IEEE division,
+ * max(a, b) as `b > a ? b : a`) with these additions:
+ *   prepass:   A_p = (0.2126f*a_p[0] + 0.7152f*a_p[1]) + 0.0722f*a_p[2]   (1 with PT_DENOISE_NO_DEMODULATE)
+ *              t = var_p / (A_p*A_p);   v_p = (var_p >= 0 && t < 1e30f) ? t : 1e30f
+ *     NaN, negative, infinite and overflowing inputs all become the "unknown" value 1e30.  Demodulating the
+ *     variance of the luminance by the luminance of the albedo is an approximation (the channels are divided
+ *     by different albedos); it is exact for a grey albedo.
+ *   each iteration, before the taps (c: that iteration's input):
+ *              l_p = (0.2126f*c_p[0] + 0.7152f*c_p[1]) + 0.0722f*c_p[2]
+ *     the prefiltered variance, always at a spacing of 1 pixel: g = {1/4, 1/2, 1/4}; for j = -1..1 (outer),
+ *     i = -1..1 (inner), q = (x + i, y + j), skipped when outside the image or pass-through:
+ *              va = va + (g[j]*g[i])*v_q;   vw = vw + (g[j]*g[i])
+ *              vbar_p = va / vw;   den_p = (sigma_luma*sigma_luma)*vbar_p + 1e-20f
+ *   each tap, after w has all of pt_denoise's factors (the sigma_color one included when it is on):
+ *              dl = l_q - l_p;   w = w * (1 / (1 + (dl*dl)/den_p))
+ *              acc[k] = acc[k] + w*c_q[k];   wsum = wsum + w;   vacc = vacc + (w*w)*v_q
+ *   result:    wsum > 0:  c'_p[k] = acc[k] / wsum,  v'_p = vacc / (wsum*wsum);  otherwise both are kept.
+ *     Pass-through pixels keep everything; iterations = 0 returns the input bit for bit.
+ * With var unknown everywhere (+inf, say), (dl*dl)/den_p vanishes against 1 and the output equals pt_denoise's
+ * in every bit: this holds whenever dl*dl < 2^-25 * sigma_luma^2 * 1e30, which any real image satisfies, and the
+ * weight of a pixel's own tap does not underflow when squared, which normals of unit length ensure (v' stays
+ * above 1e30/25 then). */
+typedef struct {
+    pt_denoise_params base;
+    float sigma_luma;           /* > 0, finite: luminance differences count in units of sigma_luma standard errors */
+} pt_denoise_guided_params;     /* 24 B */
+void pt_denoise_guided_defaults(pt_denoise_guided_params* p);   /* base = pt_denoise_defaults, sigma_luma = 2.0f: a design choice */
+int pt_denoise_guided_device(pt_ctx* ctx, const pt_denoise_guided_params* gp, int width, int height, int pixel_order,
+                             const float* d_in, const pt_feature* d_feat, const float* d_var, float* d_out, void* stream);
+int pt_denoise_guided(pt_ctx* ctx, const pt_denoise_guided_params* gp, int width, int height, int pixel_order,
+                      const float* in, const pt_feature* feat, const float* var, float* out /* host */);
 
 /* ----------------------------------------------------------- one process, N GPUs
  * A group of contexts on distinct devices with one RCCL communicator per device
