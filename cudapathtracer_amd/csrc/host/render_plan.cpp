@@ -117,6 +117,13 @@ int plan_units(const PlanInput& in, const RenderKnobs& k, const std::function<in
         const uint32_t cap = per_block > in.lds_fixed ? (uint32_t)((per_block - in.lds_fixed) / in.top_node_bytes) : 1u;
         if (top_nodes > 0) top_nodes = std::max(1u, std::min(top_nodes, cap));   // (0: no triangles, no BVH4)
     }
+    if (in.npix == 0) {   // an empty shard (more shards than tiles): no unit, no block, nothing to budget
+        *out = UnitPlan{};
+        out->wpc = wpc;
+        out->top_nodes = top_nodes;
+        out->chunks = out->chunks_mid = out->chunks_fin = 1;
+        return PT_OK;
+    }
     uint32_t blocks = (uint32_t)in.num_cus * (wpc / 4 ? wpc / 4 : 1);
     // Work units: a pixel's samples run in sequence, so a unit lasts one pixel's time and the
     // kernel's end waits for the last units started.  Whole pixels first; the last `ntail`

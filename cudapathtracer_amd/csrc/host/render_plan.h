@@ -93,6 +93,7 @@ struct PlanInput {
 };
 // lbuf_budget: bytes the split pixels' per-sample radiance may take, asked only when pixels are split and
 // PT_LBUF_BUDGET_MB (read here, at every render) does not say; its error, if any, is plan_units's.
+// npix == 0 (an empty shard) gives the empty plan: nunits = blocks = 0, every chunk count 1, the budget not asked.
 int plan_units(const PlanInput& in, const RenderKnobs& k, const std::function<int(uint64_t*)>& lbuf_budget, UnitPlan* out);
 
 }  // namespace pt

@@ -184,6 +184,24 @@ typedef struct {
 #define PT_ORDER_SCANLINE 0
 #define PT_ORDER_MORTON 1
 
+/* Empty shards.  shard_count need not fit the image: a shard with shard_index >= the number of tiles (an 8-GPU job
+ * on a small preview image) is legal wherever a shard is taken, and owns no pixel.  Nothing is launched for it:
+ *   pt_render                  an all-zero image; stats samples, rays_traced, rays_reference, rays_nominal, work_units
+ *                              and split_pixels are 0, seconds and kernel_ms the (finite) time of the empty render
+ *   pt_render_device, pt_render_features_device, pt_noise_map_device, pt_noise_variance_device, d_out of pt_accum_add
+ *                              the buffer is left untouched (the host variants return their "outside the shard" value
+ *                              for every pixel)
+ *   pt_accum_add(spp)          succeeds with zero stats; pt_accum_samples still advances by spp (no pixel is frozen);
+ *                              pt_accum_read and pt_accum_counts give zeros
+ *   pt_accum_freeze            a no-op whatever the mask; pt_accum_active gives *n_out = 0
+ *   pt_accum_save / _load      the header (which alone names the shard) plus W*H all-zero records
+ *   pt_noise_update            pixels = converged = 0 and every bin 0; samples and batches advance as usual
+ *   pt_noise_freeze            *newly_frozen = *active = 0
+ *   pt_accum_add_until         stops with stopped_converged = 1 after exactly min_batches passes: 0 >= ceil(quantile * 0)
+ *   pt_accum_add_adaptive      no pixel is active: no pass, stopped_converged = 1, active = samples_total = 0,
+ *                              pt_accum_samples unchanged
+ * and the next render on the context is unaffected. */
+
 typedef struct {
     double seconds;            /* device time of the whole render (hipEvent pair around every
                                   launch: RNG seeding, integration, split-pixel finalisation)     */

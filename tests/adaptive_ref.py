@@ -99,11 +99,13 @@ def compose(render, counts):
     return out
 
 
-def simulate(render, shape, pass_spp, cap, tol, quantile=1.0, min_batches=2, y_floor=Y_FLOOR):
+def simulate(render, shape, pass_spp, cap, tol, quantile=1.0, min_batches=2, y_floor=Y_FLOOR, mask=None):
     """pt_accum_add_adaptive from 0 samples over render(n) -> the (shape, 3) f64 image after n samples of every pixel.
+    mask: the pixels of the accumulator's shard (default: all); the others are never sampled and count for nothing.
     Returns dict(counts, samples_total, passes, stopped_converged, active, est, summary)."""
     est = AdaptiveRef(0, shape=shape)
-    frozen = np.zeros(shape, dtype=bool)
+    mine = np.ones(shape, dtype=bool) if mask is None else np.asarray(mask, dtype=bool)
+    frozen = ~mine
     counts = np.zeros(shape, dtype=np.uint32)
     samples, passes, stopped, summary = 0, 0, False, None
     while samples < cap and not frozen.all():
@@ -111,10 +113,10 @@ def simulate(render, shape, pass_spp, cap, tol, quantile=1.0, min_batches=2, y_f
         counts[~frozen] = samples
         est.update(samples, counts, compose(render, counts))
         passes += 1
-        summary = est.summary(tol, y_floor)
+        summary = est.summary(tol, y_floor, mine)
         if summary["batches"] < min_batches:
             continue
-        frozen |= est.converged(tol, y_floor)
+        frozen |= est.converged(tol, y_floor) & mine
         if frozen.all() or summary["converged"] >= int(np.ceil(np.float64(np.float32(quantile)) * summary["pixels"])):
             stopped = True
             break

@@ -60,9 +60,9 @@ def _checker(w, h):
 class Sched:
     """An accumulator driven by adds and freezes, with the counts the schedule implies kept alongside."""
 
-    def __init__(self, acc, w, h, shard_index=0, shard_count=1):
+    def __init__(self, acc, w, h, shard_index=0, shard_count=1, tile=(8, 8)):
         self.acc, self.w, self.h = acc, w, h
-        self.order = shard.shard_pixels(w, h, shard_index, shard_count, 8, 8)
+        self.order = shard.shard_pixels(w, h, shard_index, shard_count, tile[0], tile[1])
         self.mine = np.zeros(w * h, dtype=bool)
         self.mine[self.order] = True
         self.mine = self.mine.reshape(h, w)

@@ -13,6 +13,7 @@ import subprocess
 import pytest
 
 from conftest import MODELS, ROOT
+from shard_geometries import GEOMETRIES, Geometry
 
 CSRC = os.path.join(ROOT, "cudapathtracer_amd", "csrc")
 PROBE = os.path.join(CSRC, "build", "host_probe")
@@ -162,6 +163,46 @@ def test_tile_grid_shards_partition_the_image(probe):
             assert g["grid_slots"] == g["ntiles"] * tw * tw
         assert sum(g["ntiles_shard"] for g in shards) == shards[0]["ntiles"]
         assert sum(g["in_image"] for g in shards) == w * h
+
+
+def test_tile_grid_of_the_gpu_shard_geometries(probe):
+    """tests/shard_geometries.py: non-square tiles larger than 8x8 on images they do not divide, and shards with
+    shard_index >= ntiles, which are legal and own nothing.  pt::tile_grid and pt_shard_pixels against shard.py."""
+    from cudapathtracer_amd import shard
+    cases = [(Geometry(g), k) for g in sorted(GEOMETRIES) for k in range(Geometry(g).shards)]
+    got = probe(["grid"], ["%d %d %d %d %d %d" % (g.w, g.h, g.tw, g.th, k, g.shards) for g, k in cases])
+    assert len(got) == len(cases)
+    empty = 0
+    for (g, k), r in zip(cases, got):
+        pix = shard.shard_pixels(g.w, g.h, k, g.shards, g.tw, g.th)
+        tiles = shard.shard_tiles(g.w, g.h, k, g.shards, g.tw, g.th)
+        tx, ty = shard.tiles_shape(g.w, g.h, g.tw, g.th)
+        assert len(pix) == g.pixels[k], (g, k)
+        assert r["validate_rc"] == 0 and r["shard_pixels_rc"] == 0 and r["fits"], (g, k)
+        assert (r["tile_w"], r["tile_h"], r["tiles_x"], r["ntiles"]) == (g.tw, g.th, tx, tx * ty), (g, k)
+        assert (r["tile_bx"], r["tile_blocks"]) == (g.tw // 8, (g.tw // 8) * (g.th // 8)), (g, k)
+        assert r["in_image"] == len(pix) and r["ntiles_shard"] == len(tiles), (g, k)
+        assert r["npix"] == len(tiles) * g.tw * g.th and r["grid_slots"] == tx * ty * g.tw * g.th, (g, k)
+        if k >= tx * ty:
+            assert r["ntiles_shard"] == 0 and r["npix"] == 0 and r["in_image"] == 0, (g, k)
+            empty += 1
+    assert empty == 5                                      # B: 2, C, E and G: 1 each
+    for g in map(Geometry, sorted(GEOMETRIES)):            # the shards partition the image
+        every = sorted(p for k in range(g.shards) for p in shard.shard_pixels(g.w, g.h, k, g.shards, g.tw, g.th))
+        assert every == list(range(g.w * g.h)), g
+
+
+def test_plan_units_of_an_empty_shard(probe):
+    """npix == 0: the empty plan whatever the knobs say, and the budget is not asked (no division by npix)."""
+    envs = [{}, {"PT_WF_CHUNKS": 4}, {"PT_WF_CHUNKS": 4, "PT_WF_TAIL_NPIX": 37}, {"PT_WF_TAIL_CHUNKS": 1},
+            {"PT_WF_FIN_CHUNKS": 64, "PT_WF_FIN_PX": 5}]
+    cases = [(spp, e, head) for spp in (1, 9) for e in envs for head in (0, 1)]
+    got = probe(["plan"], [plan_line(0, spp, "inf", e, head=head) for spp, e, head in cases])
+    assert len(got) == len(cases)
+    for case, g in zip(cases, got):
+        assert g["rc"] == 0 and g["npix"] == 0 and g["budget_calls"] == 0, case
+        assert tuple(g[k] for k in PLAN_KEYS) == (0, 0, 0, 1, 1, 0, 1, 0, 0), case
+        assert g["wpc"] == 20 and 1 <= g["top_nodes"] <= 97, case
 
 
 def test_tile_grid_rejects_more_than_2_32_slots(probe):
