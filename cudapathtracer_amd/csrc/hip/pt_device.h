@@ -232,21 +232,45 @@ __device__ __forceinline__ float div_mk(float x, float d, float y)
     return (d == 0.0f) ? q0 : __builtin_fmaf(r, y, q0);
 }
 
-__device__ __forceinline__ bool coord_ok(float v)
+__host__ __device__ __forceinline__ bool coord_ok(float v)
 {
     const float a = __builtin_fabsf(v);
     return a == 0.0f || (a >= 0x1p-50f && a <= 0x1p20f);
 }
 
-__device__ __forceinline__ bool dir_ok(float v)
+__host__ __device__ __forceinline__ bool dir_ok(float v)
 {
     const float a = __builtin_fabsf(v);
     return a == 0.0f || (a >= 0x1p-100f && a <= 0x1p45f);
 }
 
-__device__ __forceinline__ bool ray_fast(V3 o, V3 d)
+__host__ __device__ __forceinline__ bool ray_fast(V3 o, V3 d)
 {
     return coord_ok(o.x) && coord_ok(o.y) && coord_ok(o.z) && dir_ok(d.x) && dir_ok(d.y) && dir_ok(d.z);
+}
+
+// The same predicates as mask arithmetic ('&' / '|' on int, no short circuit), for shade_lane: every term is a
+// compare without side effects, and as an '&&' / '||' chain the compiler keeps one exec-mask level per term, each
+// re-issuing the register copies of the walk state merged behind it.  Same truth tables
+// (tests/test_shade_predicates_host.py).
+// Two spellings on purpose: the chain forms above stay for every other user.  In render_head_wf the mask forms,
+// with equal truth tables, changed integrator 1's frames on the stand-in scene -- that kernel's result depends on
+// how the branch in its begin_trace is compiled (cause not found: DESIGN.md 6.4 and 10) -- so no kernel but
+// shade_lane's, whose frames were compared with the chain build value for value, is moved to them until that is
+// understood.
+__host__ __device__ __forceinline__ int coord_ok_m(float v)
+{
+    const float a = __builtin_fabsf(v);
+    return (int)(a == 0.0f) | ((int)(a >= 0x1p-50f) & (int)(a <= 0x1p20f));
+}
+__host__ __device__ __forceinline__ int dir_ok_m(float v)
+{
+    const float a = __builtin_fabsf(v);
+    return (int)(a == 0.0f) | ((int)(a >= 0x1p-100f) & (int)(a <= 0x1p45f));
+}
+__host__ __device__ __forceinline__ bool ray_fast_m(V3 o, V3 d)
+{
+    return (coord_ok_m(o.x) & coord_ok_m(o.y) & coord_ok_m(o.z) & dir_ok_m(d.x) & dir_ok_m(d.y) & dir_ok_m(d.z)) != 0;
 }
 
 // The culled walks (the BVH4 walk and trace_slow) skip boxes, so they equal the reference's walk only for

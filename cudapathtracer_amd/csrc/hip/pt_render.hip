@@ -1125,8 +1125,10 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
     auto begin_trace = [&](V3 o, V3 d, float bound) -> bool {
         wave_count(lcnt + 0, lane);
         SEC(SEC_BEGIN);
+        // (the wave-uniform tests first, as scalar branches; then one lane mask)
         if (a.num_tris == 0) { htri = -1; ht = kMaxFloat; state = ST_SHADE; return true; }   // spheres only
-        if (!((a.scene_fast != 0u) && ray_fast(o, d))) { state = ST_SLOW; return true; }
+        if (a.scene_fast == 0u) { state = ST_SLOW; return true; }
+        if (!ray_fast_m(o, d)) { state = ST_SLOW; return true; }
         if (!walk4_begin(w, o, d, a.acc_root, a.cull_abs)) {
             htri = -1; ht = kMaxFloat;
             state = (bound == kMaxFloat) ? ST_SHADE : ST_SLOW;
@@ -1432,8 +1434,9 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
             //    walk), so the walk starts with its bound at t_min instead of MAX_FLOAT.
             float bound = kMaxFloat;
             const uint32_t nem = lprobe[0];   // (the emitters are staged in the block's LDS)
-            if (i == D - 1 && nem != 0u && !(a.flags & PT_FLAG_NO_DEAD_PATH_SKIP) && !czero(wgt) &&
-                a.scene_fast != 0u && ray_fast(ro, rd)) {
+            // (the wave-uniform terms as one scalar test, the per-lane terms as one mask: no short circuit)
+            const bool probe_on = nem != 0u && !(a.flags & PT_FLAG_NO_DEAD_PATH_SKIP) && a.scene_fast != 0u;
+            if (probe_on && ((int)(i == D - 1) & (int)!czero(wgt) & (int)ray_fast_m(ro, rd)) != 0) {
                 SEC(SEC_PROBE);
                 float bt = kMaxFloat;
                 const float4* er = reinterpret_cast<const float4*>(lprobe + 4);

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Register budget check of the wavefront kernels (CPU only): compiles pt_render.hip for gfx950 with
-# extra flags ($*) and prints VGPRs / scratch / spills per wavefront kernel instance.
+# extra flags ($*) and prints VGPRs / scratch / spills / occupancy / LDS per wavefront kernel instance.
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=${RC_OUT:-/tmp/rc}
 mkdir -p $OUT
@@ -15,7 +15,7 @@ for l in open(sys.argv[1]):
     if m:
         cur = m.group(1); continue
     if cur and ("wf" in cur):
-        for key in ("VGPRs:", "ScratchSize", "VGPRs Spill", "Occupancy"):
-            if key in l:
-                print(cur[:60], l.split("remark:")[1].strip().split(" [")[0])
+        for key in ("VGPRs:", "ScratchSize", "VGPRs Spill", "Occupancy", "LDS Size"):
+            if key in l:   # (the value follows a unit in brackets: cut the trailing remark tag only)
+                print(cur[:60], l.split("remark:")[1].split(" [-Rpass")[0].strip())
 PY

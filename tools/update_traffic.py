@@ -68,8 +68,9 @@ if "GRBM_GUI_ACTIVE" in c:
         kind = "valu_issue"
         lim = ("VALU issue: the launch's VALU instructions, priced at the rate the kernel's own instruction streams "
                "issue at when replayed alone with no memory at 5 waves per SIMD (walk step %.2f, shading %.2f SIMD-"
-               "cycles per instruction; profiles/r06_valu, tools/valu_bound.py), take %s of its time -- the SIMDs "
-               "issue VALU in nearly every cycle and memory latency is hidden. Consistent with every round-6 "
+               "cycles per instruction; profiles/r06_valu, tools/valu_bound.py), take %s of its time -- VALU issue, "
+               "co-limited by the walk's L2 misses: a VALU cut returns between half and all of its price (DESIGN.md "
+               "6.3). Consistent with every round-6 "
                "experiment: removing 1-2 of the step's 10 loads at +3.7%%/+12%% VALU lost 3.9%%/7.0%% (r06_fold, "
                "r06_qnode); fewer L1 lookups or memory-side bytes bought nothing; fewer walk steps per ray always paid"
                % (vb["cycles_per_valu_walk_replay"], vb["cycles_per_valu_shading_replay"], "%.0f%%"))
@@ -79,7 +80,8 @@ if "GRBM_GUI_ACTIVE" in c:
         b["valu_issue_ms_per_launch"] = round(issue_ms, 3)
         b["valu_issue_frac_profiled"] = round(issue_ms / kms, 4) if kms else None
         b["valu_issue_method"] = ("SQ_INSTS_VALU / 1024 SIMDs x %.4f SIMD-cycles per instruction (the walk / shading blend "
-                                  "of the replayed streams, weighted as in the C3 launch) at 2.4 GHz" % vb["cycles_per_valu_blend"])
+                                  "of the replayed streams, weighted as in the C3 launch) at 2.4 GHz; the replay rates are those of "
+                                  "profiles/r06_valu, not re-measured on this source's streams" % vb["cycles_per_valu_blend"])
         b["limiter_detail"] = lim.replace("%.0f%%", "%.0f%%" % (100 * issue_ms / kms) if kms else "most")
     if "SQ_INSTS_VALU" in c:
         # wave64 VALU instructions per SIMD-cycle; measured ceiling ~0.25-0.3 for this kernel's mix (most
