@@ -125,6 +125,16 @@ class AdaptiveResult(C.Structure):
                 ("active", C.c_uint64), ("samples_total", C.c_uint64)]
 
 
+PT_SESSION_COUNTS, PT_SESSION_NOISE, PT_SESSION_NOISE_PER_PIXEL = 0x1, 0x2, 0x4   # pt_session_info.flags
+
+
+class SessionInfo(C.Structure):   # pt_session_info, 136 B
+    _fields_ = [("params", Params), ("cam", Camera), ("samples", C.c_int64), ("scene_digest", C.c_uint64),
+                ("flags", C.c_uint32), ("noise_batches", C.c_int32), ("noise_n0", C.c_int64), ("noise_W", C.c_double),
+                ("frozen_pixels", C.c_uint64)]
+
+
+assert C.sizeof(SessionInfo) == 136
 assert C.sizeof(Feature) == 48 and C.sizeof(DenoiseGuidedParams) == 24
 assert C.sizeof(NoiseSummary) == 32 + 64 * 8 and C.sizeof(ConvergeParams) == 24
 assert C.sizeof(Vec3) == 12 and C.sizeof(Triangle) == 28 and C.sizeof(Material) == 48
@@ -200,6 +210,10 @@ SIGNATURES = {
                                   C.POINTER(C.c_uint64)]),
     "pt_accum_add_adaptive": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ConvergeParams), C.c_void_p, C.c_void_p,
                                         C.POINTER(AdaptiveResult)]),
+    "pt_session_save": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p]),
+    "pt_session_load": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                  C.POINTER(C.c_int)]),
+    "pt_session_file_info": (C.c_int, [C.c_char_p, C.POINTER(SessionInfo)]),
     "pt_denoise_defaults": (None, [C.POINTER(DenoiseParams)]),
     "pt_render_features_device": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.c_void_p, C.c_void_p]),
     "pt_render_features": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.c_void_p]),

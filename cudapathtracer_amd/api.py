@@ -331,6 +331,18 @@ class Renderer:
             L.check(err.value if err.value != 0 else L.PT_E_IO)
         return Accumulator(self, h, accum_file_info(path)["params"])
 
+    def load_session(self, path, noise=True):
+        """(Accumulator, NoiseEstimate or None): the progressive state a session file holds (pt_session_load), on
+        this renderer.  The estimator continues the saved window; None when the file has none.  noise=False skips
+        the file's estimator: Accumulator.noise() then opens a fresh window.  PtError PT_E_SCENE for another scene."""
+        acc, est, has = C.c_void_p(None), C.c_void_p(None), C.c_int(0)
+        L.check(L.lib().pt_session_load(self._h, str(path).encode(), C.byref(acc), C.byref(est) if noise else None,
+                                        C.byref(has)))
+        a = Accumulator(self, acc.value, session_file_info(path)["params"])
+        if est.value:
+            a._noise = NoiseEstimate(a, est.value)
+        return a, a._noise
+
     def features(self, cam, width, height, pixel_order=0, shard_index=0, shard_count=1, tile=0):
         """Primary-hit feature buffers (pt_render_features): a FEATURE structured array of shape (H, W) -- (W*H,)
         in Morton order -- with albedo, depth, normal, prim and position of each pixel's pinhole camera ray.
@@ -483,6 +495,16 @@ def accum_file_info(path):
     return dict(params=p, camera=cam, samples=int(n.value), scene_digest=int(dg.value))
 
 
+def session_file_info(path):
+    """Header of a session file (pt_session_file_info, host-only): dict of params (spp = 0), camera, samples, the
+    scene digest, flags (PT_SESSION_*), the estimator's noise_n0 / noise_W / noise_batches and frozen_pixels."""
+    i = L.SessionInfo()
+    L.check(L.lib().pt_session_file_info(str(path).encode(), C.byref(i)))
+    return dict(params=i.params, camera=i.cam, samples=int(i.samples), scene_digest=int(i.scene_digest), flags=int(i.flags),
+                noise_n0=int(i.noise_n0), noise_W=float(i.noise_W), noise_batches=int(i.noise_batches),
+                frozen_pixels=int(i.frozen_pixels))
+
+
 class Accumulator:
     """Per-pixel XORWOW state and f64 running mean of one shard, kept on the renderer's device between
     passes (the reference's randState_device / imgBuffer_device, kernel.cu:527-553): a render built up
@@ -543,6 +565,11 @@ class Accumulator:
 
     def save(self, path):
         L.check(L.lib().pt_accum_save(self._h, str(path).encode()))
+
+    def save_session(self, path, noise=None):
+        """Write the whole progressive state to a session file (pt_session_save): the accumulator, the frozen pixels'
+        counts and, with noise = this accumulator's live NoiseEstimate, the estimator and its window."""
+        L.check(L.lib().pt_session_save(self._h, None if noise is None else noise._h, str(path).encode()))
 
     def noise(self):
         """Attach a noise estimator (pt_noise_create): its window starts at the samples done so far.  One live

@@ -21,20 +21,27 @@
 // --resume FILE                           continue the render FILE holds: every fixed parameter and the
 //                                         camera come from the file, --spp is the samples to ADD; an
 //                                         option that contradicts the file is an error
+// --session FILE                          as --checkpoint, but a session file (pt_session_save): the accumulator, the
+//                                         frozen pixels' counts and the noise estimator with its window; allowed with
+//                                         --until-error and --adaptive
+// --resume-session FILE                   continue the render a session file holds, as --resume does a checkpoint; the
+//                                         estimator continues the saved window when the file has one, so a resumed
+//                                         --until-error / --adaptive run equals the uninterrupted one
 // --pass-spp K                            render in passes of K samples (the reference's progressive
 //                                         loop, kernel.cu:709-736), rewriting --out / --pfm /
-//                                         --checkpoint after each and printing its "sample %d" line
+//                                         --checkpoint / --session after each and printing its "sample %d" line
 // --until-error TOL                       with --pass-spp K: attach a noise estimator (pt_noise_*) and stop as soon as
 //   [--error-quantile Q] [--min-batches B]  the fraction Q (default 0.95) of the pixels has a relative standard error
 //                                         of its mean luminance <= TOL, after at least B (default 2) passes; --spp
-//                                         (with --resume: the samples done plus --spp) is the cap.  A resumed render
-//                                         starts a fresh estimator window at the resumed state
+//                                         (with --resume / --resume-session: the samples done plus --spp) is the cap.
+//                                         After --resume a fresh estimator window starts at the resumed state; after
+//                                         --resume-session the saved window continues
 // --error-map FILE.pfm                    with --pass-spp K: write the squared relative standard error of every
 //                                         pixel ((float)rel2 of pt_noise_map) as a grey PFM
 // --adaptive                              with --until-error: freeze every pixel once its error is <= TOL (after at least
 //                                         B passes) and sample only the others from then on (pt_noise_freeze; the
 //                                         loop of pt_accum_add_adaptive).  Not with --checkpoint: format version 1
-//                                         holds a single sample count
+//                                         holds a single sample count (--session holds them all)
 // --count-map FILE.pfm                    with --pass-spp K: write every pixel's sample count (pt_accum_counts) as a
 //                                         grey PFM
 // --denoise [ITERS]                       filter the image with the edge-avoiding a-trous denoiser (pt_denoise,
@@ -79,6 +86,7 @@ struct Obj {
             "              [--radius R] [--gpus N] [--out image.ppm] [--pfm image.pfm] [--quiet]\n"
             "              [--tri-counts out.csv [--reference-walk]] [--morton] [--tile WxH]\n"
             "              [--checkpoint FILE] [--resume FILE] [--pass-spp K]\n"
+            "              [--session FILE] [--resume-session FILE]\n"
             "              [--denoise [ITERS]] [--aov PREFIX]\n"
             "              [--until-error TOL [--error-quantile Q] [--min-batches B] [--adaptive]] [--error-map FILE.pfm]\n"
             "              [--count-map FILE.pfm] [--denoise-guided [ITERS] [--sigma-luma S]] [--variance-map FILE.pfm]\n"
@@ -91,6 +99,8 @@ struct Obj {
             "  --denoise-guided [ITERS]  with --until-error: filter the final image guided by the estimator's variance map\n"
             "  --sigma-luma S     the guided filter's luminance tolerance in standard errors (default 2)\n"
             "  --variance-map FILE  with --pass-spp: write the variance of every pixel's mean luminance as a grey PFM\n"
+            "  --session FILE     write the whole progressive state (accumulator, frozen pixels, estimator) after each pass\n"
+            "  --resume-session FILE  continue the render FILE holds; its estimator window continues; --spp is the samples to add\n"
             "  --aov PREFIX       write PREFIX_albedo.pfm, PREFIX_normal.pfm, PREFIX_position.pfm, PREFIX_depth.pfm\n");
     exit(2);
 }
@@ -138,7 +148,7 @@ int main(int argc, char** argv)
     pt_camera cam{{0, 1, 3}, 1, 3, 0, 0, 0};                      // kernel.cu:642-648
     int gpus = 1;
     bool quiet = false, ref_walk = false;
-    std::string tri_csv, checkpoint, resume;
+    std::string tri_csv, checkpoint, resume, session, resume_session;
     int pass_spp = 0;
     bool denoise = false;
     pt_denoise_params dparams;
@@ -190,6 +200,8 @@ int main(int argc, char** argv)
         }
         else if (a == "--checkpoint") checkpoint = next();
         else if (a == "--resume") resume = next();
+        else if (a == "--session") session = next();
+        else if (a == "--resume-session") resume_session = next();
         else if (a == "--pass-spp") { pass_spp = atoi(next().c_str()); if (pass_spp < 1) usage("--pass-spp must be >= 1"); }
         else if (a == "--denoise") {
             denoise = true;
@@ -234,19 +246,28 @@ int main(int argc, char** argv)
     if (adaptive && !until_error) usage("--adaptive needs --until-error TOL (the tolerance pixels are frozen at)");
     if (adaptive && !checkpoint.empty()) usage("--adaptive cannot write a --checkpoint (format version 1 holds a single sample count)");
     if (!count_map.empty() && pass_spp < 1) usage("--count-map needs --pass-spp K");
-    const bool accumulate = !checkpoint.empty() || !resume.empty() || pass_spp > 0;
-    if (accumulate && gpus != 1) usage("--checkpoint / --resume / --pass-spp need --gpus 1 (one accumulator per shard)");
+    if (!resume.empty() && !resume_session.empty()) usage("--resume and --resume-session: choose one");
+    const bool accumulate = !checkpoint.empty() || !resume.empty() || !session.empty() || !resume_session.empty() || pass_spp > 0;
+    if (accumulate && gpus != 1)
+        usage("--checkpoint / --resume / --session / --resume-session / --pass-spp need --gpus 1 (one accumulator per shard)");
     if (accumulate && (!tri_csv.empty() || ref_walk)) usage("--tri-counts and --reference-walk do not accumulate");
-    if (!resume.empty()) {
+    const std::string& resumed = resume.empty() ? resume_session : resume;   // the file a render continues, if any
+    if (!resumed.empty()) {
         // the file fixes the render; what the command line says as well must say the same
         pt_params fp;
         pt_camera fc;
         int64_t done = 0;
-        if (pt_accum_file_info(resume.c_str(), &fp, &fc, &done, nullptr) != PT_OK) return die("--resume");
+        if (!resume.empty()) {
+            if (pt_accum_file_info(resume.c_str(), &fp, &fc, &done, nullptr) != PT_OK) return die("--resume");
+        } else {
+            pt_session_info si;
+            if (pt_session_file_info(resume_session.c_str(), &si) != PT_OK) return die("--resume-session");
+            fp = si.params; fc = si.cam; done = si.samples;
+        }
         auto has = [&](const char* o) { for (const std::string& g : given) if (g == o) return true; return false; };
         auto conflict = [&](const char* o, bool differs) {
             if (has(o) && differs) {
-                fprintf(stderr, "pt_cli: %s contradicts the resumed file %s\n", o, resume.c_str());
+                fprintf(stderr, "pt_cli: %s contradicts the resumed file %s\n", o, resumed.c_str());
                 exit(2);
             }
         };
@@ -265,7 +286,7 @@ int main(int argc, char** argv)
         p = fp;
         p.spp = add;
         cam = fc;
-        if (!quiet) printf("resuming %s: %dx%d, %lld samples done, adding %d\n", resume.c_str(), p.width, p.height, (long long)done, add);
+        if (!quiet) printf("resuming %s: %dx%d, %lld samples done, adding %d\n", resumed.c_str(), p.width, p.height, (long long)done, add);
     }
 
     const auto t0 = std::chrono::steady_clock::now();
@@ -339,14 +360,24 @@ int main(int argc, char** argv)
     if (accumulate) {
         // the reference's progressive loop (kernel.cu:709-736) as passes of an accumulator
         int err = 0;
-        pt_accum* acc = resume.empty() ? pt_accum_create(ctx[0], &p, &cam, &err) : pt_accum_load(ctx[0], resume.c_str(), &err);
-        if (!acc) return die(resume.empty() ? "pt_accum_create" : "--resume");
-        const int step = pass_spp > 0 ? pass_spp : (p.spp > 0 ? p.spp : 1);
+        pt_accum* acc = nullptr;
         pt_noise* noise = nullptr;
-        if (estimate) {
+        if (!resume_session.empty()) {
+            // the estimator of the file continues its window (it is skipped when this run estimates nothing)
+            if (pt_session_load(ctx[0], resume_session.c_str(), &acc, estimate ? &noise : nullptr, nullptr) != PT_OK)
+                return die("--resume-session");
+            if (noise && !quiet)
+                printf("noise estimate: the window saved in %s continues (%lld samples)\n", resume_session.c_str(),
+                       (long long)pt_accum_samples(acc));
+        } else {
+            acc = resume.empty() ? pt_accum_create(ctx[0], &p, &cam, &err) : pt_accum_load(ctx[0], resume.c_str(), &err);
+            if (!acc) return die(resume.empty() ? "pt_accum_create" : "--resume");
+        }
+        const int step = pass_spp > 0 ? pass_spp : (p.spp > 0 ? p.spp : 1);
+        if (estimate && !noise) {
             noise = pt_noise_create(acc, &err);
             if (!noise) return die("pt_noise_create");
-            if (!resume.empty() && !quiet)
+            if (!resumed.empty() && !quiet)
                 printf("noise estimate: a fresh window starts at the resumed state (%lld samples)\n", (long long)pt_accum_samples(acc));
         }
         bool converged = false;
@@ -378,10 +409,12 @@ int main(int argc, char** argv)
                 if (pt_accum_read(acc, img.data(), nullptr) != PT_OK) return die("pt_accum_read");
                 if (const char* what = write_images()) return die(what);
                 if (!checkpoint.empty() && pt_accum_save(acc, checkpoint.c_str()) != PT_OK) return die("--checkpoint");
+                if (!session.empty() && pt_session_save(acc, noise, session.c_str()) != PT_OK) return die("--session");
             }
         }
         if (pt_accum_read(acc, img.data(), nullptr) != PT_OK) return die("pt_accum_read");
         if (!checkpoint.empty() && pt_accum_save(acc, checkpoint.c_str()) != PT_OK) return die("--checkpoint");
+        if (!session.empty() && pt_session_save(acc, noise, session.c_str()) != PT_OK) return die("--session");
         if (until_error)   // (printed with --quiet too: it is the run's result)
             printf("stopped at %lld samples: %s\n", (long long)pt_accum_samples(acc),
                    converged ? "converged" : "not converged (the sample cap)");

@@ -108,6 +108,7 @@ struct pt_accum {
     bool any_frozen = false;          // a pixel was frozen: passes run over the list from now on
     bool list_valid = false;
     uint32_t nactive = 0;             // entries of d_list (list_valid)
+    uint32_t* d_slot_pix = nullptr;   // slot_pix on the device, uploaded when a session file first needs it (pt_session.hip)
     size_t slots() const { return slot_pix.size(); }
 };
 
@@ -184,6 +185,37 @@ void pt::accum_frozen(pt_accum* a, uint64_t newly_frozen)
     if (!newly_frozen) return;
     a->any_frozen = true;
     a->list_valid = false;
+}
+
+namespace {
+pt_accum* make_accum(pt_ctx* c, const pt_params* p, const pt_camera* cam, int* code);
+}
+
+int pt::accum_session(pt_accum* a, pt::SessionAccum* out)
+{
+    if (!a->d_slot_pix) {
+        const size_t n = a->slots() ? a->slots() : 1;
+        ACC_HIP(hipSetDevice(pt::ctx_device(a->ctx)));
+        ACC_HIP(hipMalloc(reinterpret_cast<void**>(&a->d_slot_pix), n * sizeof(uint32_t)));
+        if (a->slots()) ACC_HIP(hipMemcpy(a->d_slot_pix, a->slot_pix.data(), a->slots() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    *out = pt::SessionAccum{a->ctx, &a->params, &a->cam, a->samples, a->slots(), a->pixels, a->d_rng, a->d_mean,
+                            a->any_frozen ? a->d_frozen_at : nullptr, a->d_slot_pix, a->noise};
+    return PT_OK;
+}
+
+pt_accum* pt::accum_session_new(pt_ctx* c, const pt_params* p, const pt_camera* cam, int64_t samples, bool counts, int* code)
+{
+    pt_accum* a = make_accum(c, p, cam, code);
+    if (!a) return nullptr;
+    a->samples = samples;
+    if (counts) {
+        *code = adaptive_alloc(a);
+        if (*code != PT_OK) { pt_accum_destroy(a); return nullptr; }
+        a->any_frozen = true;
+        a->list_valid = false;
+    }
+    return a;
 }
 
 namespace {
@@ -455,8 +487,10 @@ int pt_accum_save(pt_accum* acc, const char* path)
                 return pt::fail(PT_E_INVALID, "pt_accum_save: the pixels' sample counts differ (frozen pixels stopped before %lld); "
                                 "checkpoint format version 1 holds a single sample count", (long long)acc->samples);
     }
+    pt::StageTimer timer{"pt_accum_save"};
     std::vector<Record> rec;
     if (int rc = fetch_records(acc, &rec)) return rc;
+    timer.lap("state to host");
     Header h;
     memset(&h, 0, sizeof(h));
     memcpy(h.magic, kMagic, 8);
@@ -470,6 +504,7 @@ int pt_accum_save(pt_accum* acc, const char* path)
     if (!f) return pt::fail(PT_E_IO, "pt_accum_save: cannot open %s for writing", path);
     const bool ok = fwrite(&h, 1, sizeof(h), f) == sizeof(h) && fwrite(rec.data(), sizeof(Record), rec.size(), f) == rec.size();
     if (fclose(f) != 0 || !ok) return pt::fail(PT_E_IO, "pt_accum_save: short write to %s", path);
+    timer.lap("file write");
     return PT_OK;
 }
 
@@ -478,6 +513,7 @@ pt_accum* pt_accum_load(pt_ctx* ctx, const char* path, int* err)
     pt::clear_error();
     auto bail = [&](int code) -> pt_accum* { if (err) *err = code; return nullptr; };
     if (!ctx || !path) return bail(pt::fail(PT_E_INVALID, "pt_accum_load: null argument"));
+    pt::StageTimer timer{"pt_accum_load"};
     Header h;
     FILE* f = nullptr;
     if (int rc = read_header("pt_accum_load", path, &h, &f)) return bail(rc);
@@ -485,6 +521,7 @@ pt_accum* pt_accum_load(pt_ctx* ctx, const char* path, int* err)
     const bool got = fread(rec.data(), sizeof(Record), rec.size(), f) == rec.size();
     fclose(f);
     if (!got) return bail(pt::fail(PT_E_IO, "pt_accum_load: cannot read the records of %s", path));
+    timer.lap("file read");
     uint64_t digest;
     uint32_t nt, ns;
     pt::ctx_scene_id(ctx, &digest, &nt, &ns);
@@ -512,6 +549,7 @@ pt_accum* pt_accum_load(pt_ctx* ctx, const char* path, int* err)
     };
     if (int rc = upload()) { pt_accum_destroy(a); return bail(rc); }
     a->samples = h.samples;
+    timer.lap("host to state");
     if (err) *err = PT_OK;
     return a;
 }
@@ -538,6 +576,7 @@ void pt_accum_destroy(pt_accum* acc)
     if (acc->d_frozen_at) (void)hipFree(acc->d_frozen_at);
     if (acc->d_list) (void)hipFree(acc->d_list);
     if (acc->d_scan) (void)hipFree(acc->d_scan);
+    if (acc->d_slot_pix) (void)hipFree(acc->d_slot_pix);
     delete acc;
 }
 

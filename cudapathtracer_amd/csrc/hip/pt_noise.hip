@@ -342,6 +342,32 @@ int follow_accum(pt_noise* z, hipStream_t stream)
 
 }  // namespace
 
+// ---- session files (pt_session.cpp): the estimator's window as it stands, and an estimator that continues one
+void pt::noise_session(pt_noise* z, pt::SessionNoise* out)
+{
+    *out = pt::SessionNoise{z->d_state, z->pix_live ? z->d_pix : nullptr, z->n0, z->W, z->batches};
+}
+
+pt_noise* pt::noise_session_new(pt_accum* acc, int64_t n0, double W, int32_t batches, bool per_pixel, int* code)
+{
+    pt_noise* z = pt_noise_create(acc, code);
+    if (!z) return nullptr;
+    z->n0 = n0;
+    z->W = W;
+    z->batches = batches;
+    if (per_pixel) {
+        const size_t n = z->slots() ? z->slots() : 1;
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&z->d_pix), 2 * n * sizeof(uint32_t));
+        if (e != hipSuccess) {
+            *code = pt::fail(PT_E_HIP, "pt_session_load: hipMalloc of the W_q / b_q planes failed: %s", hipGetErrorString(e));
+            pt_noise_destroy(z);
+            return nullptr;
+        }
+        z->pix_live = true;
+    }
+    return z;
+}
+
 extern "C" {
 
 void pt_noise_defaults(pt_noise_params* p)

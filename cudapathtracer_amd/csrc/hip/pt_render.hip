@@ -2689,6 +2689,7 @@ struct pt_ctx : pt::SceneInfo {            // (the scene's scalars: pt_scene_pac
     Bufs rb[kFlights];
     int fl_head = 0, fl_n = 0;                 // oldest in-flight slot, number in flight
     pt::DenoiseScratch denoise;       // pt_denoise*'s device scratch (pt_denoise.hip), grown on demand
+    pt::SessionScratch session;       // pt_session_save / _load's staging (pt_session.cpp), grown on demand
 };
 
 int pt::ctx_device(const pt_ctx* c) { return c->device; }
@@ -2784,9 +2785,10 @@ void pt_destroy(pt_ctx* c)
     void* bufs[] = {c->nodes, c->rnodes, c->tris_leaf, c->tris_orig, c->shade, c->mats,
                     c->lights, c->jump, c->jump_bytes, c->shade_m, c->scratch_out,
                     c->nodes4, c->acc_tris, c->rparent, c->hrec,
-                    c->tone_thr, c->spheres, c->tri_counts, c->emis, c->denoise.mem};
+                    c->tone_thr, c->spheres, c->tri_counts, c->emis, c->denoise.mem, c->session.dev};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
+    pt::free_pinned(c->session.host);
     for (pt_ctx::Bufs& B : c->rb)
         for (void* b : {(void*)B.spill, (void*)B.pix_states, (void*)B.lbuf, (void*)B.pmemo, (void*)B.counters,
                         (void*)B.pixel_counter, (void*)B.tile_counter, (void*)B.seed_states})
@@ -3236,6 +3238,7 @@ void pt::ctx_scene_id(const pt_ctx* c, uint64_t* digest, uint32_t* num_tris, uin
 }
 int pt::ctx_in_flight(const pt_ctx* c) { return c->fl_n; }
 pt::DenoiseScratch* pt::ctx_denoise_scratch(pt_ctx* c) { return &c->denoise; }
+pt::SessionScratch* pt::ctx_session_scratch(pt_ctx* c) { return &c->session; }
 int pt::ctx_num_cus(const pt_ctx* c) { return c->num_cus; }
 uint32_t pt::accum_max_samples() { return kAccumMaxSamples; }
 

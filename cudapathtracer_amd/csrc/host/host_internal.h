@@ -1,8 +1,11 @@
 // host_internal.h -- shared declarations of the host surface (plain C++17, no HIP).
 #pragma once
 
+#include <chrono>
 #include <cstdarg>
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -93,6 +96,89 @@ struct DenoiseScratch {
 };
 DenoiseScratch* ctx_denoise_scratch(pt_ctx* c);
 int ctx_num_cus(const pt_ctx* c);
+
+// PT_TIMING=1: the host wall time of each stage of a checkpoint / session save or load on stderr, "who: stage ms"
+// (every stage ends in a blocking call; the measurements of DESIGN.md 8).
+struct StageTimer {
+    const char* who;
+    bool on = getenv("PT_TIMING") != nullptr;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    void lap(const char* what)
+    {
+        if (!on) return;
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "%s: %-18s %9.3f ms\n", who, what, std::chrono::duration<double, std::milli>(now - t0).count());
+        t0 = now;
+    }
+};
+
+// ---- session files (pt_session.cpp: the pt_session_* entry points and the file; pt_session.hip: the pack / unpack
+// kernels).  What they need of an accumulator (pt_accum.cpp), an estimator (pt_noise.hip) and the context.
+struct SessionAccum {
+    pt_ctx* ctx;
+    const pt_params* params;
+    const pt_camera* cam;
+    int64_t samples;
+    size_t slots;
+    uint64_t pixels;               // work slots inside the image
+    uint32_t* rng;                 // device, rng[k * slots + q]
+    double* mean;                  // device, mean[k * slots + q]
+    uint32_t* frozen_at;           // device; null unless a pixel was ever frozen
+    const uint32_t* slot_pix;      // device: work slot -> scanline pixel id, 0xffffffff outside the image
+    pt_noise* noise;               // the live estimator, or null
+};
+// (uploads the slot -> pixel map on first use)
+int accum_session(pt_accum* acc, SessionAccum* out);
+// A new accumulator at `samples` whose planes session_unpack fills; counts: with the frozen_at plane, in the state
+// pt_accum_freeze leaves (a pixel is frozen, the active list invalid).  Null with *code set on failure.
+pt_accum* accum_session_new(pt_ctx* c, const pt_params* p, const pt_camera* cam, int64_t samples, bool counts, int* code);
+struct SessionNoise {
+    double* state;                 // device: prev[3], mu, m2 planes of slots doubles
+    uint32_t* pix;                 // device: W_q, b_q planes of slots words; null unless they carry the state
+    int64_t n0;
+    double W;
+    int32_t batches;
+};
+void noise_session(pt_noise* noise, SessionNoise* out);
+// A new estimator attached to `acc` with the given window (not a fresh one) whose planes session_unpack fills;
+// per_pixel: with live W_q / b_q planes.
+pt_noise* noise_session_new(pt_accum* acc, int64_t n0, double W, int32_t batches, bool per_pixel, int* code);
+// The staging of a session save / load: one device buffer and its pinned host twin, `bytes` each, grown on demand
+// inside the context and freed by pt_destroy.
+struct SessionScratch {
+    void* dev = nullptr;
+    void* host = nullptr;
+    size_t bytes = 0;
+};
+SessionScratch* ctx_session_scratch(pt_ctx* c);
+// Where a staging buffer holds what: the frozen / illegal counters first, then each section of the file at a
+// 256-byte boundary (a section's offset is 0 when the file has none).
+constexpr int kSessionSumCopies = 32;    // copies of the counters; block b adds into copy b % kSessionSumCopies
+constexpr int kSessionSumWords = 2;      // frozen pixels, illegal section-B words
+struct SessionLayout {
+    size_t a = 0, b = 0, c = 0, d = 0;   // byte offsets of sections A..D
+    size_t bytes = 0;
+};
+constexpr size_t kSessionSumBytes = (size_t)kSessionSumCopies * kSessionSumWords * sizeof(unsigned long long);
+// The planes a kernel packs from / unpacks into (null: the file has no such section) and the staging.
+struct SessionPlanes {
+    uint32_t* rng;
+    double* mean;
+    uint32_t* frozen_at;
+    double* nstate;
+    uint32_t* npix;
+    const uint32_t* slot_pix;
+    unsigned char* stage;          // device staging, laid out by `at`
+    SessionLayout at;
+    size_t slots;
+    size_t image_pixels;           // W*H
+    uint32_t samples;
+};
+// Enqueue on `stream` (nothing is launched for 0 slots).  session_pack: the planes into the staging's sections, and
+// the frozen pixels into its counters.  session_unpack: the sections into the planes, slots outside the image as
+// a new accumulator / estimator has them, and the frozen pixels and illegal section-B words into the counters.
+int session_pack(pt_ctx* c, const SessionPlanes& pl, void* stream);
+int session_unpack(pt_ctx* c, const SessionPlanes& pl, void* stream);
 
 // ---- OBJ/MTL ingest with tinyobj 0.9.13 semantics (tiny_obj_loader.cc) ------------------
 // Only what loadOBJ (modelLoader.h:125-210) consumes is kept: positions, per-triangle

@@ -20,6 +20,8 @@
  *                           accumulator from batch means, and a loop that adds passes until the image converged
  *        pt_accum_freeze / pt_noise_freeze / pt_accum_add_adaptive  (no counterpart) adaptive sampling: converged
  *                           pixels are frozen and the passes sample only the rest
+ *        pt_session_*    (no counterpart) the whole progressive state -- accumulator, frozen-at counts, estimator -- in
+ *                           one file: an adaptive render resumes in another process as if it had never stopped
  *        pt_render_features / pt_denoise  (no counterpart in the reference) per-pixel first-hit feature
  *                           buffers and an edge-avoiding a-trous filter: a preview from a few samples per pixel
  *        pt_noise_variance / pt_denoise_guided  (no counterpart) the estimator's variance map and an a-trous filter
@@ -200,6 +202,9 @@ typedef struct {
  *   pt_accum_add_until         stops with stopped_converged = 1 after exactly min_batches passes: 0 >= ceil(quantile * 0)
  *   pt_accum_add_adaptive      no pixel is active: no pass, stopped_converged = 1, active = samples_total = 0,
  *                              pt_accum_samples unchanged
+ *   pt_session_save            the header (flags without PT_SESSION_COUNTS: no pixel can be frozen; frozen pixels 0) plus
+ *                              all-zero sections: A, and C when an estimator is saved
+ *   pt_session_load            loads such a file back as such an accumulator (and estimator)
  * and the next render on the context is unaffected. */
 
 typedef struct {
@@ -432,7 +437,8 @@ int pt_accum_add_until(pt_accum* acc, pt_noise* noise, const pt_converge_params*
  *                  frozen pixels keep what the buffer held.  With no active pixel: a no-op (zero stats,
  *                  pt_accum_samples unchanged).
  * pt_accum_read    unchanged: every pixel's mean, at its own count.
- * pt_accum_save    with unequal counts PT_E_INVALID: format version 1 holds a single sample count.
+ * pt_accum_save    with unequal counts PT_E_INVALID: format version 1 holds a single sample count (a session file,
+ *                  pt_session_save below, holds them all).
  *
  * The estimator with per-pixel counts.  Once the accumulator has a frozen pixel, each pixel q carries its
  * own window weight W_q and batch count b_q (two uint32 planes, allocated then, both starting from the
@@ -477,6 +483,103 @@ int pt_accum_active(pt_accum* acc, uint32_t* out, uint32_t cap, uint64_t* n_out)
 int pt_noise_freeze(pt_noise* noise, const pt_noise_params* np, void* stream, uint64_t* newly_frozen, uint64_t* active);
 int pt_accum_add_adaptive(pt_accum* acc, pt_noise* noise, const pt_converge_params* cp, float* d_out, void* stream,
                           pt_adaptive_result* result);
+
+/* ------------------------------------------------- session files: checkpoint and resume adaptive renders
+ * The checkpoint file of pt_accum_save (format version 1) holds the accumulator alone, at a single sample count.  A
+ * SESSION FILE holds the whole progressive state of one shard: the accumulator, the per-pixel frozen-at counts of
+ * adaptive sampling and, optionally, the attached noise estimator with its window -- so an adaptive or until-error
+ * render that is saved, destroyed and loaded again (in another process, on another context of the same scene)
+ * continues exactly as if it had never stopped: every later image, count, active list, estimator state, summary,
+ * error map and variance map agrees in every byte.  pt_accum_save / _load / _file_info and format version 1 are
+ * unchanged, including their refusals.
+ *
+ * Session file (pt_session_save / pt_session_load / pt_session_file_info), little-endian; the magic is format 1's,
+ * so a reader of format 1 answers "format version 2, this build reads 1":
+ *   offset  0  char[8]   magic "PTACCUM\0"
+ *           8  uint32    format version (2)
+ *          12  uint32    header size in bytes (192)
+ *          16  pt_params 56 B (seed at +24; spp = 0; 4 bytes of zero padding last)      \
+ *          72  pt_camera 32 B                                                            |
+ *         104  int64     samples done (pt_accum_samples: the active pixels' count)      |  exactly format 1's
+ *         112  uint64    FNV-1a digest of the scene arrays, as in format 1              |  fields
+ *         120  uint32    num_tris                                                        |
+ *         124  uint32    num_spheres                                                    /
+ *         128  uint32    flags: PT_SESSION_COUNTS 0x1 (a pixel was ever frozen: section B), PT_SESSION_NOISE 0x2 (an
+ *                        estimator: section C), PT_SESSION_NOISE_PER_PIXEL 0x4 (its W_q / b_q planes carry the state:
+ *                        section D; only with 0x2); every other bit 0
+ *         132  uint32    0
+ *         136  int64     noise n0       the sample count at the estimator's last fold   \
+ *         144  f64       noise W        its window weight                               |  0 without PT_SESSION_NOISE
+ *         152  int32     noise batches  the passes it has folded                        /
+ *         156  uint32    0
+ *         160  uint64    frozen pixels of this shard (0 without PT_SESSION_COUNTS)
+ *         168  24 bytes of zero
+ *         192  the sections, in this order, each W*H entries in scanline order (pixel (x,y) at y*W + x), pixels
+ *              outside the shard all zero:
+ *                A  always                       48 B  format 1's record: six uint32 (XORWOW v0..v4, d) and three f64
+ *                                                      (the mean r, g, b); all zero at 0 samples
+ *                B  PT_SESSION_COUNTS             4 B  uint32: 0xffffffff = the pixel is active (its count is `samples`),
+ *                                                      else the count the pixel was frozen at
+ *                C  PT_SESSION_NOISE             40 B  five f64: the estimator's prev r, g, b, mu, m2
+ *                D  PT_SESSION_NOISE_PER_PIXEL    8 B  two uint32: W_q, b_q
+ * With no pixel ever frozen and no estimator (flags 0), section A is byte for byte the records pt_accum_save writes
+ * for the same accumulator.
+ *
+ * pt_session_save writes `acc` and, when `noise` is not NULL, its estimator.  Blocking.  The sections are laid out
+ * on the device (pt_session.hip: one pack kernel over the state planes) and leave it in one copy through a pinned
+ * staging buffer, which grows on demand inside the context and is freed by pt_destroy.  PT_E_INVALID: a null acc or
+ * path, a `noise` that is not acc's live estimator, asynchronous renders in flight; PT_E_IO: the file cannot be
+ * written.  Legal at any moment between two calls: between pt_accum_add and pt_noise_update the estimator's n0 and
+ * prev are saved as they stand, and the next update after a load folds what the uninterrupted run would fold;
+ * legal at 0 samples, with or without pixels frozen at 0.  Section D is written when the estimator's per-pixel
+ * planes are live (after its first call on an accumulator with a frozen pixel); before that the scalars W and batches
+ * describe every pixel, as they do after the load.
+ *
+ * pt_session_load creates the accumulator on `ctx` (*acc_out; every fixed parameter and the camera come from the
+ * file) and, when the file has an estimator and noise_out is not NULL, an estimator attached to it (*noise_out) with
+ * batches, W, n0, the five f64 planes and the W_q / b_q planes as saved: it continues the saved window, it does not
+ * open a fresh one.  *has_noise (may be NULL) says whether the file has an estimator.  With noise_out = NULL the
+ * estimator's sections are skipped and pt_noise_create on the accumulator opens a fresh window as always.  After a
+ * load with PT_SESSION_COUNTS the accumulator is in the state pt_accum_freeze leaves: the active list is rebuilt on
+ * first use.  Destroy the estimator before the accumulator, as any other.  On failure both outputs are NULL and
+ * nothing stays allocated:
+ *   PT_E_IO       an unreadable or truncated file
+ *   PT_E_INVALID  null ctx, path or acc_out; asynchronous renders in flight; a wrong magic, version or header size;
+ *                 unknown flag bits; 0x4 without 0x2; 0x4 without 0x1 (the per-pixel planes exist only beside frozen
+ *                 pixels: pt_session_save never writes one without the other); noise batches < 0; noise n0 outside
+ *                 0..samples; a noise W outside 0..samples (NaN included); a file longer than its sections; a section-B word of a pixel of the shard that
+ *                 is neither 0xffffffff nor <= samples; a header `frozen pixels` that disagrees with section B (both
+ *                 counted on the device while the sections are unpacked); parameters pt_accum_create refuses
+ *   PT_E_SCENE    the digest or the counts differ from the context's scene
+ *
+ * A refusal of the file's parameters by pt_accum_create's validation comes back under pt_session_load's name.
+ *
+ * pt_session_file_info is host-only: it reads and validates the header and the file's size (every check above that
+ * does not need the sections or a context).
+ *
+ * The staging (device and pinned host, each the size of the largest session saved or loaded on the context so far:
+ * 100 B per pixel of the image with all four sections, 207 MB at 1920x1080) is kept for the next call and never
+ * shrinks; pt_destroy frees it, like the denoiser's scratch.
+ * Measurement hook: with PT_TIMING set in the environment, pt_session_save / _load and pt_accum_save / _load print
+ * the host wall time of each of their stages (state <-> host buffer, file write / read) to stderr, as pt_create
+ * prints its phases; unset, nothing is printed and nothing else changes. */
+#define PT_SESSION_COUNTS 0x1u
+#define PT_SESSION_NOISE 0x2u
+#define PT_SESSION_NOISE_PER_PIXEL 0x4u
+typedef struct {
+    pt_params params;         /* spp = 0 */
+    pt_camera cam;
+    int64_t samples;
+    uint64_t scene_digest;
+    uint32_t flags;           /* PT_SESSION_* */
+    int32_t noise_batches;
+    int64_t noise_n0;
+    double noise_W;
+    uint64_t frozen_pixels;
+} pt_session_info;            /* 136 B */
+int pt_session_save(pt_accum* acc, pt_noise* noise /* NULL: no estimator section */, const char* path);
+int pt_session_load(pt_ctx* ctx, const char* path, pt_accum** acc_out, pt_noise** noise_out /* may be NULL */, int* has_noise);
+int pt_session_file_info(const char* path, pt_session_info* info);
 
 /* ------------------------------------------------- the variance map of the image's mean
  * What the variance-guided denoiser (pt_denoise_guided, below) takes: per pixel q the estimated variance of the
