@@ -2,7 +2,7 @@
 // loop (kernel.cu:702-737: one drawPixel launch per sample over randState_device and imgBuffer_device,
 // kernel.cu:527-553) as passes of the wavefront kernels over a per-pixel state kept on the device, and that
 // state's checkpoint file.  Host code over the HIP runtime (no kernels): the passes themselves are
-// pt::accum_pass (pt_render.hip).
+// pt::accum_pass (pt_render_host.h).
 // Adaptive sampling (pt_accum_freeze, pt_noise_freeze): a frozen pixel is never sampled again.  Its slot of the
 // frozen_at plane holds the sample count it stopped at; the other pixels all have `samples`.  Once a pixel is
 // frozen a pass runs over the active list (pt_adaptive.hip), rebuilt only when the frozen set changed.
@@ -15,14 +15,9 @@
 #include <vector>
 
 #include "../host/host_internal.h"
+#include "pt_hip_util.h"
 
 namespace {
-
-#define ACC_HIP(call)                                                                                      \
-    do {                                                                                                   \
-        const hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) return pt::fail(PT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_));    \
-    } while (0)
 
 // The checkpoint header (documented in pt.h); every field little-endian at a fixed offset.
 constexpr char kMagic[8] = {'P', 'T', 'A', 'C', 'C', 'U', 'M', '\0'};
@@ -128,11 +123,11 @@ int adaptive_alloc(pt_accum* a)
     std::vector<uint32_t> init(n, 0u);
     for (size_t q = 0; q < a->slots(); ++q)
         if (a->slot_pix[q] != 0xffffffffu) init[q] = pt::kSlotActive;
-    ACC_HIP(hipSetDevice(pt::ctx_device(a->ctx)));
-    ACC_HIP(hipMalloc(reinterpret_cast<void**>(&a->d_frozen_at), n * sizeof(uint32_t)));
-    ACC_HIP(hipMalloc(reinterpret_cast<void**>(&a->d_list), n * sizeof(uint32_t)));
-    ACC_HIP(hipMalloc(reinterpret_cast<void**>(&a->d_scan), pt::adaptive_scan_words(n) * sizeof(uint32_t)));
-    ACC_HIP(hipMemcpy(a->d_frozen_at, init.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipSetDevice(pt::ctx_device(a->ctx)));
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&a->d_frozen_at), n * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&a->d_list), n * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&a->d_scan), pt::adaptive_scan_words(n) * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy(a->d_frozen_at, init.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
     a->list_valid = false;
     return PT_OK;
 }
@@ -142,7 +137,7 @@ int active_list(pt_accum* a, void* stream)
 {
     if (int rc = adaptive_alloc(a)) return rc;
     if (a->list_valid) return PT_OK;
-    ACC_HIP(hipSetDevice(pt::ctx_device(a->ctx)));
+    HIP_TRY(hipSetDevice(pt::ctx_device(a->ctx)));
     if (int rc = pt::adaptive_compact(a->d_frozen_at, a->slots(), a->d_list, a->d_scan, stream, &a->nactive)) return rc;
     a->list_valid = true;
     return PT_OK;
@@ -154,8 +149,8 @@ int fetch_counts(pt_accum* a, std::vector<uint32_t>* cnt)
     const size_t n = a->slots();
     cnt->assign(n, 0u);
     if (a->d_frozen_at && n) {
-        ACC_HIP(hipSetDevice(pt::ctx_device(a->ctx)));
-        ACC_HIP(hipMemcpy(cnt->data(), a->d_frozen_at, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipSetDevice(pt::ctx_device(a->ctx)));
+        HIP_TRY(hipMemcpy(cnt->data(), a->d_frozen_at, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
     for (size_t q = 0; q < n; ++q) {
         if (a->slot_pix[q] == 0xffffffffu) (*cnt)[q] = 0u;
@@ -195,9 +190,9 @@ int pt::accum_session(pt_accum* a, pt::SessionAccum* out)
 {
     if (!a->d_slot_pix) {
         const size_t n = a->slots() ? a->slots() : 1;
-        ACC_HIP(hipSetDevice(pt::ctx_device(a->ctx)));
-        ACC_HIP(hipMalloc(reinterpret_cast<void**>(&a->d_slot_pix), n * sizeof(uint32_t)));
-        if (a->slots()) ACC_HIP(hipMemcpy(a->d_slot_pix, a->slot_pix.data(), a->slots() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipSetDevice(pt::ctx_device(a->ctx)));
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&a->d_slot_pix), n * sizeof(uint32_t)));
+        if (a->slots()) HIP_TRY(hipMemcpy(a->d_slot_pix, a->slot_pix.data(), a->slots() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     *out = pt::SessionAccum{a->ctx, &a->params, &a->cam, a->samples, a->slots(), a->pixels, a->d_rng, a->d_mean,
                             a->any_frozen ? a->d_frozen_at : nullptr, a->d_slot_pix, a->noise};
@@ -237,13 +232,13 @@ pt_accum* make_accum(pt_ctx* c, const pt_params* p, const pt_camera* cam, int* c
     pt::shard_slots(&a->params, &a->slot_pix);
     for (const uint32_t pix : a->slot_pix) a->pixels += pix != 0xffffffffu;
     auto alloc = [&]() -> int {
-        ACC_HIP(hipSetDevice(pt::ctx_device(c)));
+        HIP_TRY(hipSetDevice(pt::ctx_device(c)));
         const size_t n = a->slots() ? a->slots() : 1;
-        ACC_HIP(hipMalloc(reinterpret_cast<void**>(&a->d_rng), n * 6 * sizeof(uint32_t)));
-        ACC_HIP(hipMalloc(reinterpret_cast<void**>(&a->d_mean), n * 3 * sizeof(double)));
-        ACC_HIP(hipMemset(a->d_rng, 0, n * 6 * sizeof(uint32_t)));
-        ACC_HIP(hipMemset(a->d_mean, 0, n * 3 * sizeof(double)));
-        ACC_HIP(hipDeviceSynchronize());
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&a->d_rng), n * 6 * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&a->d_mean), n * 3 * sizeof(double)));
+        HIP_TRY(hipMemset(a->d_rng, 0, n * 6 * sizeof(uint32_t)));
+        HIP_TRY(hipMemset(a->d_mean, 0, n * 3 * sizeof(double)));
+        HIP_TRY(hipDeviceSynchronize());
         return PT_OK;
     };
     *code = alloc();
@@ -257,10 +252,10 @@ int fetch_records(pt_accum* a, std::vector<Record>* rec)
     const size_t n = a->slots();
     std::vector<uint32_t> rng(n * 6);
     std::vector<double> mean(n * 3);
-    ACC_HIP(hipSetDevice(pt::ctx_device(a->ctx)));
+    HIP_TRY(hipSetDevice(pt::ctx_device(a->ctx)));
     if (n) {
-        ACC_HIP(hipMemcpy(rng.data(), a->d_rng, n * 6 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        ACC_HIP(hipMemcpy(mean.data(), a->d_mean, n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(rng.data(), a->d_rng, n * 6 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(mean.data(), a->d_mean, n * 3 * sizeof(double), hipMemcpyDeviceToHost));
     }
     Record zero;
     memset(&zero, 0, sizeof(zero));
@@ -367,8 +362,8 @@ int pt_accum_freeze(pt_accum* acc, const uint8_t* mask)
     if (!any) return PT_OK;   // (nothing of this shard named: the accumulator stays as it is)
     if (int rc = adaptive_alloc(acc)) return rc;
     std::vector<uint32_t> at(n);
-    ACC_HIP(hipSetDevice(pt::ctx_device(acc->ctx)));
-    ACC_HIP(hipMemcpy(at.data(), acc->d_frozen_at, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipSetDevice(pt::ctx_device(acc->ctx)));
+    HIP_TRY(hipMemcpy(at.data(), acc->d_frozen_at, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     uint64_t newly = 0;
     for (size_t q = 0; q < n; ++q) {
         if (acc->slot_pix[q] == 0xffffffffu || at[q] != pt::kSlotActive || !mask[order_index(acc, acc->slot_pix[q])]) continue;
@@ -376,7 +371,7 @@ int pt_accum_freeze(pt_accum* acc, const uint8_t* mask)
         ++newly;
     }
     if (!newly) return PT_OK;
-    ACC_HIP(hipMemcpy(acc->d_frozen_at, at.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(acc->d_frozen_at, at.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
     pt::accum_frozen(acc, newly);
     return PT_OK;
 }
@@ -405,7 +400,7 @@ int pt_accum_active(pt_accum* acc, uint32_t* out, uint32_t cap, uint64_t* n_out)
     if (!out) return PT_OK;
     if (cap < acc->nactive) return pt::fail(PT_E_INVALID, "pt_accum_active: buffer of %u entries too small for %u", cap, acc->nactive);
     std::vector<uint32_t> list(acc->nactive);
-    if (acc->nactive) ACC_HIP(hipMemcpy(list.data(), acc->d_list, list.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (acc->nactive) HIP_TRY(hipMemcpy(list.data(), acc->d_list, list.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (size_t u = 0; u < list.size(); ++u) {
         if (list[u] >= acc->slots()) return pt::fail(PT_E_HIP, "pt_accum_active: the device list names slot %u of %zu", list[u], acc->slots());
         out[u] = acc->slot_pix[list[u]];
@@ -543,8 +538,8 @@ pt_accum* pt_accum_load(pt_ctx* ctx, const char* path, int* err)
     }
     auto upload = [&]() -> int {
         if (!n) return PT_OK;
-        ACC_HIP(hipMemcpy(a->d_rng, rng.data(), n * 6 * sizeof(uint32_t), hipMemcpyHostToDevice));
-        ACC_HIP(hipMemcpy(a->d_mean, mean.data(), n * 3 * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(a->d_rng, rng.data(), n * 6 * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(a->d_mean, mean.data(), n * 3 * sizeof(double), hipMemcpyHostToDevice));
         return PT_OK;
     };
     if (int rc = upload()) { pt_accum_destroy(a); return bail(rc); }

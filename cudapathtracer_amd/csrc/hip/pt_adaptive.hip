@@ -11,14 +11,9 @@
 #include <hip/hip_runtime.h>
 
 #include "../host/host_internal.h"
+#include "pt_hip_util.h"
 
 namespace {
-
-#define AD_HIP(call)                                                                                       \
-    do {                                                                                                   \
-        const hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) return pt::fail(PT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_));    \
-    } while (0)
 
 constexpr int kBlock = 256;   // 4 waves; one slot per lane
 
@@ -88,8 +83,8 @@ int pt::adaptive_compact(const uint32_t* frozen_at, size_t slots, uint32_t* list
     hipLaunchKernelGGL(active_count, dim3(nblocks), dim3(kBlock), 0, stream, frozen_at, n, block_tot);
     hipLaunchKernelGGL(active_scan, dim3(1), dim3(kBlock), 0, stream, block_tot, nblocks);
     hipLaunchKernelGGL(active_scatter, dim3(nblocks), dim3(kBlock), 0, stream, frozen_at, n, block_tot, list);
-    AD_HIP(hipGetLastError());
-    AD_HIP(hipMemcpyAsync(count, block_tot + nblocks, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    AD_HIP(hipStreamSynchronize(stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(count, block_tot + nblocks, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     return PT_OK;
 }

@@ -33,14 +33,9 @@
 #include <cstring>
 
 #include "../host/host_internal.h"
+#include "pt_hip_util.h"
 
 namespace {
-
-#define DN_HIP(call)                                                                                       \
-    do {                                                                                                   \
-        const hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) return pt::fail(PT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_));    \
-    } while (0)
 
 static_assert(sizeof(pt_feature) == 48, "pt_feature is 48 B");
 
@@ -423,12 +418,12 @@ int check_guided(const char* who, const pt_ctx* c, const pt_denoise_guided_param
 int filter_device(pt_ctx* c, const pt_denoise_params* dp, int w, int h, int order, const float* d_in, const pt_feature* d_feat,
                   const float* d_var, float sigma_luma, float* d_out, void* stream_v)
 {
-    DN_HIP(hipSetDevice(pt::ctx_device(c)));
+    HIP_TRY(hipSetDevice(pt::ctx_device(c)));
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
     const size_t n = (size_t)w * (size_t)h;
     if (dp->iterations == 0) {   // every pixel keeps its input
-        if (d_out != d_in) DN_HIP(hipMemcpyAsync(d_out, d_in, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
-        DN_HIP(hipStreamSynchronize(stream));
+        if (d_out != d_in) HIP_TRY(hipMemcpyAsync(d_out, d_in, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
         return PT_OK;
     }
     const bool guided = d_var != nullptr;
@@ -438,7 +433,7 @@ int filter_device(pt_ctx* c, const pt_denoise_params* dp, int w, int h, int orde
         if (S->mem) (void)hipFree(S->mem);
         S->mem = nullptr;
         S->bytes = 0;
-        DN_HIP(hipMalloc(&S->mem, need));
+        HIP_TRY(hipMalloc(&S->mem, need));
         S->bytes = need;
     }
     float4* const g0 = static_cast<float4*>(S->mem);
@@ -454,7 +449,7 @@ int filter_device(pt_ctx* c, const pt_denoise_params* dp, int w, int h, int orde
     else
         hipLaunchKernelGGL(dn_prepass, grid, dim3(256), 0, stream, d_in, reinterpret_cast<const float*>(d_feat), g0, g1, cc[0], w, h,
                            morton, demod, dp->sigma_depth);
-    DN_HIP(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     // PT_DENOISE_DIRECT=1: every iteration on the direct gather (the baseline); PT_DENOISE_TILED_MAX: the
     // largest step staged through LDS (default kTiledMaxStep)
     const bool direct = env_int("PT_DENOISE_DIRECT", 0) != 0;
@@ -471,12 +466,12 @@ int filter_device(pt_ctx* c, const pt_denoise_params* dp, int w, int h, int orde
         ga.sl2 = sigma_luma * sigma_luma;
         if (guided) {
             hipLaunchKernelGGL(dg_blur, grid, dim3(256), 0, stream, vpl, vbar, w, h);
-            DN_HIP(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
         if (!direct && a.step <= tiled_max) {
             const size_t lds = (size_t)3 * kStageRows * (size_t)(kTileX + 4 * a.step) * sizeof(float4);
             if (lds > 64 * 1024)   // (beyond the default dynamic-LDS limit; gfx950 has 160 KB per CU)
-                DN_HIP(hipFuncSetAttribute(guided ? reinterpret_cast<const void*>(&dg_iterate<true>)
+                HIP_TRY(hipFuncSetAttribute(guided ? reinterpret_cast<const void*>(&dg_iterate<true>)
                                                   : reinterpret_cast<const void*>(&dn_iterate<true>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize,
                                            3 * kStageRows * (kTileX + 4 * kTiledLimit) * (int)sizeof(float4)));
@@ -488,12 +483,12 @@ int filter_device(pt_ctx* c, const pt_denoise_params* dp, int w, int h, int orde
             if (guided) hipLaunchKernelGGL((dg_iterate<false>), grid, dim3(256), 0, stream, ga);
             else hipLaunchKernelGGL((dn_iterate<false>), grid, dim3(256), 0, stream, a);
         }
-        DN_HIP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(dn_finish, grid, dim3(256), 0, stream, cc[dp->iterations & 1], g1, reinterpret_cast<const float*>(d_feat), d_out,
                        w, h, morton, demod);
-    DN_HIP(hipGetLastError());
-    DN_HIP(hipStreamSynchronize(stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
     return PT_OK;
 }
 
@@ -501,29 +496,21 @@ int filter_device(pt_ctx* c, const pt_denoise_params* dp, int w, int h, int orde
 int filter_host(pt_ctx* c, const pt_denoise_params* dp, int w, int h, int order, const float* in, const pt_feature* feat,
                 const float* var, float sigma_luma, float* out)
 {
-    DN_HIP(hipSetDevice(pt::ctx_device(c)));
+    HIP_TRY(hipSetDevice(pt::ctx_device(c)));
     const size_t n = (size_t)w * (size_t)h;
-    float* d_img = nullptr;
-    float* d_var = nullptr;
-    pt_feature* d_feat = nullptr;
-    auto run = [&]() -> int {
-        DN_HIP(hipMalloc(reinterpret_cast<void**>(&d_img), n * 3 * sizeof(float)));
-        DN_HIP(hipMalloc(reinterpret_cast<void**>(&d_feat), n * sizeof(pt_feature)));
-        DN_HIP(hipMemcpy(d_img, in, n * 3 * sizeof(float), hipMemcpyHostToDevice));
-        DN_HIP(hipMemcpy(d_feat, feat, n * sizeof(pt_feature), hipMemcpyHostToDevice));
-        if (var) {
-            DN_HIP(hipMalloc(reinterpret_cast<void**>(&d_var), n * sizeof(float)));
-            DN_HIP(hipMemcpy(d_var, var, n * sizeof(float), hipMemcpyHostToDevice));
-        }
-        if (int rc = filter_device(c, dp, w, h, order, d_img, d_feat, d_var, sigma_luma, d_img, nullptr)) return rc;
-        DN_HIP(hipMemcpy(out, d_img, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-        return PT_OK;
-    };
-    const int rc = run();
-    if (d_img) (void)hipFree(d_img);
-    if (d_var) (void)hipFree(d_var);
-    if (d_feat) (void)hipFree(d_feat);
-    return rc;
+    pt::ScopedDevice<float> d_img, d_var;
+    pt::ScopedDevice<pt_feature> d_feat;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_img), n * 3 * sizeof(float)));
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_feat), n * sizeof(pt_feature)));
+    HIP_TRY(hipMemcpy(d_img, in, n * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_feat, feat, n * sizeof(pt_feature), hipMemcpyHostToDevice));
+    if (var) {
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_var), n * sizeof(float)));
+        HIP_TRY(hipMemcpy(d_var, var, n * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if (int rc = filter_device(c, dp, w, h, order, d_img, d_feat, d_var, sigma_luma, d_img, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(out, d_img, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    return PT_OK;
 }
 
 }  // namespace

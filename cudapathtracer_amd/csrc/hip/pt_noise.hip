@@ -28,14 +28,9 @@
 #include <vector>
 
 #include "../host/host_internal.h"
+#include "pt_hip_util.h"
 
 namespace {
-
-#define NS_HIP(call)                                                                                       \
-    do {                                                                                                   \
-        const hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) return pt::fail(PT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_));    \
-    } while (0)
 
 constexpr int kBlock = 256;
 // grid cap: blocks per CU, the rest of the slots by grid stride.  Measured at 1920x1080: 2 / 4 / 8 /
@@ -321,7 +316,7 @@ int go_per_pixel(pt_noise* z, hipStream_t stream)
 {
     if (z->pix_live) return PT_OK;
     const size_t n = z->slots() ? z->slots() : 1;
-    if (!z->d_pix) NS_HIP(hipMalloc(reinterpret_cast<void**>(&z->d_pix), 2 * n * sizeof(uint32_t)));
+    if (!z->d_pix) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&z->d_pix), 2 * n * sizeof(uint32_t)));
     if (z->slots()) {
         NoiseArgs a;
         memset(&a, 0, sizeof(a));
@@ -329,7 +324,7 @@ int go_per_pixel(pt_noise* z, hipStream_t stream)
         a.pw = z->d_pix;
         a.pb = z->d_pix + z->slots();
         hipLaunchKernelGGL(noise_fill_pix, dim3(grid_of(z)), dim3(kBlock), 0, stream, a, (uint32_t)z->W, (uint32_t)z->batches);
-        NS_HIP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     z->pix_live = true;
     return PT_OK;
@@ -400,16 +395,16 @@ pt_noise* pt_noise_create(pt_accum* acc, int* err)
             if (v.params->pixel_order == PT_ORDER_MORTON) o = pt_morton_pxl_to_i(o % w, o / w);
         }
         const size_t n = z->slots() ? z->slots() : 1;
-        NS_HIP(hipSetDevice(pt::ctx_device(v.ctx)));
-        NS_HIP(hipMalloc(reinterpret_cast<void**>(&z->d_dst), n * sizeof(uint32_t)));
-        NS_HIP(hipMalloc(reinterpret_cast<void**>(&z->d_state), n * 5 * sizeof(double)));
-        NS_HIP(hipMalloc(reinterpret_cast<void**>(&z->d_sum), kSumCopies * kSumWords * sizeof(unsigned long long)));
+        HIP_TRY(hipSetDevice(pt::ctx_device(v.ctx)));
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&z->d_dst), n * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&z->d_state), n * 5 * sizeof(double)));
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&z->d_sum), kSumCopies * kSumWords * sizeof(unsigned long long)));
         if (z->slots()) {
-            NS_HIP(hipMemcpy(z->d_dst, z->dst.data(), z->slots() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            NS_HIP(hipMemcpy(z->d_state, v.mean, z->slots() * 3 * sizeof(double), hipMemcpyDeviceToDevice));   // prev = the mean
+            HIP_TRY(hipMemcpy(z->d_dst, z->dst.data(), z->slots() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(z->d_state, v.mean, z->slots() * 3 * sizeof(double), hipMemcpyDeviceToDevice));   // prev = the mean
         }
-        NS_HIP(hipMemset(z->d_state + 3 * z->slots(), 0, (n * 5 - 3 * z->slots()) * sizeof(double)));          // mu = m2 = 0
-        NS_HIP(hipDeviceSynchronize());
+        HIP_TRY(hipMemset(z->d_state + 3 * z->slots(), 0, (n * 5 - 3 * z->slots()) * sizeof(double)));          // mu = m2 = 0
+        HIP_TRY(hipDeviceSynchronize());
         *v.noise = z;
         return PT_OK;
     };
@@ -430,7 +425,7 @@ int pt_noise_update(pt_noise* z, const pt_noise_params* np, void* stream_v, pt_n
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
     const int64_t n1 = pt::accum_view(z->acc).samples;
     const bool fold = n1 > z->n0;
-    NS_HIP(hipSetDevice(pt::ctx_device(z->ctx)));
+    HIP_TRY(hipSetDevice(pt::ctx_device(z->ctx)));
     if (int rc = follow_accum(z, stream)) return rc;
     NoiseArgs a = args_of(z, np);
     if (fold) {
@@ -443,16 +438,16 @@ int pt_noise_update(pt_noise* z, const pt_noise_params* np, void* stream_v, pt_n
     unsigned long long part[kSumCopies * kSumWords], sum[kSumWords];
     memset(part, 0, sizeof(part));
     if (z->slots()) {
-        NS_HIP(hipMemsetAsync(z->d_sum, 0, sizeof(part), stream));
+        HIP_TRY(hipMemsetAsync(z->d_sum, 0, sizeof(part), stream));
         if (z->pix_live) {
             if (fold) hipLaunchKernelGGL((noise_update<true, true>), dim3(grid_of(z)), dim3(kBlock), 0, stream, a);
             else hipLaunchKernelGGL((noise_update<false, true>), dim3(grid_of(z)), dim3(kBlock), 0, stream, a);
         }
         else if (fold) hipLaunchKernelGGL((noise_update<true>), dim3(grid_of(z)), dim3(kBlock), 0, stream, a);
         else hipLaunchKernelGGL((noise_update<false>), dim3(grid_of(z)), dim3(kBlock), 0, stream, a);
-        NS_HIP(hipGetLastError());
-        NS_HIP(hipMemcpyAsync(part, z->d_sum, sizeof(part), hipMemcpyDeviceToHost, stream));
-        NS_HIP(hipStreamSynchronize(stream));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(part, z->d_sum, sizeof(part), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
     }
     for (int k = 0; k < kSumWords; ++k) {
         sum[k] = 0;
@@ -477,15 +472,15 @@ int pt_noise_map_device(pt_noise* z, const pt_noise_params* np, float* d_rel2, v
     if (!d_rel2) return pt::fail(PT_E_INVALID, "pt_noise_map_device: null argument");
     if (int rc = check("pt_noise_map_device", z, np)) return rc;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
-    NS_HIP(hipSetDevice(pt::ctx_device(z->ctx)));
+    HIP_TRY(hipSetDevice(pt::ctx_device(z->ctx)));
     if (!z->slots()) return PT_OK;
     if (int rc = follow_accum(z, stream)) return rc;
     NoiseArgs a = args_of(z, np);
     a.map = d_rel2;
     if (z->pix_live) hipLaunchKernelGGL(noise_map<true>, dim3(grid_of(z)), dim3(kBlock), 0, stream, a);
     else hipLaunchKernelGGL(noise_map<false>, dim3(grid_of(z)), dim3(kBlock), 0, stream, a);
-    NS_HIP(hipGetLastError());
-    NS_HIP(hipStreamSynchronize(stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
     return PT_OK;
 }
 
@@ -496,18 +491,13 @@ int pt_noise_map(pt_noise* z, const pt_noise_params* np, float* rel2)
     if (int rc = check("pt_noise_map", z, np)) return rc;
     const pt_params* p = pt::accum_view(z->acc).params;
     const size_t bytes = (size_t)p->width * (size_t)p->height * sizeof(float);
-    NS_HIP(hipSetDevice(pt::ctx_device(z->ctx)));
-    float* d = nullptr;
-    auto run = [&]() -> int {
-        NS_HIP(hipMalloc(reinterpret_cast<void**>(&d), bytes));
-        NS_HIP(hipMemset(d, 0, bytes));
-        if (int rc = pt_noise_map_device(z, np, d, nullptr)) return rc;
-        NS_HIP(hipMemcpy(rel2, d, bytes, hipMemcpyDeviceToHost));
-        return PT_OK;
-    };
-    const int rc = run();
-    if (d) (void)hipFree(d);
-    return rc;
+    HIP_TRY(hipSetDevice(pt::ctx_device(z->ctx)));
+    pt::ScopedDevice<float> d;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), bytes));
+    HIP_TRY(hipMemset(d, 0, bytes));
+    if (int rc = pt_noise_map_device(z, np, d, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(rel2, d, bytes, hipMemcpyDeviceToHost));
+    return PT_OK;
 }
 
 int pt_noise_variance_device(pt_noise* z, float* d_var, void* stream_v)
@@ -515,7 +505,7 @@ int pt_noise_variance_device(pt_noise* z, float* d_var, void* stream_v)
     pt::clear_error();
     if (int rc = check_variance("pt_noise_variance_device", z, d_var)) return rc;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
-    NS_HIP(hipSetDevice(pt::ctx_device(z->ctx)));
+    HIP_TRY(hipSetDevice(pt::ctx_device(z->ctx)));
     if (!z->slots()) return PT_OK;
     if (int rc = follow_accum(z, stream)) return rc;
     pt_noise_params np;
@@ -527,8 +517,8 @@ int pt_noise_variance_device(pt_noise* z, float* d_var, void* stream_v)
     a.n_now = (uint32_t)samples;
     if (z->pix_live) hipLaunchKernelGGL(noise_variance<true>, dim3(grid_of(z)), dim3(kBlock), 0, stream, a);
     else hipLaunchKernelGGL(noise_variance<false>, dim3(grid_of(z)), dim3(kBlock), 0, stream, a);
-    NS_HIP(hipGetLastError());
-    NS_HIP(hipStreamSynchronize(stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
     return PT_OK;
 }
 
@@ -538,18 +528,13 @@ int pt_noise_variance(pt_noise* z, float* var)
     if (int rc = check_variance("pt_noise_variance", z, var)) return rc;
     const pt_params* p = pt::accum_view(z->acc).params;
     const size_t bytes = (size_t)p->width * (size_t)p->height * sizeof(float);
-    NS_HIP(hipSetDevice(pt::ctx_device(z->ctx)));
-    float* d = nullptr;
-    auto run = [&]() -> int {
-        NS_HIP(hipMalloc(reinterpret_cast<void**>(&d), bytes));
-        NS_HIP(hipMemset(d, 0, bytes));
-        if (int rc = pt_noise_variance_device(z, d, nullptr)) return rc;
-        NS_HIP(hipMemcpy(var, d, bytes, hipMemcpyDeviceToHost));
-        return PT_OK;
-    };
-    const int rc = run();
-    if (d) (void)hipFree(d);
-    return rc;
+    HIP_TRY(hipSetDevice(pt::ctx_device(z->ctx)));
+    pt::ScopedDevice<float> d;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), bytes));
+    HIP_TRY(hipMemset(d, 0, bytes));
+    if (int rc = pt_noise_variance_device(z, d, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(var, d, bytes, hipMemcpyDeviceToHost));
+    return PT_OK;
 }
 
 int pt_noise_freeze(pt_noise* z, const pt_noise_params* np, void* stream_v, uint64_t* newly_frozen, uint64_t* active)
@@ -558,7 +543,7 @@ int pt_noise_freeze(pt_noise* z, const pt_noise_params* np, void* stream_v, uint
     if (!newly_frozen || !active) return pt::fail(PT_E_INVALID, "pt_noise_freeze: null argument");
     if (int rc = check("pt_noise_freeze", z, np)) return rc;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
-    NS_HIP(hipSetDevice(pt::ctx_device(z->ctx)));
+    HIP_TRY(hipSetDevice(pt::ctx_device(z->ctx)));
     const pt::AccumView v = pt::accum_view(z->acc);
     *newly_frozen = 0;
     *active = 0;
@@ -570,11 +555,11 @@ int pt_noise_freeze(pt_noise* z, const pt_noise_params* np, void* stream_v, uint
     a.frozen_at = plane;
     a.n_now = (uint32_t)v.samples;
     unsigned long long part[kSumCopies * kSumWords];
-    NS_HIP(hipMemsetAsync(z->d_sum, 0, sizeof(part), stream));
+    HIP_TRY(hipMemsetAsync(z->d_sum, 0, sizeof(part), stream));
     hipLaunchKernelGGL(noise_freeze, dim3(grid_of(z)), dim3(kBlock), 0, stream, a);
-    NS_HIP(hipGetLastError());
-    NS_HIP(hipMemcpyAsync(part, z->d_sum, sizeof(part), hipMemcpyDeviceToHost, stream));
-    NS_HIP(hipStreamSynchronize(stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(part, z->d_sum, sizeof(part), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     for (int c = 0; c < kSumCopies; ++c) {
         *newly_frozen += part[c * kSumWords];
         *active += part[c * kSumWords + 1];
@@ -593,8 +578,8 @@ int pt_noise_read(pt_noise* z, double* mu, double* m2)
     const pt_params* p = pt::accum_view(z->acc).params;
     const size_t n = z->slots(), npix = (size_t)p->width * (size_t)p->height;
     std::vector<double> st(2 * n);
-    NS_HIP(hipSetDevice(pt::ctx_device(z->ctx)));
-    if (n) NS_HIP(hipMemcpy(st.data(), z->d_state + 3 * n, 2 * n * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipSetDevice(pt::ctx_device(z->ctx)));
+    if (n) HIP_TRY(hipMemcpy(st.data(), z->d_state + 3 * n, 2 * n * sizeof(double), hipMemcpyDeviceToHost));
     if (mu) memset(mu, 0, npix * sizeof(double));
     if (m2) memset(m2, 0, npix * sizeof(double));
     for (size_t q = 0; q < n; ++q) {

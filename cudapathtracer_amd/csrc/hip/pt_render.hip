@@ -1,23 +1,27 @@
-// pt_render.hip -- gfx950 render kernels and the render half of the C-ABI (include/pt/pt.h).
+// pt_render.hip -- the gfx950 render kernels: device code only.  The host half of this translation unit (the
+// render context, pt_create / pt_destroy and the render, trace, features and tone-map entry points of pt/pt.h) is
+// pt_render_host.h, included once as the last line.  Text after the kernels cannot change how they compile, and an
+// edit confined to that header leaves this file, and any hash taken over the kernel sources, as it is.
 //
-// One wave renders one 8x8 image tile: lane l owns pixel (8*tx + mx(l), 8*ty + my(l)) with
-// (mx, my) the Morton decode of l, and runs ALL of that pixel's samples in order with its
-// XORWOW state and f64 running mean in registers (the reference keeps both in HBM and
-// re-launches drawPixel per sample, kernel.cu:535-553, 709-736).  Waves are persistent and pull
-// tiles from an atomic counter; tile t belongs to shard t % shard_count.
+// Sections, in order:
+//   Args, counter slots        the one argument block every kernel takes
+//   tile-path integrators      spheres, the per-lane tracer, integrators 0 and 1, the camera, render_tiles.  One wave
+//                              renders one 8x8 image tile: lane l owns pixel (8*tx + mx(l), 8*ty + my(l)) with
+//                              (mx, my) the Morton decode of l, and runs ALL of that pixel's samples in order with
+//                              its XORWOW state and f64 running mean in registers (the reference keeps both in HBM
+//                              and re-launches drawPixel per sample, kernel.cu:535-553, 709-736).  Waves are
+//                              persistent and pull tiles from an atomic counter; tile t belongs to shard
+//                              t % shard_count.
+//   unit set-up                init_pixel_states, init_active_states, seed_table, build_jump_byte_tables,
+//                              finalize_pixels: the wavefront kernels' work units and RNG tables
+//   wavefront shading          the walk and the shading passes of integrator 0, then of integrator 1
+//   wf_main, kernel instances  render_unidir_wf, render_head_wf and their accumulating twins
+//   output / trace / features  tonemap_codes, trace_rays, primary_features
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstddef>
-#include <cstdio>
 #include <cstring>
-#include <mutex>
-#include <new>
-#include <string>
-#include <thread>
-#include <vector>
 
 #include "../host/host_internal.h"
 #include "../host/render_plan.h"
@@ -2592,970 +2596,6 @@ __global__ __launch_bounds__(256) void primary_features(Args a, float4* __restri
     }
 }
 
-// ------------------------------------------------------------------ host side
-#define HIP_TRY(expr)                                                                           \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess) return pt::fail(PT_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-// A device buffer grown on demand (*have counts T's): freed and allocated anew when smaller than `need`.
-// The slot is null and 0 before the hipMalloc, so a failed grow leaves it consistent.
-template <typename T>
-int grow(T** buf, size_t* have, size_t need)
-{
-    if (*have >= need) return PT_OK;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *have = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(buf), need * sizeof(T)));
-    *have = need;
-    return PT_OK;
-}
-
-template <typename T>
-int upload(T** dst, const std::vector<T>& src)
-{
-    size_t bytes = src.size() * sizeof(T);
-    if (bytes == 0) bytes = sizeof(T);
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(dst), bytes));
-    if (!src.empty()) HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-    return PT_OK;
-}
-
 }  // namespace
 
-void pt::sincos_det(float theta, float* s, float* c) { det_sincos(theta, s, c); }
-
-struct pt_ctx : pt::SceneInfo {            // (the scene's scalars: pt_scene_pack.h)
-    int device = 0;
-    int num_cus = 256;
-    pt::RenderKnobs knobs;                 // the PT_* knobs as they were at pt_create
-    // the packed scene's arrays on the device (pt::PackedScene has the same names)
-    DNode* nodes = nullptr;
-    RNode* rnodes = nullptr;
-    DTri* tris_leaf = nullptr;
-    DTri* tris_orig = nullptr;
-    DShade* shade = nullptr;
-    DMat* mats = nullptr;
-    DLight* lights = nullptr;
-    uint32_t* jump = nullptr;
-    float4* shade_m = nullptr;        // merged shading records (Args::shade_m), or none
-    DNode4* nodes4 = nullptr;
-    DTri* acc_tris = nullptr;
-    uint32_t* rparent = nullptr;
-    float4* hrec = nullptr;
-    float* tone_thr = nullptr;        // output step: the host libm's 255 code boundaries (+ t[0] = 0)
-    float4* spheres = nullptr;        // sphere primitives (center, radius)
-    DTri* emis = nullptr;             // last-bounce light probe: records of the emissive triangles
-    uint32_t* tri_counts = nullptr;   // PT_FLAG_COUNT: per-triangle test counts (num_tris entries, >= 1)
-    uint32_t* jump_bytes = nullptr;   // byte-position jump matrices (built on the first wavefront render)
-    hipEvent_t jump_ready = nullptr;  // recorded behind their build
-    float* scratch_out = nullptr;     // pt_render: the image on the device
-    size_t scratch_floats = 0;
-    void* pinned = nullptr;                    // pt_render: pinned staging buffer of the image copy-out
-    size_t pinned_bytes = 0;
-    // renders in flight (pt_render_device_async / pt_render_wait): a FIFO of kFlights slots, each with
-    // its events and a pinned host copy of the render's counters
-    struct Flight {
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;   // the whole render
-        hipEvent_t ek0 = nullptr, ek1 = nullptr;   // the integration kernel alone
-        hipEvent_t done = nullptr;                 // after the counters' copy
-        unsigned long long* hcnt = nullptr;        // pinned: the counters, copied behind the render
-        bool kernel_events = false, count = false;
-        uint64_t units = 0, split = 0;
-        int32_t spp = 0, bounces = 0;
-    };
-    static constexpr int kFlights = 2;
-    Flight fl[kFlights];
-    // A render's device scratch, one set per in-flight slot, so that two queued renders (e.g. frames on
-    // two streams) never share a buffer; set 0 also serves the batched trace entry points.
-    struct Bufs {
-        uint32_t* spill = nullptr;            // per-lane stack spill columns, then the shading records
-        size_t spill_words = 0;
-        uint32_t* pix_states = nullptr;       // init_pixel_states output (kUnitWords per work unit)
-        size_t pix_states_words = 0;
-        double* lbuf = nullptr;               // per-sample radiance of split pixels
-        size_t lbuf_words = 0;
-        uint32_t* pmemo = nullptr;            // per-pixel-slot primary hit shared by a split pixel's chunks
-        size_t pmemo_words = 0;
-        unsigned long long* counters = nullptr;
-        uint32_t* pixel_counter = nullptr;    // the unit queues
-        uint32_t* tile_counter = nullptr;
-        uint32_t* seed_states = nullptr;      // per-render seed_table output
-        uint64_t seed_cached = 0;             // the seed seed_states was built for
-        bool seed_valid = false;
-    };
-    Bufs rb[kFlights];
-    int fl_head = 0, fl_n = 0;                 // oldest in-flight slot, number in flight
-    pt::DenoiseScratch denoise;       // pt_denoise*'s device scratch (pt_denoise.hip), grown on demand
-    pt::SessionScratch session;       // pt_session_save / _load's staging (pt_session.cpp), grown on demand
-};
-
-int pt::ctx_device(const pt_ctx* c) { return c->device; }
-
-// Per-lane HBM words the walks may need: the BVH4 ring's overflow (at most 3 pushes per level)
-// and trace_slow's full stack on the reference BVH.
-static size_t stack_words_per_lane(const pt_ctx* c);
-static bool alloc_bufs(pt_ctx::Bufs& B);
-
-extern "C" {
-
-static bool create_flights(pt_ctx* c)
-{
-    for (pt_ctx::Flight& f : c->fl) {
-        if (hipEventCreate(&f.ev0) != hipSuccess || hipEventCreate(&f.ev1) != hipSuccess ||
-            hipEventCreate(&f.ek0) != hipSuccess || hipEventCreate(&f.ek1) != hipSuccess ||
-            hipEventCreateWithFlags(&f.done, hipEventDisableTiming) != hipSuccess ||
-            hipHostMalloc(reinterpret_cast<void**>(&f.hcnt), kCounterWords * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
-            return false;
-    }
-    return true;
-}
-
-// The packed scene's arrays on the device, and the per-triangle counters.
-static int upload_scene(pt_ctx* c, const pt::PackedScene& P)
-{
-    int rc = PT_OK;
-    if ((rc = upload(&c->nodes, P.nodes)) || (rc = upload(&c->rnodes, P.rnodes)) || (rc = upload(&c->tris_leaf, P.tris_leaf)) ||
-        (rc = upload(&c->tris_orig, P.tris_orig)) || (rc = upload(&c->shade, P.shade)) ||
-        (!P.shade_m.empty() && (rc = upload(&c->shade_m, P.shade_m))) || (rc = upload(&c->mats, P.mats)) ||
-        (rc = upload(&c->lights, P.lights)) || (rc = upload(&c->jump, P.jump)) || (rc = upload(&c->tone_thr, P.tone)) ||
-        (rc = upload(&c->spheres, P.spheres)) || (rc = upload(&c->nodes4, P.nodes4)) || (rc = upload(&c->acc_tris, P.acc_tris)) ||
-        (rc = upload(&c->rparent, P.rparent)) || (rc = upload(&c->hrec, P.hrec)) ||
-        (rc = upload(&c->tri_counts, std::vector<uint32_t>(std::max<uint32_t>(P.num_tris, 1u), 0u))) ||
-        (rc = upload(&c->emis, P.emis)))
-        return rc;
-    return PT_OK;
-}
-
-pt_ctx* pt_create(const pt_scene* sc, int device, int* err)
-{
-    // PT_TIMING=1: host-side phase times on stderr (ingest-speed measurements)
-    pt::PhaseTimer timer{getenv("PT_TIMING") != nullptr};
-    auto bail = [&](int code) -> pt_ctx* { if (err) *err = code; return nullptr; };
-    // the arguments
-    if (!sc || (sc->num_tris == 0 && sc->num_spheres == 0) || (sc->num_tris > 0 && (!sc->verts || !sc->tris || !sc->bvh)) ||
-        (sc->num_mats > 0 && !sc->mats) ||
-        (sc->num_spheres > 0 && !sc->spheres) || (sc->num_lights > 0 && !sc->lights))
-        return bail(pt::fail(PT_E_INVALID, "pt_create: incomplete scene"));
-    const bool spheres_only = sc->num_tris == 0 && sc->num_spheres > 0 && sc->bvh_size == 0;
-    if (!spheres_only && (sc->num_tris < 2 || sc->bvh_size != sc->num_tris - 1))
-        return bail(pt::fail(PT_E_SCENE, "pt_create: need >= 2 triangles and a BVH of num_tris-1 nodes, or spheres only "
-                             "(got %u tris, %u nodes, %u spheres)", sc->num_tris, sc->bvh_size, sc->num_spheres));
-    if (sc->bvh_depth >= PT_MAX_BVH_DEPTH)
-        return bail(pt::fail(PT_E_BVH_DEPTH, "Critical Error: BVH depth is too big (%d)", sc->bvh_depth));
-    // the device
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return bail(pt::fail(PT_E_NODEV, "pt_create: no HIP device"));
-    if (device < 0 || device >= ndev) return bail(pt::fail(PT_E_NODEV, "pt_create: device %d out of range (%d)", device, ndev));
-    if (hipSetDevice(device) != hipSuccess) return bail(pt::fail(PT_E_HIP, "hipSetDevice(%d) failed", device));
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return bail(pt::fail(PT_E_HIP, "hipGetDeviceProperties failed"));
-    if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
-        return bail(pt::fail(PT_E_NODEV, "pt_create: device %d is %s, this build targets gfx950", device, prop.gcnArchName));
-    // the scene as the kernels read it
-    const pt::RenderKnobs knobs = pt::read_render_knobs(kQueues, kTopNodesMax);
-    pt::PackedScene P;
-    if (int rc = pt::pack_scene(*sc, knobs, &timer, &P)) return bail(rc);
-    pt_ctx* c = new (std::nothrow) pt_ctx();
-    if (!c) return bail(pt::fail(PT_E_OOM, "pt_create: out of host memory"));
-    static_cast<pt::SceneInfo&>(*c) = P;
-    c->device = device;
-    c->num_cus = prop.multiProcessorCount;
-    c->knobs = P.knobs;   // (with this scene's defaults of the knobs that were not set)
-    // its arrays and the first render's buffers on the device
-    if (int rc = upload_scene(c, P)) {
-        pt_destroy(c);
-        return bail(rc);
-    }
-    if (!alloc_bufs(c->rb[0]) || !create_flights(c)) {
-        pt_destroy(c);
-        return bail(pt::fail(PT_E_HIP, "pt_create: device allocation failed"));
-    }
-    if (err) *err = PT_OK;
-    timer.lap("uploads");
-    return c;
-}
-
-void pt_destroy(pt_ctx* c)
-{
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    void* bufs[] = {c->nodes, c->rnodes, c->tris_leaf, c->tris_orig, c->shade, c->mats,
-                    c->lights, c->jump, c->jump_bytes, c->shade_m, c->scratch_out,
-                    c->nodes4, c->acc_tris, c->rparent, c->hrec,
-                    c->tone_thr, c->spheres, c->tri_counts, c->emis, c->denoise.mem, c->session.dev};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    pt::free_pinned(c->session.host);
-    for (pt_ctx::Bufs& B : c->rb)
-        for (void* b : {(void*)B.spill, (void*)B.pix_states, (void*)B.lbuf, (void*)B.pmemo, (void*)B.counters,
-                        (void*)B.pixel_counter, (void*)B.tile_counter, (void*)B.seed_states})
-            if (b) (void)hipFree(b);
-    pt::free_pinned(c->pinned);
-    if (c->jump_ready) (void)hipEventDestroy(c->jump_ready);
-    for (pt_ctx::Flight& f : c->fl) {
-        for (hipEvent_t e : {f.ev0, f.ev1, f.ek0, f.ek1, f.done})
-            if (e) (void)hipEventDestroy(e);
-        if (f.hcnt) (void)hipHostFree(f.hcnt);
-    }
-    delete c;
-}
-
-// PT_LANE_TIMING summary of one wavefront render: wall-clock ticks (100 MHz) from the first wave's start
-// to the queue's drain (the first lane without a unit), to the mean and the last lane end, and to the
-// last wave exit; idle = the lane-time after each lane's end, as a fraction of lanes x kernel span.
-static void write_lane_timing(const char* path, const std::vector<unsigned long long>& t, size_t lanes, int shards)
-{
-    const size_t waves = lanes / 64;
-    unsigned long long t0 = ~0ull, drain = ~0ull, lend = 0, wexit = 0;
-    for (size_t w = 0; w < waves; ++w) {
-        if (t[lanes + w]) t0 = std::min(t0, t[lanes + w]);
-        wexit = std::max(wexit, t[lanes + waves + w]);
-    }
-    double sum = 0.0;
-    size_t n = 0;
-    for (size_t l = 0; l < lanes; ++l) {
-        if (!t[l]) continue;
-        drain = std::min(drain, t[l]);
-        lend = std::max(lend, t[l]);
-        sum += (double)(t[l] - t0);
-        ++n;
-    }
-    if (!n || t0 == ~0ull) return;
-    const double span = (double)(wexit - t0);
-    if (FILE* f = fopen(path, "a")) {
-        fprintf(f, "lane_timing shards %d lanes %zu span %.0f drain %.0f mean_end %.0f last_end %.0f idle_frac %.4f\n", shards,
-                n, span, (double)(drain - t0), sum / (double)n, (double)(lend - t0), 1.0 - (sum / (double)n) / span);
-        fclose(f);
-    }
-}
-
-// The scene half of Args: what every entry point's kernels read of the context's scene.  (Each entry sets its
-// own stack_words, node_mask and spill.)
-static void fill_scene_args(Args& a, const pt_ctx* c)
-{
-    a.nodes = c->nodes; a.rnodes = c->rnodes; a.tris_leaf = c->tris_leaf; a.tris_orig = c->tris_orig;
-    a.shade = c->shade; a.mats = c->mats; a.lights = c->lights; a.jump = c->jump; a.shade_m = c->shade_m;
-    a.num_lights = c->num_lights; a.total_light_area = c->total_light_area;
-    a.spheres = c->spheres; a.num_spheres = c->num_spheres; a.num_tris = c->num_tris;
-    a.sphere_mat_base = c->sphere_mat_base;
-    a.emis = c->emis; a.num_emis = c->num_emis;
-    memcpy(a.root, c->root, sizeof(a.root));
-    memcpy(a.acc_root, c->acc_root, sizeof(a.acc_root));
-    a.cull_rel = kCullRel;
-    a.cull_abs = c->scene_extent * 1e-4f;
-    a.origin_max = 64.0f * c->scene_extent;
-    a.scene_fast = c->scene_fast ? 1u : 0u;
-    a.nodes4 = c->nodes4;
-    a.acc_tris = c->acc_tris;
-    a.rparent = c->rparent;
-    a.hrec = c->hrec;
-}
-
-// The camera, the image and this shard's tile grid (validated parameters).
-static void fill_view_args(Args& a, const pt_params& p, const pt_camera& cam)
-{
-    a.cam.pos[0] = cam.pos.x; a.cam.pos[1] = cam.pos.y; a.cam.pos[2] = cam.pos.z;
-    a.cam.dist = cam.dist_from_film; a.cam.focal = cam.focal_length; a.cam.radius = cam.radius;
-    a.cam.w = cam.pxl_width; a.cam.h = cam.pxl_height;
-    const pt::TileGrid g = pt::tile_grid(p);
-    a.w = g.w; a.h = g.h;
-    a.shard_index = g.shard_index; a.shard_count = g.shard_count;
-    a.tiles_x = g.tiles_x; a.ntiles_shard = g.ntiles_shard;
-    a.tile_w = g.tile_w; a.tile_h = g.tile_h;
-    a.tile_bx = g.tile_bx; a.tile_blocks = g.tile_blocks;
-    a.morton_out = (p.pixel_order == PT_ORDER_MORTON) ? 1u : 0u;
-    a.npix = g.npix;
-}
-
-// One render enqueued on `stream` in the context's next flight slot: the body of pt_render_device_async.
-// acc: the render is a pass of an accumulator (pt::accum_pass) -- p->spp more samples of every pixel on top
-// of its acc->n0, from and to the accumulator's state; d_out may then be null.  Everything else -- the
-// unit split, the buffers' growth, the jump and seed tables, the flight slots -- is the plain render's.
-static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, float* d_out, void* stream_v,
-                          const pt::AccumPass* acc)
-{
-    if (!c || !p || !cam || (!d_out && !acc)) return pt::fail(PT_E_INVALID, "pt_render: null argument");
-    if (c->fl_n >= pt_ctx::kFlights)
-        return pt::fail(PT_E_INVALID, "pt_render_device_async: %d renders in flight (pt_render_wait first)", c->fl_n);
-    if (int rc = pt::validate_render(p, cam)) return rc;
-    // the per-triangle counts live in one context-wide buffer (pt_tri_counts reads it back): only one render
-    // in flight may fill them
-    if ((p->flags & PT_FLAG_COUNT) && (p->flags & PT_FLAG_TRI_COUNTS) && c->fl_n > 0)
-        return pt::fail(PT_E_INVALID, "pt_render_device_async: PT_FLAG_TRI_COUNTS while a render is in flight");
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
-    // this render's slot: its events and its buffer set.  The slot's previous render was collected by
-    // pt_render_wait (its events synchronised), so two queued renders -- on one stream or on two, where
-    // they may run concurrently -- never share a buffer.
-    const int slot = (c->fl_head + c->fl_n) % pt_ctx::kFlights;
-    pt_ctx::Flight& F = c->fl[slot];
-    pt_ctx::Bufs& B = c->rb[slot];
-    if (!alloc_bufs(B)) return pt::fail(PT_E_HIP, "pt_render: device allocation failed");
-    const pt::RenderKnobs& K = c->knobs;
-
-    Args a;
-    memset(&a, 0, sizeof(a));
-    fill_scene_args(a, c);
-    fill_view_args(a, *p, *cam);
-    a.out = d_out; a.counters = B.counters; a.tile_counter = B.tile_counter;
-    a.spp = p->spp; a.bounces = p->bounces; a.flags = p->flags; a.seed = p->seed;
-    const bool refwalk = (p->flags & PT_FLAG_REFERENCE_TRAVERSAL) != 0;
-    const bool count = (p->flags & PT_FLAG_COUNT) != 0;
-    const uint32_t levels = (uint32_t)c->depth + 2;
-    a.stack_words = std::max<uint32_t>(levels * 128, (uint32_t)kWaveLdsWords);   // (culled walk's stack, or the BVH4 rings)
-    const size_t lds = (size_t)a.stack_words * 4;
-    if (lds > 160 * 1024) return pt::fail(PT_E_BVH_DEPTH, "pt_render: BVH depth %d needs %zu B of LDS stack", c->depth, lds);
-
-    a.pixel_counter = B.pixel_counter;
-    a.nunits = a.npix;
-    a.wf_threshold = K.wf_threshold;
-    a.root_first = K.wf_root_first;
-    a.unit_queues = K.wf_queues;
-    a.wf_iters = K.wf_iters;
-    a.node_mask = c->node_mask;
-    const bool head = p->integrator == PT_INTEGRATOR_HEAD;
-    const bool wavefront = pt::takes_wavefront(p, cam, c->scene_extent, K.head_wf);
-    if (acc) {   // (pt_accum_create refused these already: never a silent fall-back to another kernel)
-        if (!wavefront || count || K.wf_min_waves != 5 || K.head_min_waves != 5)
-            return pt::fail(PT_E_INVALID, "pt_accum_add: this mode has no accumulating kernel");
-        if ((uint64_t)acc->n0 + (uint64_t)p->spp > kAccumMaxSamples)
-            return pt::fail(PT_E_INVALID, "pt_accum_add: %u + %d samples exceed what a unit word carries (%u)", acc->n0, p->spp,
-                            kAccumMaxSamples);
-        a.accum = 1u; a.acc_n0 = acc->n0; a.acc_rng = acc->rng; a.acc_mean = acc->mean;
-    }
-
-    // (the wavefront path's init_pixel_states resets the counters itself: one launch less per frame)
-    if (!(p->spp > 0 && a.ntiles_shard > 0 && wavefront)) {
-        HIP_TRY(hipMemsetAsync(B.counters, 0, kCounterWords * sizeof(unsigned long long), stream));
-        HIP_TRY(hipMemsetAsync(B.counters + CNT_T_START, 0xff, 2 * sizeof(unsigned long long), stream));   // (atomicMin slots)
-        HIP_TRY(hipMemsetAsync(B.tile_counter, 0, 16, stream));
-        HIP_TRY(hipMemsetAsync(B.pixel_counter, 0, kQueueStride * (kQueues + 1) * 4, stream));
-    }
-    if (count && (p->flags & PT_FLAG_TRI_COUNTS)) {   // per-triangle test counts of this render (pt_tri_counts)
-        HIP_TRY(hipMemsetAsync(c->tri_counts, 0, (size_t)std::max<uint32_t>(c->num_tris, 1u) * 4, stream));
-        a.tri_counts = c->tri_counts;
-    }
-    const uint32_t waves_per_cu = 16;
-    uint32_t grid = (uint32_t)c->num_cus * waves_per_cu;
-    if (grid > a.ntiles_shard * a.tile_blocks) grid = a.ntiles_shard > 0 ? a.ntiles_shard * a.tile_blocks : 1;
-    // the tile kernel traces with the render-path BVH4 walk under the wavefront kernel's conditions
-    // (PT_TILE_FAST4=0: the reference-BVH culled walk, as before)
-    a.tile_fast4 = (!refwalk && !(p->flags & PT_FLAG_REFERENCE_BVH) && pt::near_camera(cam, c->scene_extent) && K.tile_fast4 &&
-                    c->num_tris > 0) ? 1u : 0u;
-    HIP_TRY(hipEventRecord(F.ev0, stream));
-    bool kernel_events = false;   // ek0/ek1 recorded around the integration kernel (wavefront path)
-    bool seeded_now = false;      // seed_table enqueued for p->seed by this render
-    uint64_t units = 0, split = 0;
-    if (p->spp > 0 && a.ntiles_shard > 0 && wavefront) {
-        // 4 waves per block; per wave an LDS ring of kRing packed entries x 64 lanes, deeper
-        // entries spill to HBM (a BVH4 walk pushes at most 3 entries per level)
-        Args b = a;
-        b.stack_words = kRing * 64;
-        b.node_mask = c->node4_mask;
-        b.head = head ? 1u : 0u;
-        // the launch and the work units (render_plan.cpp)
-        pt::PlanInput in;
-        in.num_cus = c->num_cus; in.npix = a.npix; in.spp = p->spp; in.head = head; in.count = count;
-        in.top_nodes = c->top_nodes;
-        in.lds_fixed = (size_t)kWaveLdsWords * 4 * 4 + 4 * sizeof(unsigned long long) + (kSections + kHist) * 4 +
-                       kProbeLdsBytes + (head ? (size_t)kHeadLdsLightBytes : 0);
-        in.top_node_bytes = kTopNodeBytes;
-        pt::UnitPlan plan;
-        // (default budget: a quarter of the device memory free now, plus what lbuf already holds)
-        auto lbuf_budget = [&B](uint64_t* bytes) -> int {
-            size_t fr = 0, tot = 0;
-            HIP_TRY(hipMemGetInfo(&fr, &tot));
-            *bytes = ((uint64_t)fr + (uint64_t)B.lbuf_words * sizeof(double)) / 4;
-            return PT_OK;
-        };
-        if (acc && acc->active) in.npix = acc->nactive;   // (the launch is sized by the units it has)
-        if (int rc = pt::plan_units(in, K, lbuf_budget, &plan)) return rc;
-        if (acc && acc->active) {
-            // an adaptive pass: unit u = the whole pixel of slot active[u], no sample-chunk split (npix stays the
-            // shard's slot count: the stride of the accumulator's planes)
-            if (acc->nactive == 0 || acc->nactive > a.npix) return pt::fail(PT_E_INVALID, "pt_accum_add: active list of %u slots", acc->nactive);
-            plan.nwhole = plan.nunits = acc->nactive;
-            plan.ntail = plan.nmid = plan.nfin = 0;
-            plan.chunks = plan.chunks_mid = plan.chunks_fin = 1;
-            plan.blocks = std::min(plan.blocks, (acc->nactive + 255u) / 256u);
-        }
-        const uint32_t blocks = plan.blocks, ntail = plan.ntail;
-        const uint32_t paths_per_block = 256u;
-        b.top_nodes = plan.top_nodes;
-        b.nwhole = plan.nwhole; b.ntail = plan.ntail; b.nmid = plan.nmid; b.chunks_mid = plan.chunks_mid;
-        b.chunks = plan.chunks; b.nfin = plan.nfin; b.chunks_fin = plan.chunks_fin; b.nunits = plan.nunits;
-        const size_t lds_wf = in.lds_fixed + (size_t)b.top_nodes * kTopNodeBytes;
-        // the whole tree staged in LDS (small scenes: C2): integrator 0's walk steps read it there too
-        // (PT_WF_LDS_TREE=0: memory loads, as for a tree larger than the top)
-        const bool lds_tree = K.wf_lds_tree && c->n4 > 0 && b.top_nodes >= c->n4;
-        // (C2: 7181 with the record's second fetch against 7267 by triangle id; C3 the other way)
-        b.rec_shading = lds_tree ? 0u : 1u;
-        // the buffers the units need, grown on demand
-        if (ntail > 0) {
-            if (int rc = grow(&B.lbuf, &B.lbuf_words, (size_t)ntail * (size_t)p->spp * 3)) return rc;
-            if (int rc = grow(&B.pmemo, &B.pmemo_words, (size_t)ntail * 2)) return rc;
-            b.lbuf = B.lbuf;
-            b.pmemo = B.pmemo;
-        }
-        const size_t per_lane = stack_words_per_lane(c);
-        const size_t rec_words = head ? (size_t)kHeadWords : (size_t)kColdWords;   // shading record per lane
-        if (int rc = grow(&B.spill, &B.spill_words, per_lane * (size_t)blocks * 256 + rec_words * (size_t)blocks * paths_per_block))
-            return rc;
-        b.spill = B.spill;
-        b.spill_stride = blocks * 256;
-        b.cold_stride = blocks * paths_per_block;
-        b.cold = B.spill + per_lane * (size_t)b.spill_stride;
-        if (int rc = grow(&B.pix_states, &B.pix_states_words, (size_t)kUnitWords * b.nunits)) return rc;
-        b.pix_states = B.pix_states;
-        // diagnostic: per-lane end / per-wave start and exit times (PT_LANE_TIMING=file appends a summary)
-        const char* timing_path = getenv("PT_LANE_TIMING");
-        std::vector<unsigned long long> times;
-        unsigned long long* d_times = nullptr;
-        if (timing_path) {
-            times.assign((size_t)blocks * 256 + 2 * (size_t)blocks * 4, 0ull);
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_times), times.size() * 8));
-            HIP_TRY(hipMemsetAsync(d_times, 0, times.size() * 8, stream));
-            b.lane_times = d_times;
-        }
-        if (K.use_jump_bytes) {
-            if (!c->jump_bytes) {   // once per context: 512 byte-sliced 160x160 GF(2) matrices (84 MB)
-                // (built into locals and published only once the build launched: a failure leaves the
-                // context without tables, so the next render tries again instead of seeding from garbage)
-                // (a render queued on another stream meanwhile waits for the build: jump_ready)
-                uint32_t* jb = nullptr;
-                const bool ok = hipMalloc(reinterpret_cast<void**>(&jb), (size_t)512 * 20 * 256 * kJumpEntryWords * 4) == hipSuccess &&
-                                (c->jump_ready || hipEventCreateWithFlags(&c->jump_ready, hipEventDisableTiming) == hipSuccess);
-                if (ok) hipLaunchKernelGGL(build_jump_byte_tables, dim3(512 * 20), dim3(256), 0, stream, c->jump, jb);
-                if (!ok || hipGetLastError() != hipSuccess || hipEventRecord(c->jump_ready, stream) != hipSuccess) {
-                    if (jb) (void)hipFree(jb);
-                    return pt::fail(ok ? PT_E_HIP : PT_E_OOM, "pt_render: jump-table setup failed");
-                }
-                c->jump_bytes = jb;
-            } else {
-                HIP_TRY(hipStreamWaitEvent(stream, c->jump_ready, 0));
-            }
-            if (!B.seed_states) {
-                HIP_TRY(hipMalloc(reinterpret_cast<void**>(&B.seed_states), (size_t)256 * kJumpEntryWords * 4));
-                B.seed_valid = false;
-            }
-            if (!B.seed_valid || B.seed_cached != p->seed) {   // (depends on the seed only: kept across renders)
-                // (marked valid only once the whole render is enqueued: any error return below leaves the
-                // slot unseeded, so the next render seeds again instead of trusting a table never written)
-                B.seed_valid = false;
-                hipLaunchKernelGGL(seed_table, dim3(1), dim3(256), 0, stream, b, B.seed_states);
-                HIP_TRY(hipGetLastError());
-                seeded_now = true;
-            }
-            b.jump_bytes = c->jump_bytes;
-            b.seed_states = B.seed_states;
-        }
-        if (acc && acc->active)
-            hipLaunchKernelGGL(init_active_states, dim3((b.nunits + 255) / 256), dim3(256), 0, stream, b, B.pix_states, acc->active);
-        else
-            hipLaunchKernelGGL(init_pixel_states, dim3((b.npix + 255) / 256), dim3(256), 0, stream, b, B.pix_states);
-        // A render queued on another stream while one is in flight: its seeding pre-pass runs beside the
-        // earlier render's last waves (its own buffers), but the integration kernel waits until the earlier
-        // render is complete (finalisation included), so a persistent grid never takes the CU slots an
-        // earlier frame's finalisation needs (that one would otherwise wait out the whole next frame)
-        if (c->fl_n > 0) HIP_TRY(hipStreamWaitEvent(stream, c->fl[(c->fl_head + c->fl_n - 1) % pt_ctx::kFlights].ev1, 0));
-        HIP_TRY(hipEventRecord(F.ek0, stream));
-        kernel_events = true;
-        units = b.nunits;
-        split = b.ntail;
-        if (acc) {   // the accumulating instances: default occupancy, no counting
-            if (head) hipLaunchKernelGGL(render_head_accum_wf, dim3(blocks), dim3(256), lds_wf, stream, b);
-            else if (lds_tree) hipLaunchKernelGGL(render_unidir_accum_wf<true>, dim3(blocks), dim3(256), lds_wf, stream, b);
-            else hipLaunchKernelGGL(render_unidir_accum_wf<false>, dim3(blocks), dim3(256), lds_wf, stream, b);
-        }
-        else if (head) {
-            if (count) hipLaunchKernelGGL((render_head_wf<true, 5>), dim3(blocks), dim3(256), lds_wf, stream, b);
-            else if (K.head_min_waves == 4) hipLaunchKernelGGL((render_head_wf<false, 4>), dim3(blocks), dim3(256), lds_wf, stream, b);
-            else hipLaunchKernelGGL((render_head_wf<false, 5>), dim3(blocks), dim3(256), lds_wf, stream, b);
-        }
-        else if (count && K.wf_min_waves == 4) hipLaunchKernelGGL((render_unidir_wf<true, 4>), dim3(blocks), dim3(256), lds_wf, stream, b);
-        else if (count && lds_tree) hipLaunchKernelGGL((render_unidir_wf<true, 5, true>), dim3(blocks), dim3(256), lds_wf, stream, b);
-        else if (count) hipLaunchKernelGGL((render_unidir_wf<true, 5>), dim3(blocks), dim3(256), lds_wf, stream, b);
-        else if (K.wf_min_waves == 6) hipLaunchKernelGGL((render_unidir_wf<false, 6>), dim3(blocks), dim3(256), lds_wf, stream, b);
-        else if (K.wf_min_waves == 5 && lds_tree) hipLaunchKernelGGL((render_unidir_wf<false, 5, true>), dim3(blocks), dim3(256), lds_wf, stream, b);
-        else if (K.wf_min_waves == 5) hipLaunchKernelGGL((render_unidir_wf<false, 5>), dim3(blocks), dim3(256), lds_wf, stream, b);
-        else hipLaunchKernelGGL((render_unidir_wf<false, 4>), dim3(blocks), dim3(256), lds_wf, stream, b);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(F.ek1, stream));
-        if (b.ntail > 0) hipLaunchKernelGGL(finalize_pixels, dim3((b.ntail + 255) / 256), dim3(256), 0, stream, b);
-        HIP_TRY(hipGetLastError());
-        if (d_times) {
-            HIP_TRY(hipMemcpyAsync(times.data(), d_times, times.size() * 8, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-            (void)hipFree(d_times);
-            write_lane_timing(timing_path, times, (size_t)blocks * 256, p->shard_count);
-        }
-    } else if (p->spp > 0 && a.ntiles_shard > 0) {
-        if (a.tile_fast4) {   // the BVH4 walk's ring overflow and the slow walk's stack: one HBM column per lane
-            if (int rc = grow(&B.spill, &B.spill_words, stack_words_per_lane(c) * (size_t)grid * 64)) return rc;
-            a.spill = B.spill;
-            a.spill_stride = grid * 64;
-        }
-#define PT_LAUNCH(I, R, C) hipLaunchKernelGGL((render_tiles<I, R, C>), dim3(grid), dim3(64), lds, stream, a)
-        if (p->integrator == PT_INTEGRATOR_HEAD) {
-            if (refwalk) { if (count) PT_LAUNCH(1, true, true); else PT_LAUNCH(1, true, false); }
-            else { if (count) PT_LAUNCH(1, false, true); else PT_LAUNCH(1, false, false); }
-        } else {
-            if (refwalk) { if (count) PT_LAUNCH(0, true, true); else PT_LAUNCH(0, true, false); }
-            else { if (count) PT_LAUNCH(0, false, true); else PT_LAUNCH(0, false, false); }
-        }
-#undef PT_LAUNCH
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(F.ev1, stream));
-    HIP_TRY(hipMemcpyAsync(F.hcnt, B.counters, kCounterWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipEventRecord(F.done, stream));
-    F.kernel_events = kernel_events;
-    F.count = count;
-    F.units = units;
-    F.split = split;
-    F.spp = p->spp;
-    F.bounces = p->bounces;
-    if (seeded_now) {
-        B.seed_cached = p->seed;
-        B.seed_valid = true;
-    }
-    ++c->fl_n;
-    return PT_OK;
-}
-
-int pt_render_device_async(pt_ctx* c, const pt_params* p, const pt_camera* cam, float* d_out, void* stream_v)
-{
-    if (!d_out) return pt::fail(PT_E_INVALID, "pt_render: null argument");
-    return render_enqueue(c, p, cam, d_out, stream_v, nullptr);
-}
-
-int pt_render_wait(pt_ctx* c, pt_stats* st)
-{
-    if (!c) return pt::fail(PT_E_INVALID, "pt_render_wait: null context");
-    if (c->fl_n == 0) return pt::fail(PT_E_INVALID, "pt_render_wait: no render in flight");
-    HIP_TRY(hipSetDevice(c->device));
-    pt_ctx::Flight& F = c->fl[c->fl_head];
-    c->fl_head = (c->fl_head + 1) % pt_ctx::kFlights;
-    --c->fl_n;
-    // (the counters' copy is the render's last operation on its stream)
-    HIP_TRY(hipEventSynchronize(F.done));
-    const unsigned long long* cnt = F.hcnt;
-    if (F.count) {
-        if (const char* path = getenv("PT_SECTION_DUMP")) {   // counting runs: shading section profile
-            if (FILE* f = fopen(path, "a")) {
-                fprintf(f, "sections");
-                for (int k = 0; k < kSections; ++k) fprintf(f, " %llu", cnt[CNT_SECTIONS + k]);
-                fprintf(f, "\nwalk_hist");
-                for (int k = 0; k < kHist; ++k) fprintf(f, " %llu", cnt[CNT_SECTIONS + kSections + k]);
-                fprintf(f, "\ntrace_slots %llu walk_slots %llu nodes %llu leaf_steps %llu start_wait %llu top_visits %llu\n", cnt[CNT_TRACE_SLOTS], cnt[CNT_WALK_SLOTS],
-                        cnt[CNT_NODES], cnt[CNT_LEAF_STEPS], cnt[CNT_START_WAIT], cnt[CNT_TOP_VISITS]);
-                fprintf(f, "wall_clock start %llu drained %llu last_exit %llu mean_exit %.1f waves %llu (ticks)\n", cnt[CNT_T_START], cnt[CNT_T_DRAINED],
-                        cnt[CNT_T_LAST_EXIT], cnt[CNT_WAVES] ? (double)cnt[CNT_T_EXIT_SUM] / (double)cnt[CNT_WAVES] : 0.0, cnt[CNT_WAVES]);
-                fprintf(f, "lane_end_mean %.1f (ticks since start)\ntail_lane_end_log2_10us",
-                        cnt[CNT_WAVES] ? (double)cnt[CNT_LANE_END_SUM] / (64.0 * (double)cnt[CNT_WAVES]) : 0.0);
-                for (int k = 0; k < kTailBins; ++k) fprintf(f, " %llu", cnt[CNT_LANE_BINS + k]);
-                fprintf(f, "\ntail_wave_exit_log2_10us");
-                for (int k = 0; k < kTailBins; ++k) fprintf(f, " %llu", cnt[CNT_WAVE_BINS + k]);
-                fprintf(f, "\niters_by_deep_lanes 0:%llu 1-4:%llu 5-8:%llu more:%llu no_leaf %llu neither %llu\n", cnt[CNT_ITERS],
-                        cnt[CNT_ITERS + 1], cnt[CNT_ITERS + 2], cnt[CNT_ITERS + 3], cnt[CNT_ITERS + 4], cnt[CNT_ITERS + 5]);
-                fclose(f);
-            }
-        }
-    }
-    float ms = 0.0f, kms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, F.ev0, F.ev1));
-    if (F.kernel_events) HIP_TRY(hipEventElapsedTime(&kms, F.ek0, F.ek1));
-    else kms = ms;   // (the tile kernel is the render's only launch)
-    if (st) {
-        st->seconds = ms * 1e-3;
-        st->kernel_ms = kms;
-        st->work_units = F.units;
-        st->split_pixels = F.split;
-        st->rays_traced = cnt[CNT_TRACED];
-        st->rays_reference = cnt[CNT_REFERENCE];
-        st->node_tests = cnt[CNT_NODES];
-        st->tri_tests = cnt[CNT_TRIS];
-        st->samples = cnt[CNT_SAMPLES];
-        st->walk_lane_slots = cnt[CNT_WALK_SLOTS];
-        st->leaf_steps = cnt[CNT_LEAF_STEPS];
-        st->shade_lane_slots = cnt[CNT_SHADE_SLOTS];
-        st->accel_fallbacks = cnt[CNT_FALLBACKS];
-        st->walk_cycles = cnt[CNT_WALK_CYCLES];
-        st->shade_cycles = cnt[CNT_SHADE_CYCLES];
-        st->spill_entries = cnt[CNT_SPILL];
-        st->lds_node_tests = cnt[CNT_TOP_VISITS];
-        const uint64_t shard_px = cnt[CNT_SAMPLES] / (uint64_t)(F.spp > 0 ? F.spp : 1);
-        st->rays_nominal = shard_px * (uint64_t)F.spp * (uint64_t)(F.bounces + 1);
-    }
-    return PT_OK;
-}
-
-int pt_render_device(pt_ctx* c, const pt_params* p, const pt_camera* cam, float* d_out, void* stream, pt_stats* st)
-{
-    if (c && c->fl_n > 0)
-        return pt::fail(PT_E_INVALID, "pt_render_device: %d asynchronous renders in flight (pt_render_wait first)", c->fl_n);
-    if (int rc = pt_render_device_async(c, p, cam, d_out, stream)) return rc;
-    return pt_render_wait(c, st);
-}
-
-}  // extern "C"
-
-// ---- accumulating passes (host_internal.h): the render context's side of pt_accum.cpp
-int pt::accum_check(const pt_ctx* c, const pt_params* p, const pt_camera* cam)
-{
-    if (int rc = validate_render(p, cam)) return rc;
-    const RenderKnobs& K = c->knobs;
-    if (p->flags & ~(uint32_t)(PT_FLAG_NO_DEAD_PATH_SKIP | PT_FLAG_NO_PRIMARY_CACHE))
-        return pt::fail(PT_E_INVALID, "pt_accum_create: flags 0x%x: only PT_FLAG_NO_DEAD_PATH_SKIP and PT_FLAG_NO_PRIMARY_CACHE "
-                        "accumulate (the reference walks and the counting variants have no accumulating kernel)", p->flags);
-    if (!takes_wavefront(p, cam, c->scene_extent, K.head_wf))
-        return pt::fail(PT_E_INVALID, "pt_accum_create: this render would take the tile kernel (%s), which does not accumulate",
-                        (p->integrator == PT_INTEGRATOR_HEAD && !K.head_wf) ? "integrator 1 with PT_HEAD_WF=0"
-                                                                              : "camera beyond 64 scene extents");
-    if (K.wf_min_waves != 5 || K.head_min_waves != 5)
-        return pt::fail(PT_E_INVALID, "pt_accum_create: only the default-occupancy kernels accumulate (PT_WF_MIN_WAVES / "
-                        "PT_HEAD_MIN_WAVES are set)");
-    return PT_OK;
-}
-
-int pt::accum_pass(pt_ctx* c, const pt_params* p, const pt_camera* cam, const AccumPass& acc, float* d_out, void* stream,
-                   pt_stats* stats)
-{
-    if (c->fl_n > 0)
-        return pt::fail(PT_E_INVALID, "pt_accum_add: %d asynchronous renders in flight (pt_render_wait first)", c->fl_n);
-    if (int rc = render_enqueue(c, p, cam, d_out, stream, &acc)) return rc;
-    return pt_render_wait(c, stats);
-}
-
-void pt::ctx_scene_id(const pt_ctx* c, uint64_t* digest, uint32_t* num_tris, uint32_t* num_spheres)
-{
-    *digest = c->scene_digest;
-    *num_tris = c->num_tris;
-    *num_spheres = c->scene_spheres;
-}
-int pt::ctx_in_flight(const pt_ctx* c) { return c->fl_n; }
-pt::DenoiseScratch* pt::ctx_denoise_scratch(pt_ctx* c) { return &c->denoise; }
-pt::SessionScratch* pt::ctx_session_scratch(pt_ctx* c) { return &c->session; }
-int pt::ctx_num_cus(const pt_ctx* c) { return c->num_cus; }
-uint32_t pt::accum_max_samples() { return kAccumMaxSamples; }
-
-int pt::copy_to_host(void* dst, const void* src, size_t bytes, void* stream_v, void** pinned, size_t* pinned_bytes)
-{
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
-    if (*pinned_bytes < bytes) {
-        free_pinned(*pinned);
-        *pinned = nullptr;
-        *pinned_bytes = 0;
-        if (hipHostMalloc(pinned, bytes, hipHostMallocDefault) != hipSuccess) {
-            *pinned = nullptr;   // (no pinned memory: the runtime's own pageable path)
-            HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-            return PT_OK;
-        }
-        *pinned_bytes = bytes;
-    }
-    HIP_TRY(hipMemcpyAsync(*pinned, src, bytes, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    const unsigned nt = (unsigned)std::min<size_t>(pt::host_threads(), std::max<size_t>(1, bytes >> 21));   // >= 2 MB each
-    const char* s = static_cast<const char*>(*pinned);
-    char* d = static_cast<char*>(dst);
-    auto part = [&](unsigned k) {
-        const size_t b0 = (bytes * k / nt) & ~(size_t)4095, b1 = (k + 1 == nt) ? bytes : ((bytes * (k + 1) / nt) & ~(size_t)4095);
-        memcpy(d + b0, s + b0, b1 - b0);
-    };
-    if (nt <= 1) {
-        memcpy(d, s, bytes);
-    } else {
-        std::vector<std::thread> th;
-        th.reserve(nt - 1);
-        for (unsigned k = 1; k < nt; ++k) th.emplace_back(part, k);
-        part(0);
-        for (std::thread& t : th) t.join();
-    }
-    return PT_OK;
-}
-
-void pt::free_pinned(void* p)
-{
-    if (p) (void)hipHostFree(p);
-}
-
-extern "C" {
-
-int pt_render(pt_ctx* c, const pt_params* p, const pt_camera* cam, float* out_rgb, pt_stats* st)
-{
-    if (!c || !p || !out_rgb) return pt::fail(PT_E_INVALID, "pt_render: null argument");
-    if (p->width <= 0 || p->height <= 0) return pt::fail(PT_E_INVALID, "pt_render: bad image size");
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t bytes = (size_t)p->width * (size_t)p->height * 3 * sizeof(float);
-    if (int rc = grow(&c->scratch_out, &c->scratch_floats, bytes / sizeof(float))) return rc;
-    HIP_TRY(hipMemsetAsync(c->scratch_out, 0, bytes, nullptr));
-    int rc = pt_render_device(c, p, cam, c->scratch_out, nullptr, st);
-    if (rc != PT_OK) return rc;
-    return pt::copy_to_host(out_rgb, c->scratch_out, bytes, nullptr, &c->pinned, &c->pinned_bytes);
-}
-
-}  // extern "C"
-
-static size_t stack_words_per_lane(const pt_ctx* c)
-{
-    size_t per_lane = (size_t)(3 * c->acc4_depth + 4);
-    if (per_lane < (size_t)(2 * (c->depth + 2))) per_lane = (size_t)(2 * (c->depth + 2));
-    return per_lane;
-}
-
-static bool alloc_bufs(pt_ctx::Bufs& B)
-{
-    if (B.counters && B.tile_counter && B.pixel_counter) return true;
-    // (all three or none: a partial failure is released, so the next call allocates again)
-    for (void** q : {reinterpret_cast<void**>(&B.counters), reinterpret_cast<void**>(&B.tile_counter),
-                     reinterpret_cast<void**>(&B.pixel_counter)})
-        if (*q) { (void)hipFree(*q); *q = nullptr; }
-    if (hipMalloc(reinterpret_cast<void**>(&B.counters), kCounterWords * sizeof(unsigned long long)) == hipSuccess &&
-        hipMalloc(reinterpret_cast<void**>(&B.tile_counter), 16) == hipSuccess &&
-        hipMalloc(reinterpret_cast<void**>(&B.pixel_counter), kQueueStride * (kQueues + 1) * 4) == hipSuccess)
-        return true;
-    for (void** q : {reinterpret_cast<void**>(&B.counters), reinterpret_cast<void**>(&B.tile_counter),
-                     reinterpret_cast<void**>(&B.pixel_counter)})
-        if (*q) { (void)hipFree(*q); *q = nullptr; }
-    return false;
-}
-
-extern "C" int pt_trace(pt_ctx* c, uint32_t n, const float* rays, int32_t* tri_out, float* t_out, uint32_t flags)
-{
-    return pt_trace_counts(c, n, rays, tri_out, t_out, flags, nullptr, nullptr);
-}
-
-extern "C" int pt_tri_counts(pt_ctx* c, uint32_t* counts, uint32_t n)
-{
-    pt::clear_error();
-    if (!c || !counts) return pt::fail(PT_E_INVALID, "pt_tri_counts: null argument");
-    if (c->fl_n > 0) return pt::fail(PT_E_INVALID, "pt_tri_counts: renders in flight (pt_render_wait first)");
-    if (n != c->num_tris) return pt::fail(PT_E_INVALID, "pt_tri_counts: n = %u, the scene has %u triangles", n, c->num_tris);
-    if (n == 0) return PT_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpy(counts, c->tri_counts, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-extern "C" int pt_trace_counts(pt_ctx* c, uint32_t n, const float* rays, int32_t* tri_out, float* t_out, uint32_t flags,
-                               uint32_t* tri_counts, uint64_t* spill_entries)
-{
-    pt::clear_error();
-    if (!c) return pt::fail(PT_E_INVALID, "pt_trace: null context");
-    if (c->fl_n > 0) return pt::fail(PT_E_INVALID, "pt_trace: renders in flight (pt_render_wait first)");
-    if (n == 0) return PT_OK;
-    if (!rays || !tri_out || !t_out) return pt::fail(PT_E_INVALID, "pt_trace: null buffer");
-    HIP_TRY(hipSetDevice(c->device));
-    Args a;
-    memset(&a, 0, sizeof(a));
-    fill_scene_args(a, c);
-    a.counters = c->rb[0].counters;
-    a.node_mask = c->node4_mask;
-    a.stack_words = (uint32_t)(c->depth + 2) * 64;
-    if (a.stack_words < (uint32_t)kWaveLdsWords) a.stack_words = kWaveLdsWords;
-    const size_t lds = (size_t)a.stack_words * 4 * 4;
-    if (lds > 160 * 1024) return pt::fail(PT_E_BVH_DEPTH, "pt_trace: BVH depth %d too deep for the LDS stack", c->depth);
-    uint32_t blocks = (n + 255) / 256;
-    const uint32_t cap = (uint32_t)c->num_cus * 8u;
-    if (blocks > cap) blocks = cap;
-    if (int rc = grow(&c->rb[0].spill, &c->rb[0].spill_words, stack_words_per_lane(c) * (size_t)blocks * 256)) return rc;
-    a.spill = c->rb[0].spill;
-    a.spill_stride = blocks * 256;
-    float* d_rays = nullptr;
-    int32_t* d_tri = nullptr;
-    float* d_t = nullptr;
-    uint32_t* d_cnt = nullptr;
-    int rc = PT_OK;
-    auto run = [&]() -> int {
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_rays), (size_t)n * 24));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_tri), (size_t)n * 4));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_t), (size_t)n * 4));
-        HIP_TRY(hipMemcpy(d_rays, rays, (size_t)n * 24, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(c->rb[0].counters, 0, kCounterWords * sizeof(unsigned long long)));
-        const bool count = tri_counts != nullptr || spill_entries != nullptr;
-        if (tri_counts && c->num_tris > 0) {   // (own scratch: the last render's counts stay for pt_tri_counts)
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_cnt), (size_t)c->num_tris * 4));
-            HIP_TRY(hipMemset(d_cnt, 0, (size_t)c->num_tris * 4));
-            a.tri_counts = d_cnt;
-        }
-        const bool ref = (flags & PT_FLAG_REFERENCE_BVH) != 0;
-        if (ref && count) hipLaunchKernelGGL((trace_rays<true, true>), dim3(blocks), dim3(256), lds, 0, a, d_rays, n, d_tri, d_t);
-        else if (ref) hipLaunchKernelGGL((trace_rays<true, false>), dim3(blocks), dim3(256), lds, 0, a, d_rays, n, d_tri, d_t);
-        else if (count) hipLaunchKernelGGL((trace_rays<false, true>), dim3(blocks), dim3(256), lds, 0, a, d_rays, n, d_tri, d_t);
-        else hipLaunchKernelGGL((trace_rays<false, false>), dim3(blocks), dim3(256), lds, 0, a, d_rays, n, d_tri, d_t);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(tri_out, d_tri, (size_t)n * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(t_out, d_t, (size_t)n * 4, hipMemcpyDeviceToHost));
-        if (tri_counts && c->num_tris > 0) {   // added to the caller's counts (kernel.cu:133 accumulates)
-            std::vector<uint32_t> h(c->num_tris);
-            HIP_TRY(hipMemcpy(h.data(), d_cnt, (size_t)c->num_tris * 4, hipMemcpyDeviceToHost));
-            for (uint32_t k = 0; k < c->num_tris; ++k) tri_counts[k] += h[k];
-        }
-        if (spill_entries) {
-            unsigned long long v = 0;
-            HIP_TRY(hipMemcpy(&v, c->rb[0].counters + CNT_SPILL, sizeof(v), hipMemcpyDeviceToHost));
-            *spill_entries = v;
-        }
-        return PT_OK;
-    };
-    rc = run();
-    if (d_rays) (void)hipFree(d_rays);
-    if (d_tri) (void)hipFree(d_tri);
-    if (d_t) (void)hipFree(d_t);
-    if (d_cnt) (void)hipFree(d_cnt);
-    return rc;
-}
-
-// What pt_render_features* checks before touching the device; *vp = params with the ignored fields neutral.
-static int features_check(const pt_ctx* c, const pt_params* p, const pt_camera* cam, const void* feat, pt_params* vp)
-{
-    if (!c || !p || !cam || !feat) return pt::fail(PT_E_INVALID, "pt_render_features: null argument");
-    if (c->fl_n > 0)
-        return pt::fail(PT_E_INVALID, "pt_render_features: %d asynchronous renders in flight (pt_render_wait first)", c->fl_n);
-    *vp = *p;
-    vp->spp = 0; vp->bounces = 1; vp->integrator = PT_INTEGRATOR_UNIDIR; vp->flags = 0; vp->seed = 0;
-    if (int rc = pt::validate_render(vp, cam)) return rc;
-    if ((uint64_t)c->num_tris + (uint64_t)c->num_spheres >= (uint64_t)PT_FEATURE_EMISSIVE)
-        return pt::fail(PT_E_INVALID, "pt_render_features: %u triangles + %u spheres do not fit the 30 id bits of pt_feature.prim",
-                        c->num_tris, c->num_spheres);
-    return PT_OK;
-}
-
-extern "C" int pt_render_features_device(pt_ctx* c, const pt_params* p_in, const pt_camera* cam, pt_feature* d_feat, void* stream_v)
-{
-    pt::clear_error();
-    static_assert(sizeof(pt_feature) == 48, "pt_feature is 48 B");
-    pt_params pv;
-    if (int rc = features_check(c, p_in, cam, d_feat, &pv)) return rc;
-    if (reinterpret_cast<uintptr_t>(d_feat) % 16 != 0)
-        return pt::fail(PT_E_INVALID, "pt_render_features_device: d_feat must be 16-byte aligned");
-    const pt_params* p = &pv;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
-    Args a;
-    memset(&a, 0, sizeof(a));
-    fill_scene_args(a, c);
-    fill_view_args(a, *p, *cam);
-    a.node_mask = c->node4_mask;
-    a.stack_words = kWaveLdsWords;
-    const size_t lds = (size_t)a.stack_words * 4 * 4;
-    if (a.npix == 0) return PT_OK;
-    uint32_t blocks = (uint32_t)(((uint64_t)a.npix + 255) / 256);
-    const uint32_t cap = (uint32_t)c->num_cus * 8u;
-    if (blocks > cap) blocks = cap;
-    if (int rc = grow(&c->rb[0].spill, &c->rb[0].spill_words, stack_words_per_lane(c) * (size_t)blocks * 256)) return rc;
-    a.spill = c->rb[0].spill;
-    a.spill_stride = blocks * 256;
-    hipLaunchKernelGGL(primary_features, dim3(blocks), dim3(256), lds, stream, a, reinterpret_cast<float4*>(d_feat));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
-    return PT_OK;
-}
-
-extern "C" int pt_render_features(pt_ctx* c, const pt_params* p, const pt_camera* cam, pt_feature* feat)
-{
-    pt::clear_error();
-    pt_params pv;
-    if (int rc = features_check(c, p, cam, feat, &pv)) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t n = (size_t)p->width * (size_t)p->height;
-    pt_feature none;
-    memset(&none, 0, sizeof(none));
-    none.prim = -1;
-    for (size_t i = 0; i < n; ++i) feat[i] = none;   // pixels outside the shard stay like this
-    pt_feature* d_feat = nullptr;
-    auto run = [&]() -> int {
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_feat), n * sizeof(pt_feature)));
-        HIP_TRY(hipMemcpy(d_feat, feat, n * sizeof(pt_feature), hipMemcpyHostToDevice));
-        if (int rc = pt_render_features_device(c, p, cam, d_feat, nullptr)) return rc;
-        HIP_TRY(hipMemcpy(feat, d_feat, n * sizeof(pt_feature), hipMemcpyDeviceToHost));
-        return PT_OK;
-    };
-    const int rc = run();
-    if (d_feat) (void)hipFree(d_feat);
-    return rc;
-}
-
-extern "C" int pt_shard_pixels(int w, int h, int shard_index, int shard_count, int tile_w, int tile_h, uint32_t* out,
-                               uint32_t cap, uint32_t* n_out)
-{
-    pt::clear_error();
-    if (w <= 0 || h <= 0 || w > 65535 || h > 65535 || shard_count < 1 || shard_index < 0 || shard_index >= shard_count || !n_out)
-        return pt::fail(PT_E_INVALID, "pt_shard_pixels: bad arguments");
-    for (const int v : {tile_w, tile_h})
-        if (v != 0 && (v < 8 || v > 256 || v % 8 != 0)) return pt::fail(PT_E_INVALID, "pt_shard_pixels: tile size %dx%d", tile_w, tile_h);
-    pt_params p;
-    memset(&p, 0, sizeof(p));
-    p.width = w; p.height = h; p.shard_index = shard_index; p.shard_count = shard_count; p.tile_w = tile_w; p.tile_h = tile_h;
-    const pt::TileGrid m = pt::tile_grid(p);
-    if (!m.fits()) return pt::fail(PT_E_INVALID, "pt_shard_pixels: %dx%d pads to more than 2^32-1 pixel slots", w, h);
-    const uint64_t slots = m.npix;
-    uint32_t n = 0;
-    for (uint64_t q = 0; q < slots; ++q) {
-        uint32_t px, py;
-        if (!unit_pixel(m, (uint32_t)q, &px, &py)) continue;
-        if (out) {
-            if (n >= cap) return pt::fail(PT_E_INVALID, "pt_shard_pixels: buffer of %u entries too small", cap);
-            out[n] = py * (uint32_t)w + px;
-        }
-        ++n;
-    }
-    *n_out = n;
-    return PT_OK;
-}
-
-int pt::shard_slots(const pt_params* p, std::vector<uint32_t>* pix)
-{
-    const pt::TileGrid m = pt::tile_grid(*p);
-    const size_t slots = m.npix;   // (= Args::npix of this shard's renders)
-    pix->assign(slots, 0xffffffffu);
-    for (size_t q = 0; q < slots; ++q) {
-        uint32_t px, py;
-        if (unit_pixel(m, (uint32_t)q, &px, &py)) (*pix)[q] = py * (uint32_t)p->width + px;
-    }
-    return PT_OK;
-}
-
-extern "C" int pt_tonemap_device(pt_ctx* c, const float* d_rgb, int w, int h, int32_t* d_codes, void* stream_v)
-{
-    pt::clear_error();
-    if (!c || !d_rgb || !d_codes || w <= 0 || h <= 0) return pt::fail(PT_E_INVALID, "pt_tonemap_device: bad arguments");
-    if (!c->tone_ok) return pt::fail(PT_E_INVALID, "pt_tonemap_device: host tone map not monotone; use pt_tonemap_u8");
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
-    const size_t n = (size_t)w * (size_t)h * 3;
-    size_t blocks = (n + 255) / 256;
-    if (blocks > (size_t)c->num_cus * 32) blocks = (size_t)c->num_cus * 32;
-    hipLaunchKernelGGL(tonemap_codes, dim3((unsigned)blocks), dim3(256), 0, stream, d_rgb, n, c->tone_thr, d_codes);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
-    return PT_OK;
-}
-
-extern "C" int pt_tonemap(pt_ctx* c, const float* rgb, int w, int h, int32_t* codes)
-{
-    pt::clear_error();
-    if (!c || !rgb || !codes || w <= 0 || h <= 0) return pt::fail(PT_E_INVALID, "pt_tonemap: bad arguments");
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t n = (size_t)w * (size_t)h * 3;
-    float* d_rgb = nullptr;
-    int32_t* d_codes = nullptr;
-    auto run = [&]() -> int {
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_rgb), n * sizeof(float)));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_codes), n * sizeof(int32_t)));
-        HIP_TRY(hipMemcpy(d_rgb, rgb, n * sizeof(float), hipMemcpyHostToDevice));
-        if (int rc = pt_tonemap_device(c, d_rgb, w, h, d_codes, nullptr)) return rc;
-        HIP_TRY(hipMemcpy(codes, d_codes, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < n; ++i)
-            if (codes[i] == INT32_MAX) codes[i] = pt_tonemap_u8((double)rgb[i]);
-        return PT_OK;
-    };
-    const int rc = run();
-    if (d_rgb) (void)hipFree(d_rgb);
-    if (d_codes) (void)hipFree(d_codes);
-    return rc;
-}
+#include "pt_render_host.h"

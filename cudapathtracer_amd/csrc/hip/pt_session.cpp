@@ -13,14 +13,9 @@
 #include <string>
 
 #include "../host/host_internal.h"
+#include "pt_hip_util.h"
 
 namespace {
-
-#define SS_HIP(call)                                                                                       \
-    do {                                                                                                   \
-        const hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) return pt::fail(PT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_));    \
-    } while (0)
 
 // The session header (documented in pt.h); every field little-endian at a fixed offset.  Bytes 0..127 are the
 // checkpoint header of format version 1.
@@ -205,16 +200,16 @@ int pt_session_save(pt_accum* acc, pt_noise* noise, const char* path)
     pl.slot_pix = sa.slot_pix;
     pl.at = layout_of(npix, sa.frozen_at != nullptr, noise != nullptr, sn.pix != nullptr);
     pl.slots = sa.slots; pl.image_pixels = npix; pl.samples = (uint32_t)sa.samples;
-    SS_HIP(hipSetDevice(pt::ctx_device(sa.ctx)));
+    HIP_TRY(hipSetDevice(pt::ctx_device(sa.ctx)));
     pt::SessionScratch* S = pt::ctx_session_scratch(sa.ctx);
     if (int rc = grow("pt_session_save", S, pl.at.bytes)) return rc;
     pl.stage = static_cast<unsigned char*>(S->dev);
     if (sa.slots) {
         // the counters, and every pixel of another shard when there are any: the kernel writes this shard's only
-        SS_HIP(hipMemsetAsync(S->dev, 0, sa.pixels == npix ? pt::kSessionSumBytes : pl.at.bytes, nullptr));
+        HIP_TRY(hipMemsetAsync(S->dev, 0, sa.pixels == npix ? pt::kSessionSumBytes : pl.at.bytes, nullptr));
         if (int rc = pt::session_pack(sa.ctx, pl, nullptr)) return rc;
-        SS_HIP(hipMemcpyAsync(S->host, S->dev, pl.at.bytes, hipMemcpyDeviceToHost, nullptr));
-        SS_HIP(hipStreamSynchronize(nullptr));
+        HIP_TRY(hipMemcpyAsync(S->host, S->dev, pl.at.bytes, hipMemcpyDeviceToHost, nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));
     } else {
         memset(S->host, 0, pl.at.bytes);   // (a shard that owns no pixel: nothing is launched)
     }
@@ -296,10 +291,10 @@ int pt_session_load(pt_ctx* ctx, const char* path, pt_accum** acc_out, pt_noise*
             pl.slot_pix = sa.slot_pix;
             pl.stage = static_cast<unsigned char*>(S->dev);
             pl.slots = sa.slots; pl.image_pixels = npix; pl.samples = (uint32_t)h.samples;
-            SS_HIP(hipMemcpyAsync(S->dev, S->host, pl.at.bytes, hipMemcpyHostToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(S->dev, S->host, pl.at.bytes, hipMemcpyHostToDevice, nullptr));
             if (int rc = pt::session_unpack(ctx, pl, nullptr)) return rc;
-            SS_HIP(hipMemcpyAsync(S->host, S->dev, pt::kSessionSumBytes, hipMemcpyDeviceToHost, nullptr));
-            SS_HIP(hipStreamSynchronize(nullptr));
+            HIP_TRY(hipMemcpyAsync(S->host, S->dev, pt::kSessionSumBytes, hipMemcpyDeviceToHost, nullptr));
+            HIP_TRY(hipStreamSynchronize(nullptr));
             sum_counters(S->host, &frozen, &bad);
         }
         if (bad)

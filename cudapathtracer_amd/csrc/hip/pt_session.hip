@@ -17,14 +17,9 @@
 #include <hip/hip_runtime.h>
 
 #include "../host/host_internal.h"
+#include "pt_hip_util.h"
 
 namespace {
-
-#define SS_HIP(call)                                                                                       \
-    do {                                                                                                   \
-        const hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) return pt::fail(PT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_));    \
-    } while (0)
 
 constexpr int kBlock = 256;
 constexpr uint32_t kBlocksPerCu = 8;   // grid cap, the rest of the slots by grid stride
@@ -144,7 +139,7 @@ int pt::session_pack(pt_ctx* c, const pt::SessionPlanes& pl, void* stream_v)
 {
     if (!pl.slots) return PT_OK;
     hipLaunchKernelGGL(session_pack_planes, dim3(grid_of(c, pl.slots)), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream_v), pl);
-    SS_HIP(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return PT_OK;
 }
 
@@ -152,6 +147,6 @@ int pt::session_unpack(pt_ctx* c, const pt::SessionPlanes& pl, void* stream_v)
 {
     if (!pl.slots) return PT_OK;
     hipLaunchKernelGGL(session_unpack_planes, dim3(grid_of(c, pl.slots)), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream_v), pl);
-    SS_HIP(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return PT_OK;
 }

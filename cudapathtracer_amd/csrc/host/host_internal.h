@@ -24,7 +24,7 @@ namespace pt {
 int fail(int code, const char* fmt, ...);
 void clear_error();
 
-// The HIP device ordinal a render context lives on (pt_render.hip; used by pt_multi.cpp).
+// The HIP device ordinal a render context lives on (pt_render_host.h; used by pt_multi.cpp).
 int ctx_device(const pt_ctx* c);
 
 // 64-bit FNV-1a over a byte range, chained through `h` (pt_accel_digest, the scene digest of pt_create).
@@ -37,7 +37,7 @@ inline uint64_t fnv1a(const void* p, size_t n, uint64_t h = kFnvBasis)
 }
 
 // ---- accumulating passes: what pt_accum.cpp (the pt_accum_* entry points) needs of a render context
-// (pt_render.hip).  The state is device memory of the context's device, in the shard's work-slot order:
+// (pt_render_host.h).  The state is device memory of the context's device, in the shard's work-slot order:
 // rng[k * slots + q] (k = v0..v4, d) and mean[k * slots + q] (k = r, g, b) of slot q.
 struct AccumPass {
     uint32_t n0;      // samples every pixel (an adaptive pass: every active pixel) has before this pass
@@ -88,7 +88,7 @@ size_t adaptive_scan_words(size_t slots);
 int adaptive_compact(const uint32_t* frozen_at, size_t slots, uint32_t* list, uint32_t* block_tot, void* stream,
                      uint32_t* count);
 
-// ---- the denoiser (pt_denoise.hip) keeps its device scratch in the render context (pt_render.hip), which
+// ---- the denoiser (pt_denoise.hip) keeps its device scratch in the render context (pt_render_host.h), which
 // frees it in pt_destroy
 struct DenoiseScratch {
     void* mem = nullptr;
@@ -222,7 +222,7 @@ struct HostScene {
 // Area of an emissive sphere light: 4*3.14159*r^2 evaluated in float, left to right.
 inline float sphere_area(float r) { return 4.0f * 3.14159f * r * r; }
 
-// Deterministic float sin/cos shared with the kernels (defined in hip/pt_render.hip).
+// Deterministic float sin/cos shared with the kernels (defined in hip/pt_render_host.h over pt_device.h's det_sincos).
 void sincos_det(float theta, float* s, float* c);
 bool tonemap_thresholds(float t[256]);
 // host threads for the parallel builders: PT_HOST_THREADS, else OMP_NUM_THREADS, else the

@@ -96,4 +96,35 @@ struct PlanInput {
 // npix == 0 (an empty shard) gives the empty plan: nunits = blocks = 0, every chunk count 1, the budget not asked.
 int plan_units(const PlanInput& in, const RenderKnobs& k, const std::function<int(uint64_t*)>& lbuf_budget, UnitPlan* out);
 
+// Which instance of the wavefront kernels a render launches: the template arguments of render_unidir_wf /
+// render_head_wf (count, min_waves, lds_walk) or their accumulating twins (accum; always 5 waves, never counting).
+struct WavefrontVariant {
+    bool head, count;
+    int min_waves;
+    bool lds_walk, accum;
+    constexpr uint32_t code() const   // one word per instance, for a switch
+    {
+        return (uint32_t)head | (uint32_t)count << 1 | (uint32_t)lds_walk << 2 | (uint32_t)accum << 3 | (uint32_t)min_waves << 4;
+    }
+};
+// The instance for a render's integrator (head: 1), PT_FLAG_COUNT, an accumulating pass (never with count), a
+// tree held whole in LDS, and the PT_WF_MIN_WAVES / PT_HEAD_MIN_WAVES knobs.  Not every combination has an
+// instance of its own: integrator 1 counts at 5 waves and has no LDS walk; integrator 0 counts at 5 waves for
+// PT_WF_MIN_WAVES=6, and walks the LDS tree at 5 waves only.  (Internal linkage: the library exports nothing for it.)
+static constexpr WavefrontVariant wavefront_variant(bool head, bool count, bool accum, bool lds_tree, int wf_min_waves,
+                                                    int head_min_waves)
+{
+    if (head) {
+        if (accum) return {true, false, 5, false, true};
+        if (count) return {true, true, 5, false, false};
+        return {true, false, head_min_waves == 4 ? 4 : 5, false, false};
+    }
+    if (accum) return {false, false, 5, lds_tree, true};
+    if (count) return wf_min_waves == 4 ? WavefrontVariant{false, true, 4, false, false}
+                                        : WavefrontVariant{false, true, 5, lds_tree, false};
+    if (wf_min_waves == 6) return {false, false, 6, false, false};
+    if (wf_min_waves == 5) return {false, false, 5, lds_tree, false};
+    return {false, false, 4, false, false};
+}
+
 }  // namespace pt

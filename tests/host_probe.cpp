@@ -5,7 +5,9 @@
 //   host_probe plan            stdin lines: npix spp num_cus head count lds_fixed budget [PT_X=value ...]
 //                              (budget: bytes the budget callable answers, or "inf")
 //   host_probe grid            stdin lines: w h tile_w tile_h shard_index shard_count
-//   host_probe pack NAME DIR   NAME: cornell | cornell_blob | quad | spheres; DIR: the models directory
+//   host_probe variants        pt::wavefront_variant over head, count, accum, lds_tree, PT_WF_MIN_WAVES 4..6,
+//                              PT_HEAD_MIN_WAVES 4..5
+//   host_probe pack NAME DIR  NAME: cornell | cornell_blob | quad | spheres; DIR: the models directory
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -82,6 +84,23 @@ static int run_grid()
                vrc, src, n, g.tile_w, g.tile_h, g.tiles_x, g.ntiles, g.ntiles_shard, g.tile_bx, g.tile_blocks, g.npix,
                (unsigned long long)g.grid_slots, g.fits() ? "true" : "false");
     }
+    return 0;
+}
+
+// pt::wavefront_variant for every legal combination of its inputs, one line each
+static int run_variants()
+{
+    for (int head = 0; head < 2; ++head)
+        for (int count = 0; count < 2; ++count)
+            for (int accum = 0; accum < 2 - count; ++accum)   // (an accumulating pass never counts)
+                for (int lds_tree = 0; lds_tree < 2; ++lds_tree)
+                    for (int wf = 4; wf <= 6; ++wf)
+                        for (int hw = 4; hw <= 5; ++hw) {
+                            const pt::WavefrontVariant v = pt::wavefront_variant(head, count, accum, lds_tree, wf, hw);
+                            printf("{\"in\": [%d, %d, %d, %d, %d, %d], \"head\": %d, \"count\": %d, \"min_waves\": %d, "
+                                   "\"lds_walk\": %d, \"accum\": %d}\n",
+                                   head, count, accum, lds_tree, wf, hw, v.head, v.count, v.min_waves, v.lds_walk, v.accum);
+                        }
     return 0;
 }
 
@@ -194,7 +213,8 @@ int main(int argc, char** argv)
     const std::string mode = argc > 1 ? argv[1] : "";
     if (mode == "plan") return run_plan();
     if (mode == "grid") return run_grid();
+    if (mode == "variants") return run_variants();
     if (mode == "pack" && argc > 3) return run_pack(argv[2], argv[3]);
-    fprintf(stderr, "usage: host_probe plan | grid | pack NAME MODELS_DIR\n");
+    fprintf(stderr, "usage: host_probe plan | grid | variants | pack NAME MODELS_DIR\n");
     return 2;
 }

@@ -258,3 +258,40 @@ def test_pack_scene(probe, name):
     top = p["top_nodes"]
     assert top == min(n4, p["top_nodes_max"])
     assert all(parent[c] < top for c in range(1, top))
+
+
+# pt::wavefront_variant: (head, count, accum, lds_tree, PT_WF_MIN_WAVES, PT_HEAD_MIN_WAVES) -> the instance's
+# (head, count, min_waves, lds_walk, accum), ANY standing for every value of that input.  The table is the launch
+# ladder of render_enqueue before the choice moved, row by row, quirks included: integrator 1 counts at 5 waves
+# whatever PT_HEAD_MIN_WAVES says and has no LDS walk; integrator 0 counts at 5 waves for PT_WF_MIN_WAVES=6, and its
+# 4- and 6-wave instances ignore the LDS tree.
+ANY = None
+VARIANT_TABLE = [
+    ((1, 0, 1, ANY, ANY, ANY), (1, 0, 5, 0, 1)),   # render_head_accum_wf
+    ((1, 1, 0, ANY, ANY, ANY), (1, 1, 5, 0, 0)),   # render_head_wf<true, 5>
+    ((1, 0, 0, ANY, ANY, 4), (1, 0, 4, 0, 0)),     # render_head_wf<false, 4>
+    ((1, 0, 0, ANY, ANY, 5), (1, 0, 5, 0, 0)),     # render_head_wf<false, 5>
+    ((0, 0, 1, 1, ANY, ANY), (0, 0, 5, 1, 1)),     # render_unidir_accum_wf<true>
+    ((0, 0, 1, 0, ANY, ANY), (0, 0, 5, 0, 1)),     # render_unidir_accum_wf<false>
+    ((0, 1, 0, ANY, 4, ANY), (0, 1, 4, 0, 0)),     # render_unidir_wf<true, 4, false>
+    ((0, 1, 0, 1, 5, ANY), (0, 1, 5, 1, 0)),       # render_unidir_wf<true, 5, true>
+    ((0, 1, 0, 0, 5, ANY), (0, 1, 5, 0, 0)),       # render_unidir_wf<true, 5, false>
+    ((0, 1, 0, 1, 6, ANY), (0, 1, 5, 1, 0)),       # (6 counts at 5)
+    ((0, 1, 0, 0, 6, ANY), (0, 1, 5, 0, 0)),
+    ((0, 0, 0, ANY, 6, ANY), (0, 0, 6, 0, 0)),     # render_unidir_wf<false, 6, false>
+    ((0, 0, 0, 1, 5, ANY), (0, 0, 5, 1, 0)),       # render_unidir_wf<false, 5, true>
+    ((0, 0, 0, 0, 5, ANY), (0, 0, 5, 0, 0)),       # render_unidir_wf<false, 5, false>
+    ((0, 0, 0, ANY, 4, ANY), (0, 0, 4, 0, 0)),     # render_unidir_wf<false, 4, false>
+]
+
+
+def test_wavefront_variant_table(probe):
+    got = probe(["variants"])
+    # every legal input once: accum with count is left out
+    assert sorted(tuple(g["in"]) for g in got) == sorted(
+        (h, c, a, t, wf, hw) for h in (0, 1) for c, a in ((0, 0), (0, 1), (1, 0)) for t in (0, 1) for wf in (4, 5, 6)
+        for hw in (4, 5))
+    for g in got:
+        rows = [want for key, want in VARIANT_TABLE if all(k is ANY or k == v for k, v in zip(key, g["in"]))]
+        assert len(rows) == 1, g["in"]
+        assert (g["head"], g["count"], g["min_waves"], g["lds_walk"], g["accum"]) == rows[0], g["in"]
