@@ -49,6 +49,11 @@ class Camera(C.Structure):
                 ("pxl_width", C.c_int32), ("pxl_height", C.c_int32)]
 
 
+class View(C.Structure):   # pt_view, 44 B: the oriented camera's basis and film extent
+    _fields_ = [("right", C.c_float * 3), ("up", C.c_float * 3), ("back", C.c_float * 3),
+                ("film_w", C.c_float), ("film_h", C.c_float)]
+
+
 class Sphere(C.Structure):   # sphere.h:7-12 (pt_sphere)
     _fields_ = [("pos", Vec3), ("rad", C.c_float), ("diffuse", C.c_double * 3), ("emission", C.c_double * 3)]
 
@@ -138,7 +143,7 @@ assert C.sizeof(SessionInfo) == 136
 assert C.sizeof(Feature) == 48 and C.sizeof(DenoiseGuidedParams) == 24
 assert C.sizeof(NoiseSummary) == 32 + 64 * 8 and C.sizeof(ConvergeParams) == 24
 assert C.sizeof(Vec3) == 12 and C.sizeof(Triangle) == 28 and C.sizeof(Material) == 48
-assert C.sizeof(BvhNode) == 32 and C.sizeof(Camera) == 32
+assert C.sizeof(BvhNode) == 32 and C.sizeof(Camera) == 32 and C.sizeof(View) == 44
 
 # symbol -> (restype, argtypes); the list IS the exported surface of include/pt/pt.h
 SIGNATURES = {
@@ -155,6 +160,11 @@ SIGNATURES = {
     "pt_morton_i_to_pxl": (None, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "pt_camera_ray": (None, [C.POINTER(Camera), C.c_uint32, C.c_int, C.c_float, C.c_float,
                              C.POINTER(Vec3), C.POINTER(Vec3)]),
+    "pt_view_look_at": (C.c_int, [Vec3, Vec3, Vec3, C.POINTER(View)]),
+    "pt_view_set_fov": (C.c_int, [C.POINTER(View), C.POINTER(Camera), C.c_float, C.c_int, C.c_int]),
+    "pt_view_validate": (C.c_int, [C.POINTER(View)]),
+    "pt_camera_ray_view": (None, [C.POINTER(Camera), C.POINTER(View), C.c_uint32, C.c_int, C.c_float, C.c_float,
+                                  C.POINTER(Vec3), C.POINTER(Vec3)]),
     "pt_write_ppm": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int]),
     "pt_write_ppm_f64": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int]),
     "pt_write_ppm_order": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -167,6 +177,12 @@ SIGNATURES = {
                                    C.POINTER(Stats)]),
     "pt_render_device_async": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.c_void_p, C.c_void_p]),
     "pt_render_wait": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
+    "pt_render_view": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.POINTER(View), C.c_void_p,
+                                 C.POINTER(Stats)]),
+    "pt_render_device_view": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.POINTER(View), C.c_void_p,
+                                        C.c_void_p, C.POINTER(Stats)]),
+    "pt_render_device_view_async": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.POINTER(View),
+                                              C.c_void_p, C.c_void_p]),
     "pt_trace": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "pt_trace_counts": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                   C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -180,10 +196,17 @@ SIGNATURES = {
     "pt_group_create": (C.c_void_p, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int)]),
     "pt_group_size": (C.c_int, [C.c_void_p]),
     "pt_render_group": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.c_void_p, C.POINTER(Stats)]),
+    "pt_render_group_view": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.POINTER(View), C.c_void_p,
+                                       C.POINTER(Stats)]),
+    "pt_render_multi_view": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(Params), C.POINTER(Camera),
+                                       C.POINTER(View), C.c_void_p, C.POINTER(Stats)]),
     "pt_group_destroy": (None, [C.c_void_p]),
     "pt_render_multi": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(Params), C.POINTER(Camera), C.c_void_p,
                                   C.POINTER(Stats)]),
     "pt_accum_create": (C.c_void_p, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.POINTER(C.c_int)]),
+    "pt_accum_create_view": (C.c_void_p, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.POINTER(View),
+                                          C.POINTER(C.c_int)]),
+    "pt_accum_view": (C.c_int, [C.c_void_p, C.POINTER(View), C.POINTER(C.c_int)]),
     "pt_accum_add": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     "pt_accum_samples": (C.c_int64, [C.c_void_p]),
     "pt_accum_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -214,7 +237,11 @@ SIGNATURES = {
     "pt_session_load": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                   C.POINTER(C.c_int)]),
     "pt_session_file_info": (C.c_int, [C.c_char_p, C.POINTER(SessionInfo)]),
+    "pt_session_file_view": (C.c_int, [C.c_char_p, C.POINTER(View), C.POINTER(C.c_int)]),
     "pt_denoise_defaults": (None, [C.POINTER(DenoiseParams)]),
+    "pt_render_features_view_device": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.POINTER(View),
+                                                 C.c_void_p, C.c_void_p]),
+    "pt_render_features_view": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.POINTER(View), C.c_void_p]),
     "pt_render_features_device": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.c_void_p, C.c_void_p]),
     "pt_render_features": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.c_void_p]),
     "pt_denoise_device": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_int, C.c_int, C.c_int, C.c_void_p,

@@ -161,9 +161,45 @@ def make_camera(pos=(0.0, 1.0, 3.0), dist_from_film=1.0, focal_length=3.0, radiu
     return c
 
 
-def camera_ray(cam, idx, lens=False, u1=0.0, u2=0.0):
+def make_view(right, up, back, film=(1.0, 1.0)):
+    """A pt_view: the world-space images of camera +x, +y, +z (the camera looks along -back) and the film's extent
+    (1, 1 = the reference's unit square).  Not validated here: every call that takes it does (an orthonormal basis
+    to 1e-3, finite, film > 0)."""
+    v = L.View()
+    for k in range(3):
+        v.right[k], v.up[k], v.back[k] = float(right[k]), float(up[k]), float(back[k])
+    v.film_w, v.film_h = float(film[0]), float(film[1])
+    return v
+
+
+def look_at(pos, target, up=(0.0, 1.0, 0.0), vfov=None, cam=None, width=None, height=None):
+    """The view of a camera at `pos` looking at `target` (pt_view_look_at; film 1 x 1).  With vfov (degrees, the
+    vertical field of view) the film is sized for it and for square pixels (pt_view_set_fov): that needs `cam` (its
+    dist_from_film) and the image size, which default to the camera's pxl_width / pxl_height."""
+    v = L.View()
+    L.check(L.lib().pt_view_look_at(L.Vec3(*[float(c) for c in pos]), L.Vec3(*[float(c) for c in target]),
+                                    L.Vec3(*[float(c) for c in up]), C.byref(v)))
+    if vfov is not None:
+        if cam is None:
+            raise ValueError("look_at: vfov needs cam (its dist_from_film sizes the film)")
+        w = cam.pxl_width if width is None else width
+        h = cam.pxl_height if height is None else height
+        L.check(L.lib().pt_view_set_fov(C.byref(v), C.byref(cam), float(vfov), int(w), int(h)))
+    return v
+
+
+def _view_ref(view):
+    return None if view is None else C.byref(view)
+
+
+def camera_ray(cam, idx, lens=False, u1=0.0, u2=0.0, view=None):
+    """(origin, direction) of pixel `idx` (a Morton index): pt_camera_ray, or pt_camera_ray_view with a view."""
     o, d = L.Vec3(), L.Vec3()
-    L.lib().pt_camera_ray(C.byref(cam), int(idx), int(bool(lens)), float(u1), float(u2), C.byref(o), C.byref(d))
+    if view is None:
+        L.lib().pt_camera_ray(C.byref(cam), int(idx), int(bool(lens)), float(u1), float(u2), C.byref(o), C.byref(d))
+    else:
+        L.lib().pt_camera_ray_view(C.byref(cam), C.byref(view), int(idx), int(bool(lens)), float(u1), float(u2),
+                                   C.byref(o), C.byref(d))
     return (o.x, o.y, o.z), (d.x, d.y, d.z)
 
 
@@ -268,10 +304,11 @@ class Renderer:
         return p
 
     def render(self, cam, width, height, spp, bounces=3, integrator=0, seed=1234, flags=0,
-               shard_index=0, shard_count=1, pixel_order=0, tile_w=0, tile_h=0, out=None):
+               shard_index=0, shard_count=1, pixel_order=0, tile_w=0, tile_h=0, out=None, view=None):
         """Returns (image float32, stats dict).  The image is (H, W, 3) in scanline order, or the
         reference's Morton-indexed imgBuff (W*H, 3) with pixel_order=PT_ORDER_MORTON.  `out`: a
-        C-contiguous float32 array of W*H*3 values to render into (reused across frames)."""
+        C-contiguous float32 array of W*H*3 values to render into (reused across frames).  `view`: an oriented
+        camera (make_view / look_at); None is the reference camera.  So for every call below that takes one."""
         p = self.params(width, height, spp, bounces, integrator, seed, flags, shard_index, shard_count,
                         pixel_order, tile_w, tile_h)
         shape = (height * width, 3) if pixel_order == L.PT_ORDER_MORTON else (height, width, 3)
@@ -280,27 +317,28 @@ class Renderer:
         elif out.dtype != np.float32 or out.size != width * height * 3 or not out.flags.c_contiguous:
             raise ValueError("out must be a C-contiguous float32 array of W*H*3 values")
         st = L.Stats()
-        L.check(L.lib().pt_render(self._h, C.byref(p), C.byref(cam), out.ctypes.data, C.byref(st)))
+        L.check(L.lib().pt_render_view(self._h, C.byref(p), C.byref(cam), _view_ref(view), out.ctypes.data, C.byref(st)))
         return out, st.as_dict()
 
     def render_device(self, cam, d_out_ptr, width, height, spp, bounces=3, integrator=0, seed=1234, flags=0,
-                      shard_index=0, shard_count=1, stream_ptr=None, pixel_order=0, tile_w=0, tile_h=0):
+                      shard_index=0, shard_count=1, stream_ptr=None, pixel_order=0, tile_w=0, tile_h=0, view=None):
         """Render this shard into a caller-owned, zero-filled device buffer (e.g. a torch tensor)."""
         p = self.params(width, height, spp, bounces, integrator, seed, flags, shard_index, shard_count,
                         pixel_order, tile_w, tile_h)
         st = L.Stats()
-        L.check(L.lib().pt_render_device(self._h, C.byref(p), C.byref(cam), C.c_void_p(int(d_out_ptr)),
-                                         None if stream_ptr is None else C.c_void_p(int(stream_ptr)), C.byref(st)))
+        L.check(L.lib().pt_render_device_view(self._h, C.byref(p), C.byref(cam), _view_ref(view), C.c_void_p(int(d_out_ptr)),
+                                              None if stream_ptr is None else C.c_void_p(int(stream_ptr)), C.byref(st)))
         return st.as_dict()
 
     def render_device_async(self, cam, d_out_ptr, width, height, spp, bounces=3, integrator=0, seed=1234, flags=0,
-                            shard_index=0, shard_count=1, stream_ptr=None, pixel_order=0, tile_w=0, tile_h=0):
+                            shard_index=0, shard_count=1, stream_ptr=None, pixel_order=0, tile_w=0, tile_h=0, view=None):
         """Enqueue render_device's work on the stream and return at once (at most 2 in flight); collect
         the stats of the oldest with wait()."""
         p = self.params(width, height, spp, bounces, integrator, seed, flags, shard_index, shard_count,
                         pixel_order, tile_w, tile_h)
-        L.check(L.lib().pt_render_device_async(self._h, C.byref(p), C.byref(cam), C.c_void_p(int(d_out_ptr)),
-                                               None if stream_ptr is None else C.c_void_p(int(stream_ptr))))
+        L.check(L.lib().pt_render_device_view_async(self._h, C.byref(p), C.byref(cam), _view_ref(view),
+                                                    C.c_void_p(int(d_out_ptr)),
+                                                    None if stream_ptr is None else C.c_void_p(int(stream_ptr))))
 
     def wait(self):
         """Stats dict of the oldest render in flight (render_device_async), once it has finished."""
@@ -309,7 +347,7 @@ class Renderer:
         return st.as_dict()
 
     def accumulator(self, cam, width, height, bounces=3, integrator=0, seed=1234, flags=0, shard_index=0,
-                    shard_count=1, pixel_order=0, tile=0):
+                    shard_count=1, pixel_order=0, tile=0, view=None):
         """A resumable render of this shard (pt_accum_create): everything but the sample count is fixed
         here; Accumulator.add(spp) then renders the next spp samples of every pixel.  `tile`: the shard
         tile size, one int or (tile_w, tile_h); 0 = 8."""
@@ -317,7 +355,7 @@ class Renderer:
         p = self.params(width, height, 0, bounces, integrator, seed, flags, shard_index, shard_count, pixel_order,
                         tw, th)
         err = C.c_int(0)
-        h = L.lib().pt_accum_create(self._h, C.byref(p), C.byref(cam), C.byref(err))
+        h = L.lib().pt_accum_create_view(self._h, C.byref(p), C.byref(cam), _view_ref(view), C.byref(err))
         if not h:
             L.check(err.value if err.value != 0 else L.PT_E_HIP)
         return Accumulator(self, h, p)
@@ -343,7 +381,7 @@ class Renderer:
             a._noise = NoiseEstimate(a, est.value)
         return a, a._noise
 
-    def features(self, cam, width, height, pixel_order=0, shard_index=0, shard_count=1, tile=0):
+    def features(self, cam, width, height, pixel_order=0, shard_index=0, shard_count=1, tile=0, view=None):
         """Primary-hit feature buffers (pt_render_features): a FEATURE structured array of shape (H, W) -- (W*H,)
         in Morton order -- with albedo, depth, normal, prim and position of each pixel's pinhole camera ray.
         Pixels outside the shard are all zero with prim = -1.  `tile`: one int or (tile_w, tile_h); 0 = 8."""
@@ -351,17 +389,18 @@ class Renderer:
         p = self.params(width, height, 0, 1, 0, 0, 0, shard_index, shard_count, pixel_order, tw, th)
         shape = (height * width,) if pixel_order == L.PT_ORDER_MORTON else (height, width)
         out = np.zeros(shape, dtype=FEATURE)
-        L.check(L.lib().pt_render_features(self._h, C.byref(p), C.byref(cam), out.ctypes.data))
+        L.check(L.lib().pt_render_features_view(self._h, C.byref(p), C.byref(cam), _view_ref(view), out.ctypes.data))
         return out
 
     def features_device(self, cam, d_feat_ptr, width, height, pixel_order=0, shard_index=0, shard_count=1, tile=0,
-                        stream_ptr=None):
+                        stream_ptr=None, view=None):
         """This shard's features into a caller-owned device buffer of W*H 48-byte records (16-byte aligned);
         records of other pixels are left untouched."""
         tw, th = (tile, tile) if np.isscalar(tile) else tile
         p = self.params(width, height, 0, 1, 0, 0, 0, shard_index, shard_count, pixel_order, tw, th)
-        L.check(L.lib().pt_render_features_device(self._h, C.byref(p), C.byref(cam), C.c_void_p(int(d_feat_ptr)),
-                                                  None if stream_ptr is None else C.c_void_p(int(stream_ptr))))
+        L.check(L.lib().pt_render_features_view_device(self._h, C.byref(p), C.byref(cam), _view_ref(view),
+                                                       C.c_void_p(int(d_feat_ptr)),
+                                                       None if stream_ptr is None else C.c_void_p(int(stream_ptr))))
 
     @staticmethod
     def denoise_params(iterations=5, normal_power_log2=5, sigma_depth=0.02, sigma_color=0.0, demodulate=True):
@@ -505,6 +544,14 @@ def session_file_info(path):
                 frozen_pixels=int(i.frozen_pixels))
 
 
+def session_file_view(path):
+    """The view a session file holds (pt_session_file_view, host-only): a pt_view, or None for a file without one
+    (format version 2)."""
+    v, has = L.View(), C.c_int(0)
+    L.check(L.lib().pt_session_file_view(str(path).encode(), C.byref(v), C.byref(has)))
+    return v if has.value else None
+
+
 class Accumulator:
     """Per-pixel XORWOW state and f64 running mean of one shard, kept on the renderer's device between
     passes (the reference's randState_device / imgBuffer_device, kernel.cu:527-553): a render built up
@@ -546,6 +593,13 @@ class Accumulator:
     @property
     def samples(self):
         return int(L.lib().pt_accum_samples(self._h))
+
+    @property
+    def view(self):
+        """The view the accumulator was created with (pt_accum_view), or None for the reference camera."""
+        v, has = L.View(), C.c_int(0)
+        L.check(L.lib().pt_accum_view(self._h, C.byref(v), C.byref(has)))
+        return v if has.value else None
 
     def _shape(self):
         p = self.params
@@ -749,7 +803,7 @@ class Group:
             pass
 
     def render(self, cam, width, height, spp, bounces=3, integrator=0, seed=1234, flags=0, pixel_order=0,
-               tile_w=0, tile_h=0, out=None):
+               tile_w=0, tile_h=0, out=None, view=None):
         """Returns (image float32 (H, W, 3) -- (W*H, 3) in Morton order --, summed stats dict)."""
         p = Renderer.params(width, height, spp, bounces, integrator, seed, flags, 0, 1, pixel_order, tile_w, tile_h)
         shape = (height * width, 3) if pixel_order == L.PT_ORDER_MORTON else (height, width, 3)
@@ -758,5 +812,6 @@ class Group:
         elif out.dtype != np.float32 or out.size != width * height * 3 or not out.flags.c_contiguous:
             raise ValueError("out must be a C-contiguous float32 array of W*H*3 values")
         st = L.Stats()
-        L.check(L.lib().pt_render_group(self._h, C.byref(p), C.byref(cam), out.ctypes.data, C.byref(st)))
+        L.check(L.lib().pt_render_group_view(self._h, C.byref(p), C.byref(cam), _view_ref(view), out.ctypes.data,
+                                             C.byref(st)))
         return out, st.as_dict()

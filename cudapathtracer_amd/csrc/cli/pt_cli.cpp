@@ -54,6 +54,13 @@
 //                                         estimator's variance map; the files written after earlier passes are unfiltered
 // --variance-map FILE.pfm                 with --pass-spp K: write the variance of every pixel's mean luminance
 //                                         (pt_noise_variance) as a grey PFM
+// --look-at X,Y,Z [--up X,Y,Z]            aim the camera (pt_view_look_at from --cam towards X,Y,Z; up defaults to 0,1,0).  With
+//   [--vfov DEG | --film W,H]             every mode that renders.  --vfov sizes the film for a vertical field of view and
+//                                         square pixels (pt_view_set_fov), --film sets its extent directly (1,1 = the
+//                                         reference's unit square, the default); without --look-at they apply to a camera
+//                                         looking down -z.  --session writes the view (format version 3); after
+//                                         --resume-session the view is the file's, and a command-line view that differs is
+//                                         an error; --checkpoint cannot hold a view (the library's message says so)
 // --aov PREFIX                            write the primary-hit feature buffers as PREFIX_albedo.pfm,
 //                                         PREFIX_normal.pfm, PREFIX_position.pfm and PREFIX_depth.pfm (depth
 //                                         replicated to 3 channels)
@@ -84,6 +91,7 @@ struct Obj {
             "              [--width W] [--height H] [--spp N | --num-samples N] [--bounces D]\n"
             "              [--integrator unidir|head] [--seed S] [--cam X,Y,Z] [--dist D] [--focal F]\n"
             "              [--radius R] [--gpus N] [--out image.ppm] [--pfm image.pfm] [--quiet]\n"
+            "              [--look-at X,Y,Z] [--up X,Y,Z] [--vfov DEG | --film W,H]\n"
             "              [--tri-counts out.csv [--reference-walk]] [--morton] [--tile WxH]\n"
             "              [--checkpoint FILE] [--resume FILE] [--pass-spp K]\n"
             "              [--session FILE] [--resume-session FILE]\n"
@@ -101,6 +109,8 @@ struct Obj {
             "  --variance-map FILE  with --pass-spp: write the variance of every pixel's mean luminance as a grey PFM\n"
             "  --session FILE     write the whole progressive state (accumulator, frozen pixels, estimator) after each pass\n"
             "  --resume-session FILE  continue the render FILE holds; its estimator window continues; --spp is the samples to add\n"
+            "  --look-at X,Y,Z    aim the camera at a point (--up X,Y,Z, default 0,1,0); --vfov DEG: the vertical field of view\n"
+            "                     with square pixels; --film W,H: the film's extent (1,1 = the reference's unit square)\n"
             "  --aov PREFIX       write PREFIX_albedo.pfm, PREFIX_normal.pfm, PREFIX_position.pfm, PREFIX_depth.pfm\n");
     exit(2);
 }
@@ -108,6 +118,13 @@ struct Obj {
 bool parse_vec3(const std::string& s, pt_vec3* v)
 {
     return sscanf(s.c_str(), "%f,%f,%f", &v->x, &v->y, &v->z) == 3;
+}
+
+// (strict: every component present and nothing after the last)
+bool parse_vec3_strict(const std::string& s, pt_vec3* v)
+{
+    char tail = 0;
+    return sscanf(s.c_str(), "%f,%f,%f%c", &v->x, &v->y, &v->z, &tail) == 3;
 }
 
 Obj parse_obj(const std::string& arg)
@@ -163,6 +180,10 @@ int main(int argc, char** argv)
     pt_converge_params conv{};
     conv.min_batches = 2; conv.quantile = 0.95f;
     pt_noise_defaults(&conv.noise);
+    // the oriented camera: --look-at / --up / --vfov / --film (any of them makes a view)
+    bool have_target = false, have_vfov = false, have_film = false, have_up = false;
+    pt_vec3 target{0, 0, 0}, up{0, 1, 0};
+    float vfov = 0.0f, film_w = 1.0f, film_h = 1.0f;
     std::vector<std::string> given;   // the options on the command line (a resumed file may contradict them)
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -222,6 +243,20 @@ int main(int argc, char** argv)
         else if (a == "--error-map") error_map = next();
         else if (a == "--adaptive") adaptive = true;
         else if (a == "--count-map") count_map = next();
+        else if (a == "--look-at") { have_target = true; if (!parse_vec3_strict(next(), &target)) usage("bad --look-at (X,Y,Z)"); }
+        else if (a == "--up") { have_up = true; if (!parse_vec3_strict(next(), &up)) usage("bad --up (X,Y,Z)"); }
+        else if (a == "--vfov") {
+            have_vfov = true;
+            vfov = strtof(next().c_str(), nullptr);
+            if (!(vfov > 0.0f && vfov < 180.0f)) usage("--vfov is in (0, 180) degrees");
+        }
+        else if (a == "--film") {
+            have_film = true;
+            char tail = 0;
+            if (sscanf(next().c_str(), "%f,%f%c", &film_w, &film_h, &tail) != 2 || !(film_w > 0.0f) || !(film_h > 0.0f) ||
+                !std::isfinite(film_w) || !std::isfinite(film_h))
+                usage("--film is W,H, both > 0");
+        }
         else if (a == "-h" || a == "--help") usage(nullptr);
         else usage(("unknown option " + a).c_str());
     }
@@ -247,6 +282,10 @@ int main(int argc, char** argv)
     if (adaptive && !checkpoint.empty()) usage("--adaptive cannot write a --checkpoint (format version 1 holds a single sample count)");
     if (!count_map.empty() && pass_spp < 1) usage("--count-map needs --pass-spp K");
     if (!resume.empty() && !resume_session.empty()) usage("--resume and --resume-session: choose one");
+    if (have_vfov && have_film) usage("--vfov and --film: choose one");
+    const bool view_given = have_target || have_up || have_vfov || have_film;
+    pt_view file_view{};
+    int file_has_view = 0;
     const bool accumulate = !checkpoint.empty() || !resume.empty() || !session.empty() || !resume_session.empty() || pass_spp > 0;
     if (accumulate && gpus != 1)
         usage("--checkpoint / --resume / --session / --resume-session / --pass-spp need --gpus 1 (one accumulator per shard)");
@@ -263,6 +302,7 @@ int main(int argc, char** argv)
             pt_session_info si;
             if (pt_session_file_info(resume_session.c_str(), &si) != PT_OK) return die("--resume-session");
             fp = si.params; fc = si.cam; done = si.samples;
+            if (pt_session_file_view(resume_session.c_str(), &file_view, &file_has_view) != PT_OK) return die("--resume-session");
         }
         auto has = [&](const char* o) { for (const std::string& g : given) if (g == o) return true; return false; };
         auto conflict = [&](const char* o, bool differs) {
@@ -287,6 +327,26 @@ int main(int argc, char** argv)
         p.spp = add;
         cam = fc;
         if (!quiet) printf("resuming %s: %dx%d, %lld samples done, adding %d\n", resumed.c_str(), p.width, p.height, (long long)done, add);
+    }
+
+    // the view: the command line's (from the camera as it stands now: after a resume, the file's), or the resumed
+    // file's; a command-line view that is not the file's is a conflict, like --dist and --focal above
+    pt_view view_store{};
+    const pt_view* cam_view = nullptr;
+    if (view_given) {
+        const pt_vec3 at = have_target ? target : pt_vec3{cam.pos.x, cam.pos.y, cam.pos.z - 1.0f};   // (else down -z)
+        if (pt_view_look_at(cam.pos, at, up, &view_store) != PT_OK) return die(have_target ? "--look-at" : "--up");
+        if (have_vfov && pt_view_set_fov(&view_store, &cam, vfov, p.width, p.height) != PT_OK) return die("--vfov");
+        if (have_film) { view_store.film_w = film_w; view_store.film_h = film_h; }
+        cam_view = &view_store;
+    }
+    if (!resumed.empty()) {
+        if (view_given && (!file_has_view || memcmp(&view_store, &file_view, sizeof(pt_view)) != 0)) {
+            fprintf(stderr, "pt_cli: --look-at / --up / --vfov / --film contradict the resumed file %s (%s)\n", resumed.c_str(),
+                    file_has_view ? "its view differs" : "it has no view");
+            return 2;
+        }
+        cam_view = file_has_view ? &file_view : nullptr;
     }
 
     const auto t0 = std::chrono::steady_clock::now();
@@ -321,7 +381,7 @@ int main(int argc, char** argv)
         feat.resize((size_t)p.width * p.height);
         pt_params fp = p;
         fp.shard_index = 0; fp.shard_count = 1;
-        return pt_render_features(ctx[0], &fp, &cam, feat.data()) == PT_OK;
+        return pt_render_features_view(ctx[0], &fp, &cam, cam_view, feat.data()) == PT_OK;
     };
     // the image files of the current `img` (after the render; with --pass-spp after every pass)
     auto write_images = [&]() -> const char* {
@@ -370,7 +430,7 @@ int main(int argc, char** argv)
                 printf("noise estimate: the window saved in %s continues (%lld samples)\n", resume_session.c_str(),
                        (long long)pt_accum_samples(acc));
         } else {
-            acc = resume.empty() ? pt_accum_create(ctx[0], &p, &cam, &err) : pt_accum_load(ctx[0], resume.c_str(), &err);
+            acc = resume.empty() ? pt_accum_create_view(ctx[0], &p, &cam, cam_view, &err) : pt_accum_load(ctx[0], resume.c_str(), &err);
             if (!acc) return die(resume.empty() ? "pt_accum_create" : "--resume");
         }
         const int step = pass_spp > 0 ? pass_spp : (p.spp > 0 ? p.spp : 1);
@@ -459,8 +519,8 @@ int main(int argc, char** argv)
         pt_accum_destroy(acc);
     } else {
         // one GPU: pt_render; N GPUs: image-tile shards on devices 0..N-1 summed by one RCCL reduce
-        const int rc = (gpus == 1) ? pt_render(ctx[0], &p, &cam, img.data(), &st)
-                                   : pt_render_multi(ctx.data(), gpus, &p, &cam, img.data(), &st);
+        const int rc = (gpus == 1) ? pt_render_view(ctx[0], &p, &cam, cam_view, img.data(), &st)
+                                   : pt_render_multi_view(ctx.data(), gpus, &p, &cam, cam_view, img.data(), &st);
         if (rc != PT_OK) return die("pt_render");
     }
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();

@@ -90,6 +90,8 @@ struct pt_accum {
     pt_ctx* ctx = nullptr;
     pt_params params;
     pt_camera cam;
+    pt_view view;                     // the oriented camera, kept for life like cam (has_view)
+    bool has_view = false;
     int64_t samples = 0;
     std::vector<uint32_t> slot_pix;   // work slot -> scanline pixel id (0xffffffff: outside the image)
     uint32_t* d_rng = nullptr;        // 6 words per slot, word-major
@@ -183,7 +185,7 @@ void pt::accum_frozen(pt_accum* a, uint64_t newly_frozen)
 }
 
 namespace {
-pt_accum* make_accum(pt_ctx* c, const pt_params* p, const pt_camera* cam, int* code);
+pt_accum* make_accum(pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view, int* code);
 }
 
 int pt::accum_session(pt_accum* a, pt::SessionAccum* out)
@@ -194,14 +196,15 @@ int pt::accum_session(pt_accum* a, pt::SessionAccum* out)
         HIP_TRY(hipMalloc(reinterpret_cast<void**>(&a->d_slot_pix), n * sizeof(uint32_t)));
         if (a->slots()) HIP_TRY(hipMemcpy(a->d_slot_pix, a->slot_pix.data(), a->slots() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
-    *out = pt::SessionAccum{a->ctx, &a->params, &a->cam, a->samples, a->slots(), a->pixels, a->d_rng, a->d_mean,
+    *out = pt::SessionAccum{a->ctx, &a->params, &a->cam, a->has_view ? &a->view : nullptr, a->samples, a->slots(), a->pixels, a->d_rng, a->d_mean,
                             a->any_frozen ? a->d_frozen_at : nullptr, a->d_slot_pix, a->noise};
     return PT_OK;
 }
 
-pt_accum* pt::accum_session_new(pt_ctx* c, const pt_params* p, const pt_camera* cam, int64_t samples, bool counts, int* code)
+pt_accum* pt::accum_session_new(pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view, int64_t samples,
+                                bool counts, int* code)
 {
-    pt_accum* a = make_accum(c, p, cam, code);
+    pt_accum* a = make_accum(c, p, cam, view, code);
     if (!a) return nullptr;
     a->samples = samples;
     if (counts) {
@@ -215,10 +218,10 @@ pt_accum* pt::accum_session_new(pt_ctx* c, const pt_params* p, const pt_camera* 
 
 namespace {
 
-// The accumulator of (c, p, cam) with zeroed state (0 samples), or null with the error recorded.
-pt_accum* make_accum(pt_ctx* c, const pt_params* p, const pt_camera* cam, int* code)
+// The accumulator of (c, p, cam, view) with zeroed state (0 samples), or null with the error recorded.
+pt_accum* make_accum(pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view, int* code)
 {
-    *code = pt::accum_check(c, p, cam);
+    *code = pt::accum_check(c, p, cam, view);
     if (*code != PT_OK) return nullptr;
     pt_accum* a = new (std::nothrow) pt_accum();
     if (!a) { *code = pt::fail(PT_E_OOM, "pt_accum_create: out of host memory"); return nullptr; }
@@ -229,6 +232,8 @@ pt_accum* make_accum(pt_ctx* c, const pt_params* p, const pt_camera* cam, int* c
     a->params.shard_index = p->shard_index; a->params.shard_count = p->shard_count; a->params.pixel_order = p->pixel_order;
     a->params.tile_w = p->tile_w; a->params.tile_h = p->tile_h;
     a->cam = *cam;
+    memset(&a->view, 0, sizeof(a->view));
+    if (view) { a->view = *view; a->has_view = true; }
     pt::shard_slots(&a->params, &a->slot_pix);
     for (const uint32_t pix : a->slot_pix) a->pixels += pix != 0xffffffffu;
     auto alloc = [&]() -> int {
@@ -275,15 +280,29 @@ int fetch_records(pt_accum* a, std::vector<Record>* rec)
 
 extern "C" {
 
-pt_accum* pt_accum_create(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, int* err)
+pt_accum* pt_accum_create_view(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, const pt_view* view, int* err)
 {
     pt::clear_error();
     int code;
     pt_accum* a = nullptr;
     if (!ctx || !params || !cam) code = pt::fail(PT_E_INVALID, "pt_accum_create: null argument");
-    else a = make_accum(ctx, params, cam, &code);
+    else a = make_accum(ctx, params, cam, view, &code);
     if (err) *err = code;
     return a;
+}
+
+pt_accum* pt_accum_create(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, int* err)
+{
+    return pt_accum_create_view(ctx, params, cam, nullptr, err);
+}
+
+int pt_accum_view(const pt_accum* acc, pt_view* out, int* has_view)
+{
+    pt::clear_error();
+    if (!acc) return pt::fail(PT_E_INVALID, "pt_accum_view: null accumulator");
+    if (has_view) *has_view = acc->has_view ? 1 : 0;
+    if (out && acc->has_view) *out = acc->view;
+    return PT_OK;
 }
 
 int pt_accum_add(pt_accum* acc, int32_t spp, float* d_out, void* stream, pt_stats* stats)
@@ -314,7 +333,7 @@ int pt_accum_add(pt_accum* acc, int32_t spp, float* d_out, void* stream, pt_stat
         pass.active = acc->d_list;
         pass.nactive = acc->nactive;
     }
-    if (int rc = pt::accum_pass(acc->ctx, &p, &acc->cam, pass, d_out, stream, stats)) return rc;
+    if (int rc = pt::accum_pass(acc->ctx, &p, &acc->cam, acc->has_view ? &acc->view : nullptr, pass, d_out, stream, stats)) return rc;
     acc->samples += spp;
     return PT_OK;
 }
@@ -474,6 +493,9 @@ int pt_accum_save(pt_accum* acc, const char* path)
     pt::clear_error();
     if (!acc || !path) return pt::fail(PT_E_INVALID, "pt_accum_save: null argument");
     if (!little_endian()) return pt::fail(PT_E_INVALID, "pt_accum_save: checkpoint files are little-endian; this host is not");
+    if (acc->has_view)
+        return pt::fail(PT_E_INVALID, "pt_accum_save: the accumulator has a view (an oriented camera); checkpoint format version 1 "
+                        "holds the 32-byte camera alone (pt_session_save writes a session file that holds the view)");
     if (acc->any_frozen) {
         std::vector<uint32_t> cnt;
         if (int rc = fetch_counts(acc, &cnt)) return rc;
@@ -525,7 +547,7 @@ pt_accum* pt_accum_load(pt_ctx* ctx, const char* path, int* err)
                              "%016llx; this context: %u, %u, %016llx)", path, h.num_tris, h.num_spheres,
                              (unsigned long long)h.scene_digest, nt, ns, (unsigned long long)digest));
     int code;
-    pt_accum* a = make_accum(ctx, &h.params, &h.cam, &code);
+    pt_accum* a = make_accum(ctx, &h.params, &h.cam, nullptr, &code);
     if (!a) return bail(code);
     const size_t n = a->slots();
     std::vector<uint32_t> rng(n * 6, 0u);

@@ -169,6 +169,12 @@ int pt_group_size(const pt_group* g) { return g ? (int)g->ctx.size() : 0; }
 
 int pt_render_group(pt_group* g, const pt_params* params, const pt_camera* cam, float* out_rgb, pt_stats* stats)
 {
+    return pt_render_group_view(g, params, cam, nullptr, out_rgb, stats);
+}
+
+int pt_render_group_view(pt_group* g, const pt_params* params, const pt_camera* cam, const pt_view* view, float* out_rgb,
+                         pt_stats* stats)
+{
     pt::clear_error();
     if (!g || !params || !cam || !out_rgb) return pt::fail(PT_E_INVALID, "pt_render_group: null argument");
     if (params->width <= 0 || params->height <= 0 || params->width > 65535 || params->height > 65535)
@@ -193,7 +199,7 @@ int pt_render_group(pt_group* g, const pt_params* params, const pt_camera* cam, 
         q.shard_index = i;
         q.shard_count = n;
         memset(&st[i], 0, sizeof(st[i]));
-        rc[i] = pt_render_device(g->ctx[i], &q, cam, g->fb[i], g->stream[i], &st[i]);
+        rc[i] = pt_render_device_view(g->ctx[i], &q, cam, view, g->fb[i], g->stream[i], &st[i]);
         if (rc[i] != PT_OK) msg[i] = pt_last_error();   // (the error channel is per thread)
     };
     if (n == 1) {
@@ -241,10 +247,16 @@ int pt_render_group(pt_group* g, const pt_params* params, const pt_camera* cam, 
 int pt_render_multi(pt_ctx* const* ctxs, int n, const pt_params* params, const pt_camera* cam, float* out_rgb,
                     pt_stats* stats)
 {
+    return pt_render_multi_view(ctxs, n, params, cam, nullptr, out_rgb, stats);
+}
+
+int pt_render_multi_view(pt_ctx* const* ctxs, int n, const pt_params* params, const pt_camera* cam, const pt_view* view,
+                         float* out_rgb, pt_stats* stats)
+{
     int err = PT_OK;
     pt_group* g = pt_group_create(ctxs, n, &err);
     if (!g) return err;
-    const int rc = pt_render_group(g, params, cam, out_rgb, stats);
+    const int rc = pt_render_group_view(g, params, cam, view, out_rgb, stats);
     std::string keep = rc != PT_OK ? std::string(pt_last_error()) : std::string();
     pt_group_destroy(g);
     if (rc != PT_OK) return pt::fail(rc, "%s", keep.c_str());

@@ -131,6 +131,11 @@ struct Args {
     uint32_t* acc_rng;              // per pixel slot q: XORWOW after its last finished sample, word k (v0..v4, d)
                                     // at [k * npix + q] (a wave's 64 slots: one 256-B row per word)
     double* acc_mean;               // per pixel slot q: the f64 running mean, channel k at [k * npix + q]
+    // The oriented camera (pt_view; camera_ray_view).  At the very end for the same reason: a NULL view is
+    // today's code, and every offset above -- what the kernels' scalar loads were tuned with -- stays where it is.
+    uint32_t oriented;              // 1: rays through the view below; 0: the reference camera (camera_ray)
+    float view_right[3], view_up[3], view_back[3];   // world-space images of camera +x, +y, +z
+    float film_w, film_h;           // film extent (1, 1 = the reference's unit square)
 };
 // Slots of Args::counters: the kernels add to them; pt_render_wait (pt_stats, PT_SECTION_DUMP) and
 // pt_trace_counts read them.
@@ -144,6 +149,7 @@ enum : uint32_t {
     CNT_LANE_BINS = 64, CNT_WAVE_BINS = 80   // kTailBins each
 };
 static_assert(offsetof(Args, origin_max) + 4 == offsetof(Args, acc_rng), "origin_max sits in Args' padding");
+static_assert(offsetof(Args, oriented) == offsetof(Args, acc_mean) + 8, "the view's words follow everything else");
 constexpr int kCounterWords = 96;
 // Unit words of an accumulating pass: UW_N0 bit 30 marks a pixel's first unit of the pass (chunk 0, or the
 // whole pixel) -- `n == 1` no longer does; its sample numbers are the 30 bits below.
@@ -553,6 +559,41 @@ __device__ __forceinline__ void camera_ray(const Cam& cam, uint32_t px, uint32_t
     *d = normalized(film - lo);
 }
 
+// The ray of an oriented camera (pt_view, pt.h: no counterpart in the reference): camera_ray's camera-space part
+// with the film scaled to film_w x film_h, then the view's basis applied to the direction (and to the lens offset).
+// Every operation is rounded on its own (no contraction); a pinhole origin is 0 + pos, as the kernels form it.
+// The set-up kernels and integrator 1's wavefront kernels take it under the wave-uniform a.oriented, a branch inside
+// the existing instances; integrator 0's wavefront kernels, the tile kernel and the features kernel have instances
+// of their own for it (kView), because the branch moved their register allocation.  (kFresh: every word of the view made opaque at its use, as cam's are
+// in the wavefront kernels, so nothing of it is hoisted across the walk.)
+template <bool kFresh = true>
+__device__ __forceinline__ void camera_ray_view(const Args& a, uint32_t px, uint32_t py, bool lens, float u1, float u2,
+                                                V3* o, V3* d)
+{
+    const Cam& cam = a.cam;
+    auto w = [](float x) { return kFresh ? fresh(x) : x; };
+    const int cw = kFresh ? fresh(cam.w) : cam.w, ch = kFresh ? fresh(cam.h) : cam.h;
+    V3 film = v3(((float)px / (float)cw - 0.5f) * w(a.film_w), ((float)py / (float)ch - 0.5f) * w(a.film_h), cam.dist);
+    film = (film * -cam.focal) / cam.dist;
+    V3 lo = v3(0.0f, 0.0f, 0.0f);
+    if (lens) {
+        const float r = cam.radius * sqrtf(u1);
+        const float theta = (float)(2 * 3.14159 * (double)u2);
+        float s, c;
+        det_sincos(theta, &s, &c);
+        lo = v3(r * c, r * s, 0.0f);
+    }
+    const V3 c = film - lo;
+    const V3 R = v3(w(a.view_right[0]), w(a.view_right[1]), w(a.view_right[2]));
+    const V3 U = v3(w(a.view_up[0]), w(a.view_up[1]), w(a.view_up[2]));
+    const V3 B = v3(w(a.view_back[0]), w(a.view_back[1]), w(a.view_back[2]));
+    *d = normalized(v3((R.x * c.x + U.x * c.y) + B.x * c.z, (R.y * c.x + U.y * c.y) + B.y * c.z, (R.z * c.x + U.z * c.y) + B.z * c.z));
+    if (lens)
+        *o = v3((R.x * lo.x + U.x * lo.y) + cam.pos[0], (R.y * lo.x + U.y * lo.y) + cam.pos[1], (R.z * lo.x + U.z * lo.y) + cam.pos[2]);
+    else
+        *o = v3(0.0f, 0.0f, 0.0f) + v3(cam.pos[0], cam.pos[1], cam.pos[2]);
+}
+
 __device__ __forceinline__ uint32_t morton2(uint32_t x, uint32_t y)   // camera.h:66-75
 {
     uint32_t r = 0;
@@ -597,8 +638,10 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
 }
 
 // ------------------------------------------------------------------ the render kernel
-template <int kIntegrator, bool kRefWalk, bool kCount>
-__global__ __launch_bounds__(64) void render_tiles(Args a)
+// (kView: the camera ray goes through the view, camera_ray_view -- render_tiles_view, kernels of their own launched
+// for an oriented render, so that the plain ones keep their names and compile exactly as they did without it)
+template <int kIntegrator, bool kRefWalk, bool kCount, bool kView>
+__device__ __forceinline__ void render_tiles_body(Args& a)
 {
     extern __shared__ uint32_t lds_stack[];
     const int lane = threadIdx.x;
@@ -629,7 +672,8 @@ __global__ __launch_bounds__(64) void render_tiles(Args a)
             float u1 = 0.0f, u2 = 0.0f;
             if (lens) { u1 = rng_uniform(rng); u2 = rng_uniform(rng); }
             V3 o, d;
-            camera_ray<false>(a.cam, px, py, lens, u1, u2, &o, &d);
+            if (kView) camera_ray_view<false>(a, px, py, lens, u1, u2, &o, &d);
+            else camera_ray<false>(a.cam, px, py, lens, u1, u2, &o, &d);
             C3 L;
             if (kIntegrator == PT_INTEGRATOR_HEAD) L = radiance_head(a, tr, o, d, rng, memo);
             else L = radiance_unidir(a, tr, o, d, rng, skip_dead, memo);
@@ -653,6 +697,16 @@ __global__ __launch_bounds__(64) void render_tiles(Args a)
         atomicAdd(a.counters + CNT_SAMPLES, c4);
         if (kCount) { atomicAdd(a.counters + CNT_NODES, c2); atomicAdd(a.counters + CNT_TRIS, c3v); }
     }
+}
+template <int kIntegrator, bool kRefWalk, bool kCount>
+__global__ __launch_bounds__(64) void render_tiles(Args a)
+{
+    render_tiles_body<kIntegrator, kRefWalk, kCount, false>(a);
+}
+template <int kIntegrator, bool kRefWalk, bool kCount>
+__global__ __launch_bounds__(64) void render_tiles_view(Args a)
+{
+    render_tiles_body<kIntegrator, kRefWalk, kCount, true>(a);
 }
 
 // ------------------------------------------------------------------ wavefront kernel
@@ -867,7 +921,10 @@ __global__ __launch_bounds__(256) void init_pixel_states(Args a, uint32_t* __res
     slot_stream(a, q, idx, n_done, r);
     const bool lens = (idx == 0) || (a.cam.radius != 0.0f);
     V3 o, d = v3(0.0f, 0.0f, 0.0f);
-    if (!lens) camera_ray(a.cam, px, py, false, 0.0f, 0.0f, &o, &d);   // the pixel's pinhole ray
+    if (!lens) {   // the pixel's pinhole ray
+        if (a.oriented) camera_ray_view(a, px, py, false, 0.0f, 0.0f, &o, &d);
+        else camera_ray(a.cam, px, py, false, 0.0f, 0.0f, &o, &d);
+    }
     uint32_t done = 0;
     for (uint32_t c = 0; c < nc; ++c) {
         const uint32_t s0 = split ? chunk_first(a, c, nc) : 0u;
@@ -916,7 +973,10 @@ __global__ __launch_bounds__(256) void init_active_states(Args a, uint32_t* __re
     slot_stream(a, q, idx, a.acc_n0, r);
     const bool lens = (idx == 0) || (a.cam.radius != 0.0f);
     V3 o, d = v3(0.0f, 0.0f, 0.0f);
-    if (!lens) camera_ray(a.cam, px, py, false, 0.0f, 0.0f, &o, &d);   // the pixel's pinhole ray
+    if (!lens) {   // the pixel's pinhole ray
+        if (a.oriented) camera_ray_view(a, px, py, false, 0.0f, 0.0f, &o, &d);
+        else camera_ray(a.cam, px, py, false, 0.0f, 0.0f, &o, &d);
+    }
     st[u] = r.v0;
     st[N + u] = r.v1;
     st[2 * N + u] = r.v2;
@@ -1089,7 +1149,9 @@ __device__ __forceinline__ const Args& kernel_args_opaque()
 // kAccum: a pass of an accumulator (Args::accum): a pixel's first unit starts from the slot's stored f64
 // mean, the unit that runs a pixel's last sample of the pass stores the XORWOW state back, and a whole
 // pixel's unit stores its mean.  Sample numbers, and so the divisors of the mean, continue from acc_n0.
-template <bool kCount, bool kAccum>
+// kView: the lens units' camera ray goes through the view (camera_ray_view); the host launches these instances
+// for an oriented render, so the plain ones compile exactly as they did without the view.
+template <bool kCount, bool kAccum, bool kView = false>
 __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, int lane, uint32_t& state, V3& ro, V3& rd,
                                            int32_t& htri, float& ht, W4& w, const Stack4& S,
                                            unsigned long long* lcnt, const uint32_t* lprobe, uint32_t* done_rel,
@@ -1156,7 +1218,8 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
         SEC(SEC_START);
         if (lens || !(fl & CF_CAMC)) {
             SEC(SEC_CAMERA);
-            camera_ray(a.cam, px, py, lens, u1, u2, &ro, &rd);
+            if (kView) camera_ray_view(a, px, py, lens, u1, u2, &ro, &rd);
+            else camera_ray(a.cam, px, py, lens, u1, u2, &ro, &rd);
             if (!lens) {   // a pinhole ray is the same for every sample of the pixel
                 R.st(CW_CD, __float_as_uint(rd.x)); R.st(CW_CD + 1, __float_as_uint(rd.y)); R.st(CW_CD + 2, __float_as_uint(rd.z));
                 fl |= CF_CAMC;
@@ -1895,7 +1958,8 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
         R.st4(HW_N0, __float_as_uint(n0.x), __float_as_uint(n0.y), __float_as_uint(n0.z), 0u);
         if (lens) {   // this sample's camera ray (its draws came first)
             V3 co, cd;
-            camera_ray(a.cam, px, py, true, lu1, lu2, &co, &cd);
+            if (a.oriented) camera_ray_view(a, px, py, true, lu1, lu2, &co, &cd);
+            else camera_ray(a.cam, px, py, true, lu1, lu2, &co, &cd);
             R.st4(HW_CD, __float_as_uint(cd.x), __float_as_uint(cd.y), __float_as_uint(cd.z), 0u);
             R.st4(HW_CO, __float_as_uint(co.x), __float_as_uint(co.y), __float_as_uint(co.z), 0u);
         }
@@ -2209,7 +2273,7 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
 // The wavefront kernel's body, shared by both integrators (kHead: integrator 1, shade_lane_head).
 // kLdsWalk: walk steps read the staged top from LDS (integrator 1 always; integrator 0 when the LDS
 // top holds the whole tree) instead of issuing every node's loads to memory.
-template <bool kCount, bool kHead, bool kLdsWalk = kHead, bool kAccum = false>
+template <bool kCount, bool kHead, bool kLdsWalk = kHead, bool kAccum = false, bool kView = false>
 __device__ __forceinline__ void wf_main(const Args& a)
 {
     extern __shared__ uint32_t lds_wf[];
@@ -2351,7 +2415,7 @@ __device__ __forceinline__ void wf_main(const Args& a)
         // (the lane id is recomputed for the shading pass: one VGPR less live across the walk loop)
         if (state != ST_TRACE && state != ST_DONE) {
             if (kHead) shade_lane_head<kCount, kAccum>(R, (int)__lane_id(), state, ro, rd, htri, ht, w, S, lcnt, lprobe, done_rel, cnt);
-            else shade_lane<kCount, kAccum>(a, R, (int)__lane_id(), state, ro, rd, htri, ht, w, S, lcnt, lprobe, done_rel, cnt);
+            else shade_lane<kCount, kAccum, kView>(a, R, (int)__lane_id(), state, ro, rd, htri, ht, w, S, lcnt, lprobe, done_rel, cnt);
         }
         if (kCount) shade_clk += clock64() - clk0;
         if (__ballot(state != ST_DONE) == 0ull) break;
@@ -2427,6 +2491,20 @@ __global__ __launch_bounds__(256, 5) void render_unidir_accum_wf(Args a)
 __global__ __launch_bounds__(256, 5) void render_head_accum_wf(Args a)
 {
     wf_main<false, true, true, true>(a);
+}
+
+// Integrator 0 through an oriented camera (Args::oriented; kView): twins of render_unidir_wf and
+// render_unidir_accum_wf, after them, so that a render without a view runs the kernels it always ran.  (Integrator
+// 1's kernels take the view under a uniform branch: their register budget did not move)
+template <bool kCount, int kMinWaves, bool kLdsWalk = false>
+__global__ __launch_bounds__(256, kMinWaves) void render_unidir_view_wf(Args a)
+{
+    wf_main<kCount, false, kLdsWalk, false, true>(a);
+}
+template <bool kLdsWalk>
+__global__ __launch_bounds__(256, 5) void render_unidir_accum_view_wf(Args a)
+{
+    wf_main<false, false, kLdsWalk, true, true>(a);
 }
 
 // ------------------------------------------------------------------ output step
@@ -2533,7 +2611,9 @@ __global__ __launch_bounds__(256) void trace_rays(Args a, const float* __restric
 // trace_rays<false, false> traces a ray, then the hit's material and normal as one 48-B pt_feature.
 // One lane per work slot, in the wavefront kernels' slot order (unit_pixel: a wave = one 8x8 block, so
 // its rays are coherent); slots outside the image write nothing.
-__global__ __launch_bounds__(256) void primary_features(Args a, float4* __restrict__ out)
+// (kView: the oriented pinhole ray; primary_features_view is the kernel of a render with a view)
+template <bool kView>
+__device__ __forceinline__ void primary_features_body(const Args& a, float4* __restrict__ out)
 {
     extern __shared__ uint32_t lds_tr[];
     const int lane = threadIdx.x & 63;
@@ -2550,7 +2630,8 @@ __global__ __launch_bounds__(256) void primary_features(Args a, float4* __restri
         uint32_t px, py;
         if (!unit_pixel(a, q, &px, &py)) continue;
         V3 o, d;
-        camera_ray<false>(a.cam, px, py, false, 0.0f, 0.0f, &o, &d);
+        if (kView) camera_ray_view<false>(a, px, py, false, 0.0f, 0.0f, &o, &d);
+        else camera_ray<false>(a.cam, px, py, false, 0.0f, 0.0f, &o, &d);
         int32_t htri = -1;
         float ht = kMaxFloat;
         if (a.num_tris == 0) {
@@ -2594,6 +2675,14 @@ __global__ __launch_bounds__(256) void primary_features(Args a, float4* __restri
         float4* rec = out + out_pixel(a, px, py) * 3;
         rec[0] = r0; rec[1] = r1; rec[2] = r2;
     }
+}
+__global__ __launch_bounds__(256) void primary_features(Args a, float4* __restrict__ out)
+{
+    primary_features_body<false>(a, out);
+}
+__global__ __launch_bounds__(256) void primary_features_view(Args a, float4* __restrict__ out)
+{
+    primary_features_body<true>(a, out);
 }
 
 }  // namespace

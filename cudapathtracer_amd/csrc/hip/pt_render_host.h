@@ -263,12 +263,20 @@ static void fill_scene_args(Args& a, const pt_ctx* c)
     a.hrec = c->hrec;
 }
 
-// The camera, the image and this shard's tile grid (validated parameters).
-static void fill_view_args(Args& a, const pt_params& p, const pt_camera& cam)
+// The camera, its view (null: the reference camera), the image and this shard's tile grid (validated parameters).
+static void fill_view_args(Args& a, const pt_params& p, const pt_camera& cam, const pt_view* view)
 {
     a.cam.pos[0] = cam.pos.x; a.cam.pos[1] = cam.pos.y; a.cam.pos[2] = cam.pos.z;
     a.cam.dist = cam.dist_from_film; a.cam.focal = cam.focal_length; a.cam.radius = cam.radius;
     a.cam.w = cam.pxl_width; a.cam.h = cam.pxl_height;
+    a.oriented = view ? 1u : 0u;
+    if (view) {
+        memcpy(a.view_right, view->right, sizeof(a.view_right));
+        memcpy(a.view_up, view->up, sizeof(a.view_up));
+        memcpy(a.view_back, view->back, sizeof(a.view_back));
+        a.film_w = view->film_w;
+        a.film_h = view->film_h;
+    }
     const pt::TileGrid g = pt::tile_grid(p);
     a.w = g.w; a.h = g.h;
     a.shard_index = g.shard_index; a.shard_count = g.shard_count;
@@ -435,7 +443,8 @@ struct LaneTiming {
 };
 }  // namespace
 
-// The integration kernel of a wavefront render: the instance pt::wavefront_variant names.
+// The integration kernel of a wavefront render: the instance pt::wavefront_variant names.  An oriented render
+// (b.oriented) of integrator 0 takes that instance's view twin; integrator 1's instances serve both.
 static int launch_wavefront(const pt::WavefrontVariant& v, const WavefrontLaunch& L, hipStream_t stream, const Args& b)
 {
     constexpr auto code = [](bool head, bool count, int min_waves, bool lds_walk, bool accum) {
@@ -460,6 +469,22 @@ static int launch_wavefront(const pt::WavefrontVariant& v, const WavefrontLaunch
         return pt::fail(PT_E_INVALID, "pt_render: no wavefront kernel instance for head %d count %d waves %d lds %d accum %d",
                         v.head, v.count, v.min_waves, v.lds_walk, v.accum);
     }
+    if (b.oriented && !v.head) {   // (below every plain instance, so that those are emitted first, as they were)
+        switch (v.code()) {
+        case code(false, false, 5, true, true): kernel = render_unidir_accum_view_wf<true>; break;
+        case code(false, false, 5, false, true): kernel = render_unidir_accum_view_wf<false>; break;
+        case code(false, true, 4, false, false): kernel = render_unidir_view_wf<true, 4>; break;
+        case code(false, true, 5, true, false): kernel = render_unidir_view_wf<true, 5, true>; break;
+        case code(false, true, 5, false, false): kernel = render_unidir_view_wf<true, 5>; break;
+        case code(false, false, 6, false, false): kernel = render_unidir_view_wf<false, 6>; break;
+        case code(false, false, 5, true, false): kernel = render_unidir_view_wf<false, 5, true>; break;
+        case code(false, false, 5, false, false): kernel = render_unidir_view_wf<false, 5>; break;
+        case code(false, false, 4, false, false): kernel = render_unidir_view_wf<false, 4>; break;
+        default:
+            return pt::fail(PT_E_INVALID, "pt_render: no oriented wavefront kernel instance for count %d waves %d lds %d accum %d",
+                            v.count, v.min_waves, v.lds_walk, v.accum);
+        }
+    }
     hipLaunchKernelGGL(kernel, dim3(L.blocks), dim3(256), L.lds, stream, b);
     HIP_TRY(hipGetLastError());
     return PT_OK;
@@ -478,6 +503,8 @@ static int launch_tiles(const pt_ctx* c, const pt_params* p, pt_ctx::Bufs& B, si
     const bool refwalk = (p->flags & PT_FLAG_REFERENCE_TRAVERSAL) != 0, count = (p->flags & PT_FLAG_COUNT) != 0;
     // (the instances in this order: the order of first use is the order the compiler emits them in)
 #define PT_LAUNCH(I, R, C) hipLaunchKernelGGL((render_tiles<I, R, C>), dim3(grid), dim3(64), lds, stream, a)
+#define PT_LAUNCH_VIEW(I, R, C) hipLaunchKernelGGL((render_tiles_view<I, R, C>), dim3(grid), dim3(64), lds, stream, a)
+    if (!a.oriented) {
     if (p->integrator == PT_INTEGRATOR_HEAD) {
         if (refwalk) { if (count) PT_LAUNCH(1, true, true); else PT_LAUNCH(1, true, false); }
         else { if (count) PT_LAUNCH(1, false, true); else PT_LAUNCH(1, false, false); }
@@ -485,6 +512,14 @@ static int launch_tiles(const pt_ctx* c, const pt_params* p, pt_ctx::Bufs& B, si
         if (refwalk) { if (count) PT_LAUNCH(0, true, true); else PT_LAUNCH(0, true, false); }
         else { if (count) PT_LAUNCH(0, false, true); else PT_LAUNCH(0, false, false); }
     }
+    } else if (p->integrator == PT_INTEGRATOR_HEAD) {   // (the view's instances: after every plain one)
+        if (refwalk) { if (count) PT_LAUNCH_VIEW(1, true, true); else PT_LAUNCH_VIEW(1, true, false); }
+        else { if (count) PT_LAUNCH_VIEW(1, false, true); else PT_LAUNCH_VIEW(1, false, false); }
+    } else {
+        if (refwalk) { if (count) PT_LAUNCH_VIEW(0, true, true); else PT_LAUNCH_VIEW(0, true, false); }
+        else { if (count) PT_LAUNCH_VIEW(0, false, true); else PT_LAUNCH_VIEW(0, false, false); }
+    }
+#undef PT_LAUNCH_VIEW
 #undef PT_LAUNCH
     HIP_TRY(hipGetLastError());
     return PT_OK;
@@ -537,13 +572,15 @@ static int enqueue_wavefront(pt_ctx* c, const pt_params* p, const pt::AccumPass*
 // acc: the render is a pass of an accumulator (pt::accum_pass) -- p->spp more samples of every pixel on top
 // of its acc->n0, from and to the accumulator's state; d_out may then be null.  Everything else -- the
 // unit split, the buffers' growth, the jump and seed tables, the flight slots -- is the plain render's.
-static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, float* d_out, void* stream_v,
+static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view, float* d_out, void* stream_v,
                           const pt::AccumPass* acc)
 {
     if (!c || !p || !cam || (!d_out && !acc)) return pt::fail(PT_E_INVALID, "pt_render: null argument");
     if (c->fl_n >= pt_ctx::kFlights)
         return pt::fail(PT_E_INVALID, "pt_render_device_async: %d renders in flight (pt_render_wait first)", c->fl_n);
     if (int rc = pt::validate_render(p, cam)) return rc;
+    if (view)
+        if (int rc = pt::validate_view("pt_render", view)) return rc;
     // the per-triangle counts live in one context-wide buffer (pt_tri_counts reads it back): only one render
     // in flight may fill them
     if ((p->flags & PT_FLAG_COUNT) && (p->flags & PT_FLAG_TRI_COUNTS) && c->fl_n > 0)
@@ -563,7 +600,7 @@ static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, f
     Args a;
     memset(&a, 0, sizeof(a));
     fill_scene_args(a, c);
-    fill_view_args(a, *p, *cam);
+    fill_view_args(a, *p, *cam, view);
     a.out = d_out; a.counters = B.counters; a.tile_counter = B.tile_counter;
     a.spp = p->spp; a.bounces = p->bounces; a.flags = p->flags; a.seed = p->seed;
     const bool count = (p->flags & PT_FLAG_COUNT) != 0;
@@ -624,10 +661,16 @@ static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, f
     return PT_OK;
 }
 
-int pt_render_device_async(pt_ctx* c, const pt_params* p, const pt_camera* cam, float* d_out, void* stream_v)
+int pt_render_device_view_async(pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view, float* d_out,
+                                void* stream_v)
 {
     if (!d_out) return pt::fail(PT_E_INVALID, "pt_render: null argument");
-    return render_enqueue(c, p, cam, d_out, stream_v, nullptr);
+    return render_enqueue(c, p, cam, view, d_out, stream_v, nullptr);
+}
+
+int pt_render_device_async(pt_ctx* c, const pt_params* p, const pt_camera* cam, float* d_out, void* stream_v)
+{
+    return pt_render_device_view_async(c, p, cam, nullptr, d_out, stream_v);
 }
 
 int pt_render_wait(pt_ctx* c, pt_stats* st)
@@ -691,20 +734,28 @@ int pt_render_wait(pt_ctx* c, pt_stats* st)
     return PT_OK;
 }
 
-int pt_render_device(pt_ctx* c, const pt_params* p, const pt_camera* cam, float* d_out, void* stream, pt_stats* st)
+int pt_render_device_view(pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view, float* d_out, void* stream,
+                          pt_stats* st)
 {
     if (c && c->fl_n > 0)
         return pt::fail(PT_E_INVALID, "pt_render_device: %d asynchronous renders in flight (pt_render_wait first)", c->fl_n);
-    if (int rc = pt_render_device_async(c, p, cam, d_out, stream)) return rc;
+    if (int rc = pt_render_device_view_async(c, p, cam, view, d_out, stream)) return rc;
     return pt_render_wait(c, st);
+}
+
+int pt_render_device(pt_ctx* c, const pt_params* p, const pt_camera* cam, float* d_out, void* stream, pt_stats* st)
+{
+    return pt_render_device_view(c, p, cam, nullptr, d_out, stream, st);
 }
 
 }  // extern "C"
 
 // ---- accumulating passes (host_internal.h): the render context's side of pt_accum.cpp
-int pt::accum_check(const pt_ctx* c, const pt_params* p, const pt_camera* cam)
+int pt::accum_check(const pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view)
 {
     if (int rc = validate_render(p, cam)) return rc;
+    if (view)
+        if (int rc = validate_view("pt_accum_create", view)) return rc;
     const RenderKnobs& K = c->knobs;
     if (p->flags & ~(uint32_t)(PT_FLAG_NO_DEAD_PATH_SKIP | PT_FLAG_NO_PRIMARY_CACHE))
         return pt::fail(PT_E_INVALID, "pt_accum_create: flags 0x%x: only PT_FLAG_NO_DEAD_PATH_SKIP and PT_FLAG_NO_PRIMARY_CACHE "
@@ -719,12 +770,12 @@ int pt::accum_check(const pt_ctx* c, const pt_params* p, const pt_camera* cam)
     return PT_OK;
 }
 
-int pt::accum_pass(pt_ctx* c, const pt_params* p, const pt_camera* cam, const AccumPass& acc, float* d_out, void* stream,
-                   pt_stats* stats)
+int pt::accum_pass(pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view, const AccumPass& acc, float* d_out,
+                   void* stream, pt_stats* stats)
 {
     if (c->fl_n > 0)
         return pt::fail(PT_E_INVALID, "pt_accum_add: %d asynchronous renders in flight (pt_render_wait first)", c->fl_n);
-    if (int rc = render_enqueue(c, p, cam, d_out, stream, &acc)) return rc;
+    if (int rc = render_enqueue(c, p, cam, view, d_out, stream, &acc)) return rc;
     return pt_render_wait(c, stats);
 }
 
@@ -785,13 +836,18 @@ extern "C" {
 
 int pt_render(pt_ctx* c, const pt_params* p, const pt_camera* cam, float* out_rgb, pt_stats* st)
 {
+    return pt_render_view(c, p, cam, nullptr, out_rgb, st);
+}
+
+int pt_render_view(pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view, float* out_rgb, pt_stats* st)
+{
     if (!c || !p || !out_rgb) return pt::fail(PT_E_INVALID, "pt_render: null argument");
     if (p->width <= 0 || p->height <= 0) return pt::fail(PT_E_INVALID, "pt_render: bad image size");
     HIP_TRY(hipSetDevice(c->device));
     const size_t bytes = (size_t)p->width * (size_t)p->height * 3 * sizeof(float);
     if (int rc = pt::grow(&c->scratch_out, &c->scratch_floats, bytes / sizeof(float))) return rc;
     HIP_TRY(hipMemsetAsync(c->scratch_out, 0, bytes, nullptr));
-    int rc = pt_render_device(c, p, cam, c->scratch_out, nullptr, st);
+    int rc = pt_render_device_view(c, p, cam, view, c->scratch_out, nullptr, st);
     if (rc != PT_OK) return rc;
     return pt::copy_to_host(out_rgb, c->scratch_out, bytes, nullptr, &c->pinned, &c->pinned_bytes);
 }
@@ -875,7 +931,8 @@ extern "C" int pt_trace_counts(pt_ctx* c, uint32_t n, const float* rays, int32_t
 }
 
 // What pt_render_features* checks before touching the device; *vp = params with the ignored fields neutral.
-static int features_check(const pt_ctx* c, const pt_params* p, const pt_camera* cam, const void* feat, pt_params* vp)
+static int features_check(const pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view, const void* feat,
+                          pt_params* vp)
 {
     if (!c || !p || !cam || !feat) return pt::fail(PT_E_INVALID, "pt_render_features: null argument");
     if (c->fl_n > 0)
@@ -883,6 +940,8 @@ static int features_check(const pt_ctx* c, const pt_params* p, const pt_camera* 
     *vp = *p;
     vp->spp = 0; vp->bounces = 1; vp->integrator = PT_INTEGRATOR_UNIDIR; vp->flags = 0; vp->seed = 0;
     if (int rc = pt::validate_render(vp, cam)) return rc;
+    if (view)
+        if (int rc = pt::validate_view("pt_render_features", view)) return rc;
     if ((uint64_t)c->num_tris + (uint64_t)c->num_spheres >= (uint64_t)PT_FEATURE_EMISSIVE)
         return pt::fail(PT_E_INVALID, "pt_render_features: %u triangles + %u spheres do not fit the 30 id bits of pt_feature.prim",
                         c->num_tris, c->num_spheres);
@@ -891,10 +950,16 @@ static int features_check(const pt_ctx* c, const pt_params* p, const pt_camera* 
 
 extern "C" int pt_render_features_device(pt_ctx* c, const pt_params* p_in, const pt_camera* cam, pt_feature* d_feat, void* stream_v)
 {
+    return pt_render_features_view_device(c, p_in, cam, nullptr, d_feat, stream_v);
+}
+
+extern "C" int pt_render_features_view_device(pt_ctx* c, const pt_params* p_in, const pt_camera* cam, const pt_view* view,
+                                              pt_feature* d_feat, void* stream_v)
+{
     pt::clear_error();
     static_assert(sizeof(pt_feature) == 48, "pt_feature is 48 B");
     pt_params pv;
-    if (int rc = features_check(c, p_in, cam, d_feat, &pv)) return rc;
+    if (int rc = features_check(c, p_in, cam, view, d_feat, &pv)) return rc;
     if (reinterpret_cast<uintptr_t>(d_feat) % 16 != 0)
         return pt::fail(PT_E_INVALID, "pt_render_features_device: d_feat must be 16-byte aligned");
     const pt_params* p = &pv;
@@ -903,7 +968,7 @@ extern "C" int pt_render_features_device(pt_ctx* c, const pt_params* p_in, const
     Args a;
     memset(&a, 0, sizeof(a));
     fill_scene_args(a, c);
-    fill_view_args(a, *p, *cam);
+    fill_view_args(a, *p, *cam, view);
     a.node_mask = c->node4_mask;
     a.stack_words = kWaveLdsWords;
     const size_t lds = (size_t)a.stack_words * 4 * 4;
@@ -914,7 +979,8 @@ extern "C" int pt_render_features_device(pt_ctx* c, const pt_params* p_in, const
     if (int rc = pt::grow(&c->rb[0].spill, &c->rb[0].spill_words, stack_words_per_lane(c) * (size_t)blocks * 256)) return rc;
     a.spill = c->rb[0].spill;
     a.spill_stride = blocks * 256;
-    hipLaunchKernelGGL(primary_features, dim3(blocks), dim3(256), lds, stream, a, reinterpret_cast<float4*>(d_feat));
+    hipLaunchKernelGGL(a.oriented ? primary_features_view : primary_features, dim3(blocks), dim3(256), lds, stream, a,
+                       reinterpret_cast<float4*>(d_feat));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
     return PT_OK;
@@ -922,9 +988,14 @@ extern "C" int pt_render_features_device(pt_ctx* c, const pt_params* p_in, const
 
 extern "C" int pt_render_features(pt_ctx* c, const pt_params* p, const pt_camera* cam, pt_feature* feat)
 {
+    return pt_render_features_view(c, p, cam, nullptr, feat);
+}
+
+extern "C" int pt_render_features_view(pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view, pt_feature* feat)
+{
     pt::clear_error();
     pt_params pv;
-    if (int rc = features_check(c, p, cam, feat, &pv)) return rc;
+    if (int rc = features_check(c, p, cam, view, feat, &pv)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)p->width * (size_t)p->height;
     pt_feature none;
@@ -934,7 +1005,7 @@ extern "C" int pt_render_features(pt_ctx* c, const pt_params* p, const pt_camera
     pt::ScopedDevice<pt_feature> d_feat;
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_feat), n * sizeof(pt_feature)));
     HIP_TRY(hipMemcpy(d_feat, feat, n * sizeof(pt_feature), hipMemcpyHostToDevice));
-    if (int rc = pt_render_features_device(c, p, cam, d_feat, nullptr)) return rc;
+    if (int rc = pt_render_features_view_device(c, p, cam, view, d_feat, nullptr)) return rc;
     HIP_TRY(hipMemcpy(feat, d_feat, n * sizeof(pt_feature), hipMemcpyDeviceToHost));
     return PT_OK;
 }

@@ -20,7 +20,8 @@ namespace {
 // The session header (documented in pt.h); every field little-endian at a fixed offset.  Bytes 0..127 are the
 // checkpoint header of format version 1.
 constexpr char kMagic[8] = {'P', 'T', 'A', 'C', 'C', 'U', 'M', '\0'};
-constexpr uint32_t kVersion = 2;
+constexpr uint32_t kVersion = 2;        // without a view: byte for byte the format it always was
+constexpr uint32_t kVersionView = 3;    // with a view: version 2's 192 bytes, then the 64-byte ViewTail
 constexpr uint32_t kCounts = 0x1u, kNoise = 0x2u, kNoisePerPixel = 0x4u;
 constexpr size_t kBytesA = 48, kBytesB = 4, kBytesC = 40, kBytesD = 8;
 struct Header {
@@ -41,6 +42,13 @@ struct Header {
     uint64_t frozen_pixels;
     unsigned char zero2[24];
 };
+// Format version 3's header is version 2's, then this: the file is recognised by its version and header size together.
+struct ViewTail {
+    pt_view view;            // 44 B at 192
+    unsigned char zero[20];
+};
+static_assert(sizeof(ViewTail) == 64, "the view's part of a version-3 header is 64 B");
+constexpr size_t kHeaderView = sizeof(Header) + sizeof(ViewTail);   // 256
 static_assert(sizeof(pt_params) == 56, "pt_params is 56 B in the session header");
 static_assert(sizeof(Header) == 192, "session header is 192 B");
 static_assert(offsetof(Header, flags) == 128 && offsetof(Header, noise_n0) == 136 && offsetof(Header, noise_batches) == 152 &&
@@ -57,26 +65,41 @@ bool little_endian()
 size_t file_bytes(const Header& h)
 {
     const size_t n = (size_t)h.params.width * (size_t)h.params.height;
-    return sizeof(Header) + n * (kBytesA + ((h.flags & kCounts) ? kBytesB : 0) + ((h.flags & kNoise) ? kBytesC : 0) +
+    return (size_t)h.header_bytes + n * (kBytesA + ((h.flags & kCounts) ? kBytesB : 0) + ((h.flags & kNoise) ? kBytesC : 0) +
                                  ((h.flags & kNoisePerPixel) ? kBytesD : 0));
 }
 
 // Reads and validates the header of `path` and the file's size; *keep: the file, positioned at the sections.
-int read_header(const char* what, const char* path, Header* h, FILE** keep)
+// *has_view: the file is format version 3, and *view its (validated) view.
+int read_header(const char* what, const char* path, Header* h, pt_view* view, bool* has_view, FILE** keep)
 {
+    *has_view = false;
     if (!little_endian()) return pt::fail(PT_E_INVALID, "%s: session files are little-endian; this host is not", what);
     FILE* f = fopen(path, "rb");
     if (!f) return pt::fail(PT_E_IO, "%s: cannot open %s", what, path);
     auto bail = [&](int code) { fclose(f); return code; };
     if (fread(h, 1, 16, f) != 16) return bail(pt::fail(PT_E_IO, "%s: %s is shorter than a header", what, path));
     if (memcmp(h->magic, kMagic, 8) != 0) return bail(pt::fail(PT_E_INVALID, "%s: %s is not a session file (bad magic)", what, path));
-    if (h->version != kVersion)
-        return bail(pt::fail(PT_E_INVALID, "%s: %s has format version %u, a session file has %u%s", what, path, h->version, kVersion,
-                             h->version == 1 ? " (a version-1 checkpoint: pt_accum_load reads it)" : ""));
-    if (h->header_bytes != sizeof(Header))
-        return bail(pt::fail(PT_E_INVALID, "%s: %s has a %u-byte header, expected %zu", what, path, h->header_bytes, sizeof(Header)));
+    if (h->version != kVersion && h->version != kVersionView)
+        return bail(pt::fail(PT_E_INVALID, "%s: %s has format version %u, a session file has %u (or %u with a view)%s", what, path,
+                             h->version, kVersion, kVersionView, h->version == 1 ? " (a version-1 checkpoint: pt_accum_load reads it)" : ""));
+    const size_t header_want = h->version == kVersionView ? kHeaderView : sizeof(Header);
+    if (h->header_bytes != header_want)
+        return bail(pt::fail(PT_E_INVALID, "%s: %s has a %u-byte header, format version %u has %zu", what, path, h->header_bytes,
+                             h->version, header_want));
     if (fread(reinterpret_cast<char*>(h) + 16, 1, sizeof(Header) - 16, f) != sizeof(Header) - 16)
         return bail(pt::fail(PT_E_IO, "%s: %s is shorter than the %zu-byte header", what, path, sizeof(Header)));
+    if (h->version == kVersionView) {
+        ViewTail t;
+        if (fread(&t, 1, sizeof(t), f) != sizeof(t))
+            return bail(pt::fail(PT_E_IO, "%s: %s is truncated inside the %zu-byte header (the view)", what, path, kHeaderView));
+        for (const unsigned char z : t.zero)
+            if (z) return bail(pt::fail(PT_E_INVALID, "%s: %s has a non-zero byte in the reserved bytes 236..255 of its header", what, path));
+        const std::string who = std::string(what) + ": " + path;
+        if (int rc = pt::validate_view(who.c_str(), &t.view)) return bail(rc);
+        *view = t.view;
+        *has_view = true;
+    }
     const pt_params& p = h->params;
     if (p.width <= 0 || p.height <= 0 || p.width > 65535 || p.height > 65535 || h->samples < 0 ||
         h->samples > (int64_t)pt::accum_max_samples())
@@ -106,7 +129,7 @@ int read_header(const char* what, const char* path, Header* h, FILE** keep)
     if (size > want)
         return bail(pt::fail(PT_E_INVALID, "%s: %s has %lld bytes, its %dx%d sections make %lld", what, path, size, p.width, p.height, want));
     if (keep) {
-        if (fseek(f, (long)sizeof(Header), SEEK_SET) != 0) return bail(pt::fail(PT_E_IO, "%s: cannot seek in %s", what, path));
+        if (fseek(f, (long)h->header_bytes, SEEK_SET) != 0) return bail(pt::fail(PT_E_IO, "%s: cannot seek in %s", what, path));
         *keep = f;
     } else {
         fclose(f);
@@ -182,8 +205,11 @@ int pt_session_save(pt_accum* acc, pt_noise* noise, const char* path)
     Header h;
     memset(&h, 0, sizeof(h));
     memcpy(h.magic, kMagic, 8);
-    h.version = kVersion;
-    h.header_bytes = (uint32_t)sizeof(Header);
+    h.version = sa.view ? kVersionView : kVersion;
+    h.header_bytes = (uint32_t)(sa.view ? kHeaderView : sizeof(Header));
+    ViewTail tail;
+    memset(&tail, 0, sizeof(tail));
+    if (sa.view) tail.view = *sa.view;
     h.params = *sa.params;
     h.cam = *sa.cam;
     h.samples = sa.samples;
@@ -219,7 +245,8 @@ int pt_session_save(pt_accum* acc, pt_noise* noise, const char* path)
     FILE* f = fopen(path, "wb");
     if (!f) return pt::fail(PT_E_IO, "pt_session_save: cannot open %s for writing", path);
     const char* host = static_cast<const char*>(S->host);
-    bool ok = fwrite(&h, 1, sizeof(h), f) == sizeof(h) && fwrite(host + pl.at.a, kBytesA, npix, f) == npix;
+    bool ok = fwrite(&h, 1, sizeof(h), f) == sizeof(h) && (!sa.view || fwrite(&tail, 1, sizeof(tail), f) == sizeof(tail)) &&
+              fwrite(host + pl.at.a, kBytesA, npix, f) == npix;
     if (ok && (h.flags & kCounts)) ok = fwrite(host + pl.at.b, kBytesB, npix, f) == npix;
     if (ok && (h.flags & kNoise)) ok = fwrite(host + pl.at.c, kBytesC, npix, f) == npix;
     if (ok && (h.flags & kNoisePerPixel)) ok = fwrite(host + pl.at.d, kBytesD, npix, f) == npix;
@@ -239,8 +266,10 @@ int pt_session_load(pt_ctx* ctx, const char* path, pt_accum** acc_out, pt_noise*
         return pt::fail(PT_E_INVALID, "pt_session_load: %d asynchronous renders in flight (pt_render_wait first)", pt::ctx_in_flight(ctx));
     pt::StageTimer timer{"pt_session_load"};
     Header h;
+    pt_view view;
+    bool has_view = false;
     FILE* f = nullptr;
-    if (int rc = read_header("pt_session_load", path, &h, &f)) return rc;
+    if (int rc = read_header("pt_session_load", path, &h, &view, &has_view, &f)) return rc;
     auto bail = [&](int code) { fclose(f); return code; };
     uint64_t digest;
     uint32_t nt, ns;
@@ -273,7 +302,7 @@ int pt_session_load(pt_ctx* ctx, const char* path, pt_accum** acc_out, pt_noise*
         const std::string why = pt_last_error();
         return pt::fail(rc, "pt_session_load: %s: %s", path, why.c_str());
     };
-    pt_accum* acc = pt::accum_session_new(ctx, &h.params, &h.cam, h.samples, counts, &code);
+    pt_accum* acc = pt::accum_session_new(ctx, &h.params, &h.cam, has_view ? &view : nullptr, h.samples, counts, &code);
     if (!acc) return renamed(code);
     pt_noise* noise = nullptr;
     auto fill = [&]() -> int {
@@ -322,7 +351,9 @@ int pt_session_file_info(const char* path, pt_session_info* info)
     pt::clear_error();
     if (!path || !info) return pt::fail(PT_E_INVALID, "pt_session_file_info: null argument");
     Header h;
-    if (int rc = read_header("pt_session_file_info", path, &h, nullptr)) return rc;
+    pt_view view;
+    bool has_view = false;
+    if (int rc = read_header("pt_session_file_info", path, &h, &view, &has_view, nullptr)) return rc;
     memset(info, 0, sizeof(*info));
     info->params = h.params;
     info->cam = h.cam;
@@ -333,6 +364,19 @@ int pt_session_file_info(const char* path, pt_session_info* info)
     info->noise_n0 = h.noise_n0;
     info->noise_W = h.noise_W;
     info->frozen_pixels = h.frozen_pixels;
+    return PT_OK;
+}
+
+int pt_session_file_view(const char* path, pt_view* out, int* has_view_out)
+{
+    pt::clear_error();
+    if (!path) return pt::fail(PT_E_INVALID, "pt_session_file_view: null path");
+    Header h;
+    pt_view view;
+    bool has_view = false;
+    if (int rc = read_header("pt_session_file_view", path, &h, &view, &has_view, nullptr)) return rc;
+    if (has_view_out) *has_view_out = has_view ? 1 : 0;
+    if (out && has_view) *out = view;
     return PT_OK;
 }
 

@@ -17,12 +17,17 @@ static_assert(sizeof(pt_material) == 48, "materialDesc is 48 B (modelLoader.h:21
 static_assert(sizeof(pt_sphere) == 64, "sphere.h sphere is 64 B");
 static_assert(sizeof(pt_bvh_node) == 32, "BVH_array_node is 32 B (BVH.h:111-115)");
 static_assert(sizeof(pt_camera) == 32, "camera is 32 B (camera.h:26-34)");
+static_assert(sizeof(pt_view) == 44, "pt_view is 44 B (11 floats, no padding)");
 
 namespace pt {
 
 // Thread-local error channel behind pt_last_error().
 int fail(int code, const char* fmt, ...);
 void clear_error();
+
+// The condition a pt_view must meet (pt.h: finite, film > 0, orthonormal to 1e-3 in double); PT_E_INVALID under
+// `who`'s name otherwise (scene.cpp).
+int validate_view(const char* who, const pt_view* v);
 
 // The HIP device ordinal a render context lives on (pt_render_host.h; used by pt_multi.cpp).
 int ctx_device(const pt_ctx* c);
@@ -50,10 +55,11 @@ struct AccumPass {
 };
 // Validates (params, cam) as pt_render_device_async does and refuses every mode without an accumulating
 // kernel (render_tiles, the counting variants, non-default occupancy).
-int accum_check(const pt_ctx* c, const pt_params* p, const pt_camera* cam);
+// (view: the accumulator's pt_view, or null for the reference camera)
+int accum_check(const pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view);
 // p->spp more samples of every pixel (of every active pixel), blocking; d_out (device, W*H*3) may be null.
-int accum_pass(pt_ctx* c, const pt_params* p, const pt_camera* cam, const AccumPass& acc, float* d_out, void* stream,
-               pt_stats* stats);
+int accum_pass(pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view, const AccumPass& acc, float* d_out,
+               void* stream, pt_stats* stats);
 // Work slot q of the shard -> scanline pixel id y*W + x, or 0xffffffff for a slot outside the image.
 int shard_slots(const pt_params* p, std::vector<uint32_t>* pix);
 // The FNV-1a digest of the scene arrays the context was created from, and their primitive counts.
@@ -118,6 +124,7 @@ struct SessionAccum {
     pt_ctx* ctx;
     const pt_params* params;
     const pt_camera* cam;
+    const pt_view* view;           // null: the reference camera (a version-2 file)
     int64_t samples;
     size_t slots;
     uint64_t pixels;               // work slots inside the image
@@ -131,7 +138,8 @@ struct SessionAccum {
 int accum_session(pt_accum* acc, SessionAccum* out);
 // A new accumulator at `samples` whose planes session_unpack fills; counts: with the frozen_at plane, in the state
 // pt_accum_freeze leaves (a pixel is frozen, the active list invalid).  Null with *code set on failure.
-pt_accum* accum_session_new(pt_ctx* c, const pt_params* p, const pt_camera* cam, int64_t samples, bool counts, int* code);
+pt_accum* accum_session_new(pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view, int64_t samples, bool counts,
+                            int* code);
 struct SessionNoise {
     double* state;                 // device: prev[3], mu, m2 planes of slots doubles
     uint32_t* pix;                 // device: W_q, b_q planes of slots words; null unless they carry the state

@@ -51,6 +51,26 @@ void clear_error() { g_error.clear(); }
 
 const char* last_error_cstr() { return g_error.c_str(); }
 
+// The condition of pt.h: 11 finite floats, a film > 0, an orthonormal basis to 1e-3 (in double).
+int validate_view(const char* who, const pt_view* v)
+{
+    const float* f = v->right;   // (right, up, back, film_w, film_h: 11 consecutive floats)
+    for (int k = 0; k < 11; ++k)
+        if (!std::isfinite(f[k])) return fail(PT_E_INVALID, "%s: view: a component is not finite", who);
+    if (!(v->film_w > 0.0f) || !(v->film_h > 0.0f))
+        return fail(PT_E_INVALID, "%s: view: film %g x %g must be > 0", who, (double)v->film_w, (double)v->film_h);
+    auto dotd = [](const float* a, const float* b) {
+        return ((double)a[0] * (double)b[0] + (double)a[1] * (double)b[1]) + (double)a[2] * (double)b[2];
+    };
+    const double e[6] = {dotd(v->right, v->right) - 1.0, dotd(v->up, v->up) - 1.0, dotd(v->back, v->back) - 1.0,
+                         dotd(v->right, v->up), dotd(v->right, v->back), dotd(v->up, v->back)};
+    static const char* const names[6] = {"right.right - 1", "up.up - 1", "back.back - 1", "right.up", "right.back", "up.back"};
+    for (int k = 0; k < 6; ++k)
+        if (!(std::fabs(e[k]) <= 1e-3))
+            return fail(PT_E_INVALID, "%s: view: the basis is not orthonormal (%s = %g, limit 1e-3)", who, names[k], e[k]);
+    return PT_OK;
+}
+
 }  // namespace pt
 
 using namespace pt;
@@ -217,6 +237,96 @@ void pt_camera_ray(const pt_camera* cam, uint32_t idx, int lens, float u1, float
     film = v3(film.x * k / cam->dist_from_film, film.y * k / cam->dist_from_film, film.z * k / cam->dist_from_film);
     *origin = v3(o.x + cam->pos.x, o.y + cam->pos.y, o.z + cam->pos.z);
     *dir = vunit(vsub(film, o));
+}
+
+// ---- the oriented camera (pt_view, pt.h): no counterpart in the reference
+int pt_view_validate(const pt_view* v)
+{
+    pt::clear_error();
+    if (!v) return pt::fail(PT_E_INVALID, "pt_view_validate: null view");
+    return pt::validate_view("pt_view_validate", v);
+}
+
+int pt_view_look_at(pt_vec3 pos, pt_vec3 target, pt_vec3 up, pt_view* out)
+{
+    pt::clear_error();
+    if (!out) return pt::fail(PT_E_INVALID, "pt_view_look_at: null view");
+    for (const float c : {pos.x, pos.y, pos.z, target.x, target.y, target.z, up.x, up.y, up.z})
+        if (!std::isfinite(c)) return pt::fail(PT_E_INVALID, "pt_view_look_at: a component is not finite");
+    // all in double from the float inputs, rounded to float once at the end
+    const double b[3] = {(double)pos.x - (double)target.x, (double)pos.y - (double)target.y, (double)pos.z - (double)target.z};
+    const double bl = sqrt((b[0] * b[0] + b[1] * b[1]) + b[2] * b[2]);
+    if (!(bl > 0.0)) return pt::fail(PT_E_INVALID, "pt_view_look_at: the position is the target");
+    const double back[3] = {b[0] / bl, b[1] / bl, b[2] / bl};
+    const double u[3] = {(double)up.x, (double)up.y, (double)up.z};
+    const double r[3] = {u[1] * back[2] - u[2] * back[1], u[2] * back[0] - u[0] * back[2], u[0] * back[1] - u[1] * back[0]};
+    const double rl = sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
+    const double ul = sqrt((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]);
+    // (parallel: the cross product vanishes against |up|, to double rounding)
+    if (!(rl > 1e-12 * ul)) return pt::fail(PT_E_INVALID, "pt_view_look_at: up is parallel to the viewing direction (or zero)");
+    const double right[3] = {r[0] / rl, r[1] / rl, r[2] / rl};
+    const double up2[3] = {back[1] * right[2] - back[2] * right[1], back[2] * right[0] - back[0] * right[2],
+                           back[0] * right[1] - back[1] * right[0]};
+    for (int k = 0; k < 3; ++k) {
+        out->right[k] = (float)right[k];
+        out->up[k] = (float)up2[k];
+        out->back[k] = (float)back[k];
+    }
+    out->film_w = 1.0f;
+    out->film_h = 1.0f;
+    return PT_OK;
+}
+
+int pt_view_set_fov(pt_view* v, const pt_camera* cam, float vfov_deg, int width, int height)
+{
+    pt::clear_error();
+    if (!v || !cam) return pt::fail(PT_E_INVALID, "pt_view_set_fov: null argument");
+    if (!(vfov_deg > 0.0f && vfov_deg < 180.0f)) return pt::fail(PT_E_INVALID, "pt_view_set_fov: vfov %g outside (0, 180) degrees", (double)vfov_deg);
+    if (width <= 0 || height <= 0) return pt::fail(PT_E_INVALID, "pt_view_set_fov: image size %dx%d", width, height);
+    if (!(cam->dist_from_film > 0.0f) || !std::isfinite(cam->dist_from_film))
+        return pt::fail(PT_E_INVALID, "pt_view_set_fov: dist_from_film %g must be finite and > 0", (double)cam->dist_from_film);
+    const double half = ((double)vfov_deg * 3.14159265358979323846) / 360.0;
+    const double fh = (2.0 * (double)cam->dist_from_film) * tan(half);
+    const double fw = (fh * (double)width) / (double)height;
+    const float film_w = (float)fw, film_h = (float)fh;
+    if (!(film_w > 0.0f) || !(film_h > 0.0f) || !std::isfinite(film_w) || !std::isfinite(film_h))
+        return pt::fail(PT_E_INVALID, "pt_view_set_fov: film %g x %g is not finite and > 0", fw, fh);
+    v->film_w = film_w;
+    v->film_h = film_h;
+    return PT_OK;
+}
+
+// The arithmetic of pt.h, one rounded f32 operation at a time (this TU is compiled without contraction).
+void pt_camera_ray_view(const pt_camera* cam, const pt_view* view, uint32_t idx, int lens, float u1, float u2, pt_vec3* origin,
+                        pt_vec3* dir)
+{
+    if (!view) { pt_camera_ray(cam, idx, lens, u1, u2, origin, dir); return; }
+    uint32_t px, py;
+    pt_morton_i_to_pxl(idx, &px, &py);
+    pt_vec3 film = v3((static_cast<float>(px) / static_cast<float>(cam->pxl_width) - 0.5f) * view->film_w,
+                      (static_cast<float>(py) / static_cast<float>(cam->pxl_height) - 0.5f) * view->film_h, cam->dist_from_film);
+    pt_vec3 lo = v3(0.0f, 0.0f, 0.0f);
+    if (lens) {
+        float r = cam->radius * sqrtf(u1);
+        float theta = static_cast<float>(2 * 3.14159 * static_cast<double>(u2));
+        float sn, cs;
+        pt::sincos_det(theta, &sn, &cs);
+        lo = v3(r * cs, r * sn, 0.0f);
+    }
+    const float k = -cam->focal_length;
+    film = v3(film.x * k / cam->dist_from_film, film.y * k / cam->dist_from_film, film.z * k / cam->dist_from_film);
+    const pt_vec3 c = vsub(film, lo);
+    const float* R = view->right;
+    const float* U = view->up;
+    const float* B = view->back;
+    const pt_vec3 w = v3((R[0] * c.x + U[0] * c.y) + B[0] * c.z, (R[1] * c.x + U[1] * c.y) + B[1] * c.z,
+                         (R[2] * c.x + U[2] * c.y) + B[2] * c.z);
+    *dir = vunit(w);
+    if (lens)
+        *origin = v3((R[0] * lo.x + U[0] * lo.y) + cam->pos.x, (R[1] * lo.x + U[1] * lo.y) + cam->pos.y,
+                     (R[2] * lo.x + U[2] * lo.y) + cam->pos.z);
+    else
+        *origin = v3(0.0f + cam->pos.x, 0.0f + cam->pos.y, 0.0f + cam->pos.z);
 }
 
 // kernel.cu:771 -> color.h:59-62 normalized, color.h:68-71 gammaCorrect(c, 1/2.2), (int)(c*255)

@@ -10,6 +10,9 @@
  *                           via tinyobj::LoadObj (tiny_obj_loader.cc:638-884)
  *        pt_scene_build_bvh <- buildBVH (BVH.h:443-474) + depth guard (kernel.cu:627-631)
  *        pt_camera_ray / pt_morton_* <- camera.h:36-97
+ *        pt_view / pt_view_look_at / pt_view_set_fov / pt_camera_ray_view  (no counterpart) an oriented camera: a
+ *                           view places the pt_camera in the world (look-at, film extent); every entry point that
+ *                           takes a camera has a *_view twin, and a NULL view is the reference camera
  *        pt_write_ppm    <- kernel.cu:763-778 + color.h:59-71
  *   2. Render (hand-written gfx950 HIP kernels):
  *        pt_create       <- the uploads of kernel.cu:637-700 (scene, camera, BVH to device)
@@ -128,6 +131,52 @@ uint32_t pt_morton_pxl_to_i(uint32_t x, uint32_t y);
 void pt_morton_i_to_pxl(uint32_t idx, uint32_t* x, uint32_t* y);
 void pt_camera_ray(const pt_camera* cam, uint32_t idx, int lens, float u1, float u2,
                    pt_vec3* origin, pt_vec3* dir);
+
+/* ------------------------------------------------- the oriented camera (no counterpart in the reference)
+ * pt_camera mirrors the reference's struct: it looks down -z with +y up, and its film is the unit square whatever
+ * the image's shape (pxlToFilm, camera.h: no aspect correction).  A pt_view places that camera in the world: an
+ * orthonormal basis and the film's extent.  Every entry point that takes a camera has a *_view twin with
+ * `const pt_view* view` after `cam`; view = NULL is the reference camera, today's code and today's bits (the plain
+ * entry points are calls of their twins with NULL).
+ *
+ * The ray of pixel (px, py) of a W x H camera (W = pxl_width, H = pxl_height), all f32, every operation rounded on
+ * its own, no contraction, IEEE division and square root; `lens` as everywhere: radius != 0 or Morton index 0:
+ *   f   = ((float)px/(float)W - 0.5f) * film_w,  ((float)py/(float)H - 0.5f) * film_h,  dist
+ *   f   = (f * -focal) / dist
+ *   lo  = lens ? (r*cos(theta), r*sin(theta), 0) with r = radius*sqrt(u1), theta = (float)(2*3.14159*(double)u2),
+ *                as pt_camera_ray  :  (0, 0, 0)
+ *   c   = f - lo
+ *   w_k = (right[k]*c.x + up[k]*c.y) + back[k]*c.z           k = 0, 1, 2
+ *   d   = w / sqrt((w.x*w.x + w.y*w.y) + w.z*w.z)             (the normalisation pt_camera_ray uses)
+ *   o_k = lens ? (right[k]*lo.x + up[k]*lo.y) + pos[k]  :  (0 + pos[k])
+ * An identity view (right = +x, up = +y, back = +z, film 1 x 1) is NOT promised to equal the NULL view in the sign
+ * of a zero component: (-0)*1 + c.y*0 is +0 when c.y > 0, where the reference camera keeps -0.  Compare an oriented
+ * render against this arithmetic, never against the reference camera.
+ *
+ * A view is valid when all 11 floats are finite, film_w > 0 and film_h > 0, and, in double, each of |r.r - 1|,
+ * |u.u - 1|, |b.b - 1|, |r.u|, |r.b|, |u.b| is <= 1e-3 (a condition, not a measurement; left-handed bases -- mirrors
+ * -- are allowed).  Every entry point that takes a view returns PT_E_INVALID for an invalid one.
+ *
+ * Host helpers (no device; computed in double from the float inputs, rounded to float once at the end):
+ *   pt_view_look_at  back = (pos - target)/|pos - target|, right = cross(up, back)/|cross(up, back)|,
+ *                    up' = cross(back, right), film 1 x 1.  PT_E_INVALID: pos == target, up parallel to back (or
+ *                    zero: |cross(up, back)| <= 1e-12 |up|), a non-finite input, a null out.  pos (0,1,3), target (0,1,0), up (0,1,0) -- the
+ *                    reference camera's pose -- gives the identity.
+ *   pt_view_set_fov  film_h = 2*dist_from_film*tan(vfov/2), film_w = film_h*width/height (square pixels); the
+ *                    basis is left alone.  PT_E_INVALID: vfov_deg outside (0, 180), width or height <= 0, a
+ *                    dist_from_film that is not finite and > 0, a result that is not finite and > 0 as a float.
+ *   pt_view_validate the condition above (PT_OK or PT_E_INVALID with the reason in pt_last_error).
+ *   pt_camera_ray_view  the arithmetic above on the host, as pt_camera_ray is for the reference camera (which a
+ *                    NULL view gives); the view is not validated. */
+typedef struct {
+    float right[3], up[3], back[3];  /* world-space images of camera +x, +y, +z; the camera looks along -back */
+    float film_w, film_h;            /* film extent in the reference's film units; 1, 1 = the reference's unit square */
+} pt_view;                           /* 44 B, static_assert'ed */
+int pt_view_look_at(pt_vec3 pos, pt_vec3 target, pt_vec3 up, pt_view* out);
+int pt_view_set_fov(pt_view* v, const pt_camera* cam, float vfov_deg, int width, int height);
+int pt_view_validate(const pt_view* v);
+void pt_camera_ray_view(const pt_camera* cam, const pt_view* view /* NULL = pt_camera_ray */, uint32_t idx, int lens,
+                        float u1, float u2, pt_vec3* origin, pt_vec3* dir);
 
 /* kernel.cu:763-778: "P3 W H 255\n" then "%d %d %d " for rows y = 0..H-1 and x = W-1..0,
  * c = (int)(pow(c/(c+1), (float)(1/2.2)) * 255).  rgb is the scanline mean buffer written by
@@ -255,12 +304,17 @@ pt_ctx* pt_create(const pt_scene* scene, int device, int* err);
  * outside this shard are written as 0.  Blocking.  The image leaves the device through a pinned
  * staging buffer owned by the context (one DMA, then a parallel host copy into out_rgb). */
 int pt_render(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, float* out_rgb, pt_stats* stats);
+/* The same through an oriented camera (pt_view above; NULL = pt_render).  So for every *_view entry point below. */
+int pt_render_view(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, const pt_view* view, float* out_rgb,
+                   pt_stats* stats);
 
 /* Same into a DEVICE buffer d_out[W*H*3] on `stream` (a hipStream_t, NULL = default stream).
  * Only this shard's pixels are written; the caller zero-fills the buffer (a multi-GPU job
  * then sums the shards with one RCCL reduce).  Blocking (it waits for its own events). */
 int pt_render_device(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, float* d_out,
                      void* stream, pt_stats* stats);
+int pt_render_device_view(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, const pt_view* view, float* d_out,
+                          void* stream, pt_stats* stats);
 
 /* pt_render_device in two halves: _async enqueues the whole render on `stream` and returns at once (up
  * to 2 renders in flight per context, each with its own work buffers: two renders on two streams may run
@@ -269,6 +323,8 @@ int pt_render_device(pt_ctx* ctx, const pt_params* params, const pt_camera* cam,
  * idle gap between them (the bench's frame loop).  pt_render_device = _async + wait, and refuses to run
  * while renders are in flight, as do pt_trace* and pt_tri_counts. */
 int pt_render_device_async(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, float* d_out, void* stream);
+int pt_render_device_view_async(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, const pt_view* view,
+                                float* d_out, void* stream);
 int pt_render_wait(pt_ctx* ctx, pt_stats* stats);
 
 /* ------------------------------------------------- resumable accumulation (progressive rendering)
@@ -324,6 +380,11 @@ int pt_render_wait(pt_ctx* ctx, pt_stats* stats);
  * the header and the file's size; any out pointer may be NULL. */
 typedef struct pt_accum pt_accum;
 pt_accum* pt_accum_create(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, int* err);
+/* With an oriented camera: the accumulator keeps its view for life, as it keeps its camera.  pt_accum_view reads it
+ * back: *has_view = 1 and *out the view, or *has_view = 0 (either pointer may be NULL).  pt_accum_save refuses an
+ * accumulator with a view (PT_E_INVALID: format version 1's 32-byte camera has no room; pt_session_save holds it). */
+pt_accum* pt_accum_create_view(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, const pt_view* view, int* err);
+int pt_accum_view(const pt_accum* acc, pt_view* out, int* has_view);
 int pt_accum_add(pt_accum* acc, int32_t spp, float* d_out, void* stream, pt_stats* stats);
 int64_t pt_accum_samples(const pt_accum* acc);
 int pt_accum_read(pt_accum* acc, float* out_rgb, double* out_mean);
@@ -522,6 +583,18 @@ int pt_accum_add_adaptive(pt_accum* acc, pt_noise* noise, const pt_converge_para
  *                                                      else the count the pixel was frozen at
  *                C  PT_SESSION_NOISE             40 B  five f64: the estimator's prev r, g, b, mu, m2
  *                D  PT_SESSION_NOISE_PER_PIXEL    8 B  two uint32: W_q, b_q
+ * An accumulator with a view (pt_accum_create_view) is written as FORMAT VERSION 3, recognised by its version and
+ * header size together (no flag bit says so); one without a view is written as version 2, byte for byte as before:
+ *           8  uint32    format version (3)
+ *          12  uint32    header size in bytes (256)
+ *          16  ...       bytes 16..191 exactly version 2's fields
+ *         192  pt_view   44 B: right, up, back, film_w, film_h
+ *         236  20 bytes of zero
+ *         256  the sections, as above
+ * pt_session_load and pt_session_file_info read both versions; a stored view that is not valid (pt_view above), a
+ * non-zero byte in 236..255, version 3 with another header size than 256 and version 2 with another than 192 are
+ * PT_E_INVALID.  pt_session_file_view reads the view of a file (validated as pt_session_file_info validates the
+ * file): *has_view = 1 and *out the view for version 3, *has_view = 0 for version 2; either pointer may be NULL.
  * With no pixel ever frozen and no estimator (flags 0), section A is byte for byte the records pt_accum_save writes
  * for the same accumulator.
  *
@@ -580,6 +653,7 @@ typedef struct {
 int pt_session_save(pt_accum* acc, pt_noise* noise /* NULL: no estimator section */, const char* path);
 int pt_session_load(pt_ctx* ctx, const char* path, pt_accum** acc_out, pt_noise** noise_out /* may be NULL */, int* has_noise);
 int pt_session_file_info(const char* path, pt_session_info* info);
+int pt_session_file_view(const char* path, pt_view* out, int* has_view);
 
 /* ------------------------------------------------- the variance map of the image's mean
  * What the variance-guided denoiser (pt_denoise_guided, below) takes: per pixel q the estimated variance of the
@@ -704,6 +778,11 @@ void pt_denoise_defaults(pt_denoise_params* p);   /* {5, 5, 0.02f, 0.0f, 0} */
 
 int pt_render_features_device(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, pt_feature* d_feat, void* stream);
 int pt_render_features(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, pt_feature* feat /* host */);
+/* With a view the ray is pt_camera_ray_view(cam, view, ..., lens = 0, ...): the oriented pinhole ray. */
+int pt_render_features_view_device(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, const pt_view* view,
+                                   pt_feature* d_feat, void* stream);
+int pt_render_features_view(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, const pt_view* view,
+                            pt_feature* feat /* host */);
 int pt_denoise_device(pt_ctx* ctx, const pt_denoise_params* dp, int width, int height, int pixel_order,
                       const float* d_in, const pt_feature* d_feat, float* d_out, void* stream);
 int pt_denoise(pt_ctx* ctx, const pt_denoise_params* dp, int width, int height, int pixel_order,
@@ -773,10 +852,14 @@ typedef struct pt_group pt_group;
 pt_group* pt_group_create(pt_ctx* const* ctxs, int n, int* err);
 int pt_group_size(const pt_group* group);
 int pt_render_group(pt_group* group, const pt_params* params, const pt_camera* cam, float* out_rgb, pt_stats* stats);
+int pt_render_group_view(pt_group* group, const pt_params* params, const pt_camera* cam, const pt_view* view,
+                         float* out_rgb, pt_stats* stats);
 void pt_group_destroy(pt_group* group);
 /* create + render + destroy */
 int pt_render_multi(pt_ctx* const* ctxs, int n, const pt_params* params, const pt_camera* cam, float* out_rgb,
                     pt_stats* stats);
+int pt_render_multi_view(pt_ctx* const* ctxs, int n, const pt_params* params, const pt_camera* cam, const pt_view* view,
+                         float* out_rgb, pt_stats* stats);
 
 void pt_destroy(pt_ctx* ctx);
 const char* pt_last_error(void);

@@ -1,0 +1,220 @@
+"""Reference for the oriented camera (pt_view, include/pt/pt.h): the ray arithmetic restated in numpy float32, one
+rounded operation per line, and the oracle's per-pixel render loop (or_render, oracle/pt_oracle.c) restated around
+it -- the oracle library itself knows nothing of views; only its RNG, its sin/cos and its two integrators are called.
+
+TEST INFRASTRUCTURE ONLY.
+"""
+import ctypes as C
+import functools
+
+import numpy as np
+
+import oracle
+
+F = np.float32
+
+# the views the tests share: (right, up, back, film)
+IDENTITY = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1))
+# an exact 90-degree yaw about +y: the camera looks along -x (back = +x); axis swap with a sign flip, many exact zeros
+YAW90 = ((0, 0, -1), (0, 1, 0), (1, 0, 0), (1, 1))
+# the identity with +x mirrored: a left-handed basis
+MIRROR = ((-1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1))
+
+
+def look_at64(pos, target, up):
+    """pt_view_look_at restated in float64 from the float32 inputs: (right, up', back) as float32 triples."""
+    p = np.asarray(pos, dtype=F).astype(np.float64)
+    t = np.asarray(target, dtype=F).astype(np.float64)
+    u = np.asarray(up, dtype=F).astype(np.float64)
+    b = p - t
+    bl = np.sqrt((b[0] * b[0] + b[1] * b[1]) + b[2] * b[2])
+    back = b / bl
+    r = np.array([u[1] * back[2] - u[2] * back[1], u[2] * back[0] - u[0] * back[2], u[0] * back[1] - u[1] * back[0]])
+    rl = np.sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2])
+    right = r / rl
+    up2 = np.array([back[1] * right[2] - back[2] * right[1], back[2] * right[0] - back[0] * right[2],
+                    back[0] * right[1] - back[1] * right[0]])
+    return right.astype(F), up2.astype(F), back.astype(F)
+
+
+def generic(pos=(0.0, 1.0, 3.0)):
+    """A generic look-at view from `pos`: no component of the basis is 0 or 1."""
+    r, u, b = look_at64(pos, (0.3, 0.7, -0.2), (0.1, 1.0, 0.05))
+    return (tuple(float(v) for v in r), tuple(float(v) for v in u), tuple(float(v) for v in b), (1, 1))
+
+
+def with_film(view, film):
+    return (view[0], view[1], view[2], tuple(film))
+
+
+def _sincos(theta):
+    s, c = np.empty(theta.shape, dtype=F), np.empty(theta.shape, dtype=F)
+    so, co = C.c_float(), C.c_float()
+    f = oracle.lib().or_sincos
+    for i, t in enumerate(theta):
+        f(float(t), C.byref(so), C.byref(co))
+        s[i], c[i] = so.value, co.value
+    return s, c
+
+
+def rays(cam, view, px, py, lens, u1=None, u2=None):
+    """(origins, directions), float32 (n, 3): the rays of pixels (px[i], py[i]) of `cam` = (pos, dist, focal, radius,
+    W, H) through `view` = (right, up, back, (film_w, film_h)).  lens: one flag for all; u1, u2 the lens draws."""
+    pos, dist, focal, radius, W, H = cam
+    pos = np.asarray(pos, dtype=F)
+    dist, focal, radius = F(dist), F(focal), F(radius)
+    R, U, B = (np.asarray(v, dtype=F) for v in view[:3])
+    film_w, film_h = F(view[3][0]), F(view[3][1])
+    px = np.asarray(px, dtype=np.uint32).reshape(-1)
+    py = np.asarray(py, dtype=np.uint32).reshape(-1)
+    n = len(px)
+    fx = px.astype(F) / F(W)
+    fx = fx - F(0.5)
+    fx = fx * film_w
+    fy = py.astype(F) / F(H)
+    fy = fy - F(0.5)
+    fy = fy * film_h
+    fz = np.full(n, dist, dtype=F)
+    nf = -focal
+    fx = fx * nf
+    fx = fx / dist
+    fy = fy * nf
+    fy = fy / dist
+    fz = fz * nf
+    fz = fz / dist
+    lox = np.zeros(n, dtype=F)
+    loy = np.zeros(n, dtype=F)
+    loz = np.zeros(n, dtype=F)
+    if lens:
+        u1 = np.asarray(u1, dtype=F).reshape(-1)
+        u2 = np.asarray(u2, dtype=F).reshape(-1)
+        r = radius * np.sqrt(u1)
+        theta = ((2 * 3.14159) * u2.astype(np.float64)).astype(F)
+        s, c = _sincos(theta)
+        lox = r * c
+        loy = r * s
+    cx = fx - lox
+    cy = fy - loy
+    cz = fz - loz
+    w = np.empty((n, 3), dtype=F)
+    for k in range(3):
+        a = R[k] * cx
+        b = U[k] * cy
+        a = a + b
+        b = B[k] * cz
+        w[:, k] = a + b
+    l2 = w[:, 0] * w[:, 0]
+    t = w[:, 1] * w[:, 1]
+    l2 = l2 + t
+    t = w[:, 2] * w[:, 2]
+    l2 = l2 + t
+    ln = np.sqrt(l2)
+    d = np.empty((n, 3), dtype=F)
+    o = np.empty((n, 3), dtype=F)
+    for k in range(3):
+        d[:, k] = w[:, k] / ln
+        if lens:
+            a = R[k] * lox
+            b = U[k] * loy
+            a = a + b
+            o[:, k] = a + pos[k]
+        else:
+            o[:, k] = F(0.0) + pos[k]
+    assert o.dtype == F and d.dtype == F
+    return o, d
+
+
+def morton(x, y):
+    r = 0
+    for b in range(16):
+        r |= ((x >> b) & 1) << (2 * b)
+        r |= ((y >> b) & 1) << (2 * b + 1)
+    return r
+
+
+def morton_xy(idx):
+    x = y = 0
+    for b in range(16):
+        x |= ((idx >> (2 * b)) & 1) << b
+        y |= ((idx >> (2 * b + 1)) & 1) << b
+    return x, y
+
+
+_signed = False
+
+
+def _integrators():
+    """The oracle's two integrators with their ctypes signatures (oracle.py sets none for them)."""
+    global _signed
+    h = oracle.lib()
+    if not _signed:
+        h.or_radiance_unidir.argtypes = [C.POINTER(oracle.OScene), oracle.OVec3, oracle.OVec3, C.c_int,
+                                         C.POINTER(oracle.OXorwow), C.POINTER(C.c_double * 3), C.POINTER(oracle.OCounters)]
+        h.or_radiance_unidir.restype = None
+        h.or_radiance_head.argtypes = [C.POINTER(oracle.OScene), oracle.OVec3, oracle.OVec3, C.POINTER(oracle.OXorwow),
+                                       C.POINTER(C.c_double * 3), C.POINTER(oracle.OCounters)]
+        h.or_radiance_head.restype = None
+        _signed = True
+    return h
+
+
+def render(osc, cam, view, spp, bounces=3, integrator=0, seed=1234, pixels=None, counts=None):
+    """or_render's per-pixel loop with the oriented ray: the f64 mean image (H, W, 3).  pixels: iterable of y*W + x
+    (default: all; the others stay 0).  counts: (H, W) per-pixel sample counts instead of spp."""
+    h = _integrators()
+    pos, dist, focal, radius, W, H = cam
+    out = np.zeros((H, W, 3), dtype=np.float64)
+    if pixels is None:
+        pixels = range(W * H)
+    rng = oracle.OXorwow()
+    cnt = oracle.OCounters()
+    L = (C.c_double * 3)()
+    for pix in pixels:
+        px, py = int(pix) % W, int(pix) // W
+        idx = morton(px, py)
+        h.or_xorwow_init(seed, idx, C.byref(rng))
+        lens = idx == 0 or float(F(radius)) != 0.0
+        nspp = spp if counts is None else int(counts[py, px])
+        if not lens:
+            o, d = rays(cam, view, [px], [py], False)
+        mean = [0.0, 0.0, 0.0]
+        for n in range(1, nspp + 1):
+            if lens:
+                u1 = h.or_uniform(C.byref(rng))
+                u2 = h.or_uniform(C.byref(rng))
+                o, d = rays(cam, view, [px], [py], True, [u1], [u2])
+            ov = oracle.OVec3(float(o[0, 0]), float(o[0, 1]), float(o[0, 2]))
+            dv = oracle.OVec3(float(d[0, 0]), float(d[0, 1]), float(d[0, 2]))
+            if integrator == 1:
+                h.or_radiance_head(C.byref(osc.c), ov, dv, C.byref(rng), C.byref(L), C.byref(cnt))
+            else:
+                h.or_radiance_unidir(C.byref(osc.c), ov, dv, int(bounces), C.byref(rng), C.byref(L), C.byref(cnt))
+            fn1, fn = float(F(n - 1)), float(F(n))
+            for ch in range(3):
+                mean[ch] = (mean[ch] * fn1) / fn + L[ch] / fn
+        out[py, px] = mean
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _cached(scene_key, cam, view, spp, bounces, integrator, seed):
+    return render(_scenes[scene_key], cam, view, spp, bounces, integrator, seed)
+
+
+_scenes = {}
+
+
+def render_cached(scene_key, osc, cam, view, spp, bounces=3, integrator=0, seed=1234):
+    """render() of the whole image, computed once per distinct argument set and shared (treat it as read-only)."""
+    _scenes[scene_key] = osc
+    img = _cached(scene_key, cam, view, spp, bounces, integrator, seed)
+    img.setflags(write=False)
+    return img
+
+
+def same_bits(a, b):
+    a = np.ascontiguousarray(a)
+    b = np.ascontiguousarray(b)
+    assert a.dtype == b.dtype and a.shape == b.shape, (a.dtype, b.dtype, a.shape, b.shape)
+    u = {4: np.uint32, 8: np.uint64}[a.dtype.itemsize]
+    return int(np.count_nonzero(a.view(u) != b.view(u)))
