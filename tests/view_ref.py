@@ -47,6 +47,67 @@ def with_film(view, film):
     return (view[0], view[1], view[2], tuple(film))
 
 
+def fov_film(dist_from_film, vfov_deg, width, height):
+    """pt_view_set_fov restated in float64 from the float32 inputs: the film (w, h) of a vertical field of view with
+    square pixels, each rounded to float32 once."""
+    half = (float(F(vfov_deg)) * 3.14159265358979323846) / 360.0
+    fh = (2.0 * float(F(dist_from_film))) * np.tan(half)
+    fw = (fh * float(width)) / float(height)
+    return (float(F(fw)), float(F(fh)))
+
+
+def _scaled(v, s):
+    return tuple(float(F(F(c) * F(s))) for c in v)
+
+
+def _negated(v):
+    return tuple(-float(c) for c in v)
+
+
+def _extra_shots():
+    pos = (0.0, 1.0, 3.0)                      # the reference camera's position: in front of the box's open side
+    inside = (0.6, 1.0, 0.3)                   # inside the box
+    g = generic(pos)
+    # the basis' squared lengths 9e-4 off 1, one above and one below: pt_view_validate's terms right.right - 1 and
+    # up.up - 1 at nine tenths of its limit of 1e-3
+    slack = (_scaled(g[0], np.sqrt(1.0 + 9e-4)), _scaled(g[1], np.sqrt(1.0 - 9e-4)), g[2], (1, 1))
+    return {
+        # the reference pose with +x mirrored: a left-handed basis
+        "mirror": (pos, 1.0, 3.0, MIRROR),
+        # a 90-degree roll about the viewing axis: right = +y, up = -x, back = +z
+        "roll90": (pos, 1.0, 3.0, ((0, 1, 0), (-1, 0, 0), (0, 0, 1), (1, 1))),
+        # under the box's ceiling, looking straight down -y (back = +y) with the roll of the x axis: many exact zeros
+        "down": ((0.0, 1.9, 0.0), 1.0, 3.0, ((1, 0, 0), (0, 0, -1), (0, 1, 0), (1, 1))),
+        # generic turned round (back negated, and right for handedness): it looks away from the scene, every ray misses
+        "away": (pos, 1.0, 3.0, (_negated(g[0]), g[1], _negated(g[2]), (1, 1))),
+        "slack": (pos, 1.0, 3.0, slack),
+        # a very wide film: grazing directions with tiny components (from inside the box, where such rays still meet a
+        # wall: from the reference position all but the centre pixels would miss); a very narrow one: all pixels nearly
+        # one direction
+        "wide": (inside, 1.0, 3.0, with_film(generic(inside), (64, 48))),
+        "narrow": (pos, 1.0, 3.0, with_film(g, (2.0 ** -6, 2.0 ** -6))),
+        # pt.look_at(..., vfov=35, cam=cam) of a 24 x 16 (or any 3:2) camera
+        "fov": (pos, 1.0, 3.0, with_film(g, fov_film(1.0, 35.0, 24, 16))),
+    }
+
+
+# named shots (pos, dist_from_film, focal_length, view), usable with any scene that fits in about [-2, 2]^3
+SHOTS_EXTRA = _extra_shots()
+
+
+def far_pose(m):
+    """(pos, dist_from_film, focal_length, view) of an oblique camera whose largest coordinate is -x = -m, looking at
+    (0, 1, 0), with the field of view narrowed so that a box of extent 2 fills the frame (focal_length = the distance,
+    dist_from_film a third of it, as the far cameras of test_gpu_ray_ranges.py)."""
+    m = float(F(m))
+    pos = tuple(float(F(c)) for c in (-m, 0.5 * m + 1.0, 0.25 * m))
+    target = (0.0, 1.0, 0.0)
+    focal = float(np.sqrt(sum((p - t) ** 2 for p, t in zip(pos, target))))
+    r, u, b = look_at64(pos, target, (0.1, 1.0, 0.05))
+    view = (tuple(float(v) for v in r), tuple(float(v) for v in u), tuple(float(v) for v in b), (1, 1))
+    return pos, float(F(focal / 3.0)), float(F(focal)), view
+
+
 def _sincos(theta):
     s, c = np.empty(theta.shape, dtype=F), np.empty(theta.shape, dtype=F)
     so, co = C.c_float(), C.c_float()
@@ -158,9 +219,12 @@ def _integrators():
     return h
 
 
-def render(osc, cam, view, spp, bounces=3, integrator=0, seed=1234, pixels=None, counts=None):
+def render(osc, cam, view, spp, bounces=3, integrator=0, seed=1234, pixels=None, counts=None, tri_counts=None,
+           return_counters=False):
     """or_render's per-pixel loop with the oriented ray: the f64 mean image (H, W, 3).  pixels: iterable of y*W + x
-    (default: all; the others stay 0).  counts: (H, W) per-pixel sample counts instead of spp."""
+    (default: all; the others stay 0).  counts: (H, W) per-pixel sample counts instead of spp.  tri_counts: optional
+    uint32[num_tris] array the integrators add their per-triangle test counts to (OCounters.tri_counts, as
+    oracle.render).  return_counters: return (image, dict(traces, node_tests, tri_tests)) instead."""
     h = _integrators()
     pos, dist, focal, radius, W, H = cam
     out = np.zeros((H, W, 3), dtype=np.float64)
@@ -168,6 +232,9 @@ def render(osc, cam, view, spp, bounces=3, integrator=0, seed=1234, pixels=None,
         pixels = range(W * H)
     rng = oracle.OXorwow()
     cnt = oracle.OCounters()
+    if tri_counts is not None:
+        assert tri_counts.dtype == np.uint32 and tri_counts.flags.c_contiguous and len(tri_counts) == osc.c.num_tris
+        cnt.tri_counts = tri_counts.ctypes.data
     L = (C.c_double * 3)()
     for pix in pixels:
         px, py = int(pix) % W, int(pix) // W
@@ -193,23 +260,26 @@ def render(osc, cam, view, spp, bounces=3, integrator=0, seed=1234, pixels=None,
             for ch in range(3):
                 mean[ch] = (mean[ch] * fn1) / fn + L[ch] / fn
         out[py, px] = mean
+    if return_counters:
+        return out, dict(traces=int(cnt.traces), node_tests=int(cnt.node_tests), tri_tests=int(cnt.tri_tests))
     return out
 
 
 @functools.lru_cache(maxsize=None)
 def _cached(scene_key, cam, view, spp, bounces, integrator, seed):
-    return render(_scenes[scene_key], cam, view, spp, bounces, integrator, seed)
+    return render(_scenes[scene_key], cam, view, spp, bounces, integrator, seed, return_counters=True)
 
 
 _scenes = {}
 
 
-def render_cached(scene_key, osc, cam, view, spp, bounces=3, integrator=0, seed=1234):
-    """render() of the whole image, computed once per distinct argument set and shared (treat it as read-only)."""
+def render_cached(scene_key, osc, cam, view, spp, bounces=3, integrator=0, seed=1234, return_counters=False):
+    """render() of the whole image, computed once per distinct argument set and shared (treat it as read-only).
+    return_counters: (image, a copy of the oracle's counters) instead."""
     _scenes[scene_key] = osc
-    img = _cached(scene_key, cam, view, spp, bounces, integrator, seed)
+    img, cnt = _cached(scene_key, cam, view, spp, bounces, integrator, seed)
     img.setflags(write=False)
-    return img
+    return (img, dict(cnt)) if return_counters else img
 
 
 def same_bits(a, b):
