@@ -14,7 +14,8 @@
 //                              t % shard_count.
 //   unit set-up                init_pixel_states, init_active_states, seed_table, build_jump_byte_tables,
 //                              finalize_pixels: the wavefront kernels' work units and RNG tables
-//   wavefront shading          the walk and the shading passes of integrator 0, then of integrator 1
+//   wavefront shading          what the two shading passes share (unit dealing, winner check, hit bookkeeping,
+//                              stream store-back, whole-pixel end), then the passes of integrator 0 and integrator 1
 //   wf_main, kernel instances  render_unidir_wf, render_head_wf and their accumulating twins
 //   output / trace / features  tonemap_codes, trace_rays, primary_features
 #include <hip/hip_runtime.h>
@@ -333,28 +334,37 @@ __device__ __forceinline__ C3 mat_albedo(const DMat* m) { return c3(m->albedo[0]
 __device__ __forceinline__ C3 mat_emission(const DMat* m) { return c3(m->emission[0], m->emission[1], m->emission[2]); }
 __device__ __forceinline__ C3 brdf(const DMat* m) { return cmulf(mat_albedo(m), (float)(1 / 3.14159)); }  // kernel.cu:101-104
 
-// Area-CDF pick over the emissive triangles + uniform point (kernel.cu:466-495 / 231-262).
-// The scan stops once randArea <= 0: no later light can then satisfy randArea > 0 (areas are
-// >= 0), so the selection is unchanged.
-__device__ __forceinline__ int32_t pick_light(const Args& a, Rng& rng, V3* p)
+// Area-CDF pick over the light records lt[0..num_lights) (global, or staged in LDS), ra = total area * u
+// (kernel.cu:466-495 / 231-262); num_lights is the slot of triangle 0 (nothing picked).  The scan stops once
+// randArea <= 0: no later light can then satisfy randArea > 0 (areas are >= 0), so the selection is unchanged.
+__device__ __forceinline__ uint32_t light_scan(const DLight* lt, uint32_t num_lights, float ra)
 {
-    float ra = a.total_light_area * rng_uniform(rng);
-    uint32_t sel = a.num_lights;   // slot of triangle 0 (nothing picked)
-    for (uint32_t j = 0; j < a.num_lights && ra > 0; ++j) {
-        const float area = a.lights[j].area;
+    uint32_t sel = num_lights;
+    for (uint32_t j = 0; j < num_lights && ra > 0; ++j) {
+        const float area = lt[j].area;
         if (ra < area && ra > 0) sel = j;
         ra -= area;
     }
+    return sel;
+}
+// uniform point of a sphere light (d8): z = 1 - 2u, phi = 2*3.14159*v
+__device__ __forceinline__ V3 light_point_sphere(const DLight& L, float u, float v)
+{
+    const float z = 1.0f - 2.0f * u;
+    const float rxy = sqrtf(__builtin_fmaxf(0.0f, 1.0f - z * z));
+    const float phi = (float)(2 * 3.14159 * (double)v);
+    float si, co;
+    det_sincos(phi, &si, &co);
+    return v3(L.v0[0], L.v0[1], L.v0[2]) + v3(rxy * co, rxy * si, z) * L.a1[0];
+}
+__device__ __forceinline__ int32_t pick_light(const Args& a, Rng& rng, V3* p)
+{
+    const uint32_t sel = light_scan(a.lights, a.num_lights, a.total_light_area * rng_uniform(rng));
     float u = rng_uniform(rng);
     float v = rng_uniform(rng);
     const DLight& L = a.lights[sel];
-    if (L.pad != 0.0f) {   // sphere light (d8): uniform point, z = 1 - 2u, phi = 2*3.14159*v
-        const float z = 1.0f - 2.0f * u;
-        const float rxy = sqrtf(__builtin_fmaxf(0.0f, 1.0f - z * z));
-        const float phi = (float)(2 * 3.14159 * (double)v);
-        float si, co;
-        det_sincos(phi, &si, &co);
-        *p = v3(L.v0[0], L.v0[1], L.v0[2]) + v3(rxy * co, rxy * si, z) * L.a1[0];
+    if (L.pad != 0.0f) {
+        *p = light_point_sphere(L, u, v);
         return L.tri;
     }
     const V3 v0 = v3(L.v0[0], L.v0[1], L.v0[2]);
@@ -870,6 +880,16 @@ __device__ __forceinline__ void slot_stream(const Args& a, uint32_t q, uint32_t 
     }
 }
 
+// The direction of pixel (px, py)'s pinhole ray, stored with its units (a lens pixel: 0, its rays are formed per sample).
+__device__ __forceinline__ V3 pinhole_dir(const Args& a, uint32_t px, uint32_t py, bool lens)
+{
+    V3 o, d = v3(0.0f, 0.0f, 0.0f);
+    if (!lens) {
+        if (a.oriented) camera_ray_view(a, px, py, false, 0.0f, 0.0f, &o, &d);
+        else camera_ray(a.cam, px, py, false, 0.0f, 0.0f, &o, &d);
+    }
+    return d;
+}
 // This render's counters, unit counters and wall-clock minima, by the first block of the unit set-up kernel
 // (no memset launches).
 __device__ __forceinline__ void reset_render_counters(const Args& a)
@@ -920,11 +940,7 @@ __global__ __launch_bounds__(256) void init_pixel_states(Args a, uint32_t* __res
     const uint32_t n_done = a.accum ? a.acc_n0 : 0u;   // samples the pixel has before this render
     slot_stream(a, q, idx, n_done, r);
     const bool lens = (idx == 0) || (a.cam.radius != 0.0f);
-    V3 o, d = v3(0.0f, 0.0f, 0.0f);
-    if (!lens) {   // the pixel's pinhole ray
-        if (a.oriented) camera_ray_view(a, px, py, false, 0.0f, 0.0f, &o, &d);
-        else camera_ray(a.cam, px, py, false, 0.0f, 0.0f, &o, &d);
-    }
+    const V3 d = pinhole_dir(a, px, py, lens);
     uint32_t done = 0;
     for (uint32_t c = 0; c < nc; ++c) {
         const uint32_t s0 = split ? chunk_first(a, c, nc) : 0u;
@@ -972,11 +988,7 @@ __global__ __launch_bounds__(256) void init_active_states(Args a, uint32_t* __re
     Rng r;
     slot_stream(a, q, idx, a.acc_n0, r);
     const bool lens = (idx == 0) || (a.cam.radius != 0.0f);
-    V3 o, d = v3(0.0f, 0.0f, 0.0f);
-    if (!lens) {   // the pixel's pinhole ray
-        if (a.oriented) camera_ray_view(a, px, py, false, 0.0f, 0.0f, &o, &d);
-        else camera_ray(a.cam, px, py, false, 0.0f, 0.0f, &o, &d);
-    }
+    const V3 d = pinhole_dir(a, px, py, lens);
     st[u] = r.v0;
     st[N + u] = r.v1;
     st[2 * N + u] = r.v2;
@@ -1020,6 +1032,21 @@ __global__ __launch_bounds__(256) void build_jump_byte_tables(const uint32_t* __
     e[5] = 0u; e[6] = 0u; e[7] = 0u;
 }
 
+// The running mean of kernel.cu:551-552 after sample n of radiance l: m * (n-1) / n + l / n, every operation rounded
+// on its own.  The six quotients by fn as one IEEE reciprocal + Markstein corrections (RN(x/fn) for finite x clear
+// of under/overflow) -- else the whole wave divides.
+__device__ __forceinline__ C3 mean_step(int n, double m0, double m1, double m2, C3 l)
+{
+    const double fn1 = (double)(float)(n - 1), fn = (double)(float)n;
+    const double x0 = m0 * fn1, x1 = m1 * fn1, x2 = m2 * fn1;
+    if (__ballot(!(quot_ok(x0) && quot_ok(x1) && quot_ok(x2) && quot_ok(l.r) && quot_ok(l.g) && quot_ok(l.b))) == 0ull) {
+        const double rf = 1.0 / fn;
+        return c3(div_mk_d(x0, fn, rf) + div_mk_d(l.r, fn, rf), div_mk_d(x1, fn, rf) + div_mk_d(l.g, fn, rf),
+                  div_mk_d(x2, fn, rf) + div_mk_d(l.b, fn, rf));
+    }
+    return c3(x0 / fn + l.r / fn, x1 / fn + l.g / fn, x2 / fn + l.b / fn);
+}
+
 // Split slots: the running mean of kernel.cu:551-552, in sample order, over the stored
 // per-sample radiance of each split pixel of this shard.
 __global__ __launch_bounds__(256) void finalize_pixels(Args a)
@@ -1042,22 +1069,9 @@ __global__ __launch_bounds__(256) void finalize_pixels(Args a)
     if (e0 != 0u) { m0 = L[0]; m1 = L[1]; m2 = L[2]; }
     else if (am) { m0 = am[0]; m1 = am[a.npix]; m2 = am[2 * (size_t)a.npix]; }
     L += (size_t)e0 * stride;
-    // one sample: the six quotients by fn as one IEEE reciprocal + Markstein corrections (RN(x/fn)
-    // for finite x clear of under/overflow, as in the render kernel's sample end) -- else the wave
-    // divides
     auto step = [&](int n, double l0, double l1, double l2) {
-        const double fn1 = (double)(float)(n - 1), fn = (double)(float)n;
-        const double x0 = m0 * fn1, x1 = m1 * fn1, x2 = m2 * fn1;
-        if (__ballot(!(quot_ok(x0) && quot_ok(x1) && quot_ok(x2) && quot_ok(l0) && quot_ok(l1) && quot_ok(l2))) == 0ull) {
-            const double rf = 1.0 / fn;
-            m0 = div_mk_d(x0, fn, rf) + div_mk_d(l0, fn, rf);
-            m1 = div_mk_d(x1, fn, rf) + div_mk_d(l1, fn, rf);
-            m2 = div_mk_d(x2, fn, rf) + div_mk_d(l2, fn, rf);
-        } else {
-            m0 = x0 / fn + l0 / fn;
-            m1 = x1 / fn + l1 / fn;
-            m2 = x2 / fn + l2 / fn;
-        }
+        const C3 m = mean_step(n, m0, m1, m2, c3(l0, l1, l2));
+        m0 = m.r; m1 = m.g; m2 = m.b;
     };
     // eight samples' loads issued together, the next eight issued before these are consumed (a wave's
     // loads of one sample are 64 consecutive slots: whole lines)
@@ -1146,6 +1160,127 @@ __device__ __forceinline__ const Args& kernel_args_opaque()
     return *(const Args*)p;
 }
 
+// ------------------------------------------------------------------ shared by the two shading passes
+// The refill's unit dealing: lanes `idle` of the wave take the next units of this shard from the unit
+// counters; returns this lane's unit (`me`: this lane is idle), a.nunits once every counter is exhausted.
+// With unit_queues > 1 the units are dealt from kQueues counters (one 128-B line each), counter x owning the
+// blocks j = x (mod kQueues) of kQueueBlock units in order -- so the unit sequence is still taken roughly front
+// to back -- each wave starting at its block's counter and moving on when that one is exhausted (the block's LDS
+// mask, so every wave of the block and every lane sees the same): the refill's atomics spread over kQueues
+// addresses.  Which units a lane gets never changes what it computes.
+// Counting variant: a lane that finds the queue drained leaves its end's ticks after the drain and since the
+// kernel's start in done_rel (binned at the kernel's end).
+template <bool kCount>
+__device__ __forceinline__ uint32_t take_unit(const Args& a, int lane, uint64_t idle, bool me, const uint32_t* lprobe,
+                                              uint32_t* done_rel)
+{
+    uint32_t u = kNoUnit;
+    if (a.unit_queues > 1u) {
+        uint32_t qdone = *reinterpret_cast<volatile const uint32_t*>(lprobe + 1);
+        const uint32_t x0 = blockIdx.x & (kQueues - 1u);
+        for (uint32_t r = 0; r < kQueues && idle && qdone != (1u << kQueues) - 1u; ++r) {
+            const uint32_t x = (x0 + r) & (kQueues - 1u);
+            if (qdone & (1u << x)) continue;
+            const int leader = __ffsll((long long)idle) - 1;
+            uint32_t base = 0;
+            if (lane == leader) base = atomicAdd(a.pixel_counter + kQueueStride * (x + 1u), (uint32_t)__popcll(idle));
+            base = __shfl(base, leader, 64);
+            if (me && u == kNoUnit) {
+                const uint32_t k = base + (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
+                const uint64_t uq = ((uint64_t)(k / kQueueBlock) * kQueues + x) * kQueueBlock + (k % kQueueBlock);
+                if (uq < a.nunits) u = (uint32_t)uq;
+            }
+            const uint64_t left = __ballot(me && u == kNoUnit);
+            if (left) {   // (a counter only grows: past its class's end for good)
+                qdone |= 1u << x;
+                if (lane == leader) atomicOr(const_cast<uint32_t*>(lprobe + 1), 1u << x);
+            }
+            idle = left;
+        }
+        if (me && u == kNoUnit) u = a.nunits;   // every counter exhausted
+    } else {
+        const uint32_t need = (uint32_t)__popcll(idle);
+        const int leader = __ffsll((long long)idle) - 1;
+        uint32_t base = 0;
+        if (lane == leader) base = atomicAdd(a.pixel_counter, need);
+        base = __shfl(base, leader, 64);
+        if (me) u = base + (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
+    }
+    if (kCount && me && u >= a.nunits) {
+        const unsigned long long now = wall_clock64();
+        atomicMin(a.counters + CNT_T_DRAINED, now);
+        const unsigned long long d0 = __hip_atomic_load(a.counters + CNT_T_DRAINED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned long long s0 = __hip_atomic_load(a.counters + CNT_T_START, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        done_rel[0] = (uint32_t)min(now - min(now, d0), 0xffffffffull);
+        done_rel[1] = (uint32_t)min(now - min(now, s0), 0xffffffffull);
+    }
+    return u;
+}
+
+// The winner check of a finished walk (ST_CHECK; htri: the winner's render-path slot): the winner must be a
+// triangle the reference tests (DESIGN.md "Traversal"); if not (rare), the exact reference-BVH walk redoes the
+// ray (false: ST_SLOW).  htri becomes the triangle's id.
+__device__ __forceinline__ bool check_winner(const Args& a, int32_t& htri, const V3& ro, const V3& rd)
+{
+    const float4* hr = a.hrec + 3 * (size_t)(uint32_t)htri;
+    const float4 b0 = hr[0], b1 = hr[1];
+    htri = (int32_t)__float_as_uint(b1.w);
+    return ref_tested_box(b0, b1, __float_as_uint(b1.z), ro, rd, a.rnodes, a.rparent);
+}
+
+// A hit is at hand (after a walk, the slow walk or the memo): the spheres unless it is a memo, then the primary
+// memo's bookkeeping -- a unit's first primary hit goes to the record (words memo_w, memo_w + 1) and, from the
+// pixel's owner, to pmemo[the slot in word slot_w] for the pixel's other chunks.
+__device__ __forceinline__ void take_hit(const Args& a, const ColdRec& R, int memo_w, int slot_w, uint32_t& fl, V3 ro,
+                                         V3 rd, int32_t& htri, float& ht)
+{
+    if (a.num_spheres && !(fl & CF_MEMO)) apply_spheres(a, ro, rd, &htri, &ht);
+    fl &= ~CF_MEMO;
+    if (fl & CF_PRIMARY) {
+        fl = (fl | CF_HAVE) & ~CF_PRIMARY;
+        R.st2(memo_w, (uint32_t)htri, __float_as_uint(ht));
+        if (fl & CF_OWNER) {
+            const uint32_t q = R.ld(slot_w);
+            // (one relaxed 64-bit store: no release, i.e. no write-back of this XCD's L2)
+            __hip_atomic_store(reinterpret_cast<uint64_t*>(a.pmemo) + q,
+                               ((uint64_t)__float_as_uint(ht) << 32) | (uint32_t)(htri + 2), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+            fl &= ~CF_OWNER;
+        }
+    }
+}
+
+// An accumulating pass: the XORWOW state after a pixel's last sample of the pass, to its slot's row ar of acc_rng
+// (word k at stride P = npix).
+__device__ __forceinline__ void store_stream(size_t P, uint32_t* ar, uint32_t v0, uint32_t v1, uint32_t v2,
+                                             uint32_t v3, uint32_t v4, uint32_t d)
+{
+    ar[0] = v0; ar[P] = v1; ar[2 * P] = v2; ar[3 * P] = v3; ar[4 * P] = v4;
+    ar[5 * P] = d;
+}
+
+// A whole pixel's unit ends: an accumulating pass keeps the slot's mean and stream for the next pass; the pixel's
+// floats go to the image (an accumulating pass: when it has one).
+template <bool kAccum>
+__device__ __forceinline__ void finish_pixel(const Args& a, uint32_t slot, uint32_t px, uint32_t py, double m0, double m1,
+                                             double m2, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, uint32_t v4,
+                                             uint32_t d)
+{
+    if (kAccum) {
+        const size_t P = a.npix;
+        double* am = a.acc_mean + slot;
+        am[0] = m0; am[P] = m1; am[2 * P] = m2;
+        store_stream(P, a.acc_rng + slot, v0, v1, v2, v3, v4, d);
+    }
+    if (!kAccum || a.out) {
+        float* o3 = a.out + out_pixel(a, px, py) * 3;
+        o3[0] = (float)m0;
+        o3[1] = (float)m1;
+        o3[2] = (float)m2;
+    }
+}
+
+// ------------------------------------------------------------------ wavefront kernel, integrator 0
 // kAccum: a pass of an accumulator (Args::accum): a pixel's first unit starts from the slot's stored f64
 // mean, the unit that runs a pixel's last sample of the pass stores the XORWOW state back, and a whole
 // pixel's unit stores its mean.  Sample numbers, and so the divisors of the mean, continue from acc_n0.
@@ -1169,13 +1304,8 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
     uint32_t hslot = kNone;
     if (state == ST_CHECK) {
         SEC(SEC_CHECK);
-        // the winner must be a triangle the reference tests (DESIGN.md "Traversal"); if not
-        // (rare), the exact reference-BVH walk redoes the ray
         const uint32_t slot = (uint32_t)htri;
-        const float4* hr = a.hrec + 3 * (size_t)slot;
-        const float4 b0 = hr[0], b1 = hr[1];
-        htri = (int32_t)__float_as_uint(b1.w);
-        state = ref_tested_box(b0, b1, __float_as_uint(b1.z), ro, rd, a.rnodes, a.rparent) ? ST_SHADE : ST_SLOW;
+        state = check_winner(a, htri, ro, rd) ? ST_SHADE : ST_SLOW;
         if (state == ST_SHADE && a.num_spheres == 0 && a.rec_shading) hslot = slot;
     }
     int n = (int)k0.x, i = (int)k0.y;
@@ -1274,20 +1404,7 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
                        &htri, &ht, kCount ? a.tri_counts : nullptr);
         }
         state = ST_SHADE;
-        if (a.num_spheres && !(fl & CF_MEMO)) apply_spheres(a, ro, rd, &htri, &ht);
-        fl &= ~CF_MEMO;
-        if (fl & CF_PRIMARY) {
-            fl = (fl | CF_HAVE) & ~CF_PRIMARY;
-            R.st2(CW_MTRI, (uint32_t)htri, __float_as_uint(ht));
-            if (fl & CF_OWNER) {
-                const uint32_t q = R.ld(CW_Q);
-                // (one relaxed 64-bit store: no release, i.e. no write-back of this XCD's L2)
-                __hip_atomic_store(reinterpret_cast<uint64_t*>(a.pmemo) + q,
-                                   ((uint64_t)__float_as_uint(ht) << 32) | (uint32_t)(htri + 2), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-                fl &= ~CF_OWNER;
-            }
-        }
+        take_hit(a, R, CW_MTRI, CW_Q, fl, ro, rd, htri, ht);
         // bounce i of radianceAlongSingleStep2 (kernel.cu:427-512) on hit (htri, ht)
         {
             SEC(SEC_BOUNCE);
@@ -1347,19 +1464,11 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
             if (!cosb) {
                 SEC(SEC_LIGHT);
                 r3 = rng_uniform(rng);
-                // area-CDF pick (pick_light); the scan stops once randArea <= 0
-                float ra = a.total_light_area * r1;
-                uint32_t sel = a.num_lights;
                 // (the records staged in the block's LDS when few; the pick reads them there)
                 const DLight* const lt = (a.num_lights < kLdsLights)
                                              ? reinterpret_cast<const DLight*>(lprobe + 4 + kMaxProbeEmitters * 12)
                                              : a.lights;
-                for (uint32_t j = 0; j < a.num_lights && ra > 0; ++j) {
-                    const float area = lt[j].area;
-                    if (ra < area && ra > 0) sel = j;
-                    ra -= area;
-                }
-                L = lt + sel;
+                L = lt + light_scan(lt, a.num_lights, a.total_light_area * r1);
                 if (L->pad != 0.0f) { need_sc = true; ang = r3; }   // sphere light: phi = 2*3.14159*v
             } else {
                 SEC(SEC_COSINE);
@@ -1423,42 +1532,14 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
                                               : c3(dbl(a01.x, a01.y), dbl(a01.z, a01.w), dbl(a2m0.x, a2m0.y));
                 if (!(fl & CF_SPLIT) || (fl & CF_CHUNK0)) {
                     const uint4 m12 = R.ld4(CW_M + 2);
-                    const double fn1 = (double)(float)(n - 1), fn = (double)(float)n;   // kernel.cu:551-552
-                    const double x0 = dbl(a2m0.z, a2m0.w) * fn1, x1 = dbl(m12.x, m12.y) * fn1,
-                                 x2 = dbl(m12.z, m12.w) * fn1;
-                    double m0, m1, m2;
-                    // the six quotients by fn: one IEEE reciprocal + Markstein corrections (RN(x/fn)
-                    // for finite x clear of under/overflow -- else the whole wave divides)
-                    if (__ballot(!(quot_ok(x0) && quot_ok(x1) && quot_ok(x2) && quot_ok(acc.r) && quot_ok(acc.g) &&
-                                   quot_ok(acc.b))) == 0ull) {
-                        const double rf = 1.0 / fn;
-                        m0 = div_mk_d(x0, fn, rf) + div_mk_d(acc.r, fn, rf);
-                        m1 = div_mk_d(x1, fn, rf) + div_mk_d(acc.g, fn, rf);
-                        m2 = div_mk_d(x2, fn, rf) + div_mk_d(acc.b, fn, rf);
-                    } else {
-                        m0 = x0 / fn + acc.r / fn;
-                        m1 = x1 / fn + acc.g / fn;
-                        m2 = x2 / fn + acc.b / fn;
-                    }
+                    const C3 m = mean_step(n, dbl(a2m0.z, a2m0.w), dbl(m12.x, m12.y), dbl(m12.z, m12.w), acc);
+                    const double m0 = m.r, m1 = m.g, m2 = m.b;
                     if ((uint32_t)n >= nend) {   // (a whole pixel's unit ends at spp)
                         if (fl & CF_CHUNK0) {
                             double* P = a.lbuf + (size_t)c8.w * 3;
                             P[0] = m0; P[1] = m1; P[2] = m2;
-                        } else {
-                            if (kAccum) {   // the slot's mean and stream (c8.w: a whole unit's slot), for the next pass
-                                const size_t P = a.npix;
-                                double* am = a.acc_mean + c8.w;
-                                am[0] = m0; am[P] = m1; am[2 * P] = m2;
-                                uint32_t* ar = a.acc_rng + c8.w;
-                                ar[0] = rng.v0; ar[P] = rng.v1; ar[2 * P] = rng.v2; ar[3 * P] = rng.v3; ar[4 * P] = rng.v4;
-                                ar[5 * P] = rng.d;
-                            }
-                            if (!kAccum || a.out) {
-                                float* o3 = a.out + out_pixel(a, px, py) * 3;
-                                o3[0] = (float)m0;
-                                o3[1] = (float)m1;
-                                o3[2] = (float)m2;
-                            }
+                        } else {   // (c8.w: an accumulating whole unit's slot)
+                            finish_pixel<kAccum>(a, c8.w, px, py, m0, m1, m2, rng.v0, rng.v1, rng.v2, rng.v3, rng.v4, rng.d);
                         }
                         state = ST_IDLE;
                         break;
@@ -1474,12 +1555,8 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
                     L[1] = acc.g;
                     L[2] = acc.b;
                     if ((uint32_t)n >= nend) {
-                        if (kAccum && nend == a.acc_n0 + (uint32_t)a.spp) {   // the pixel's last sample of the pass
-                            const size_t P = a.npix;
-                            uint32_t* ar = a.acc_rng + a.nwhole + c8.w;
-                            ar[0] = rng.v0; ar[P] = rng.v1; ar[2 * P] = rng.v2; ar[3 * P] = rng.v3; ar[4 * P] = rng.v4;
-                            ar[5 * P] = rng.d;
-                        }
+                        if (kAccum && nend == a.acc_n0 + (uint32_t)a.spp)   // the pixel's last sample of the pass
+                            store_stream(a.npix, a.acc_rng + a.nwhole + c8.w, rng.v0, rng.v1, rng.v2, rng.v3, rng.v4, rng.d);
                         state = ST_IDLE;
                         break;
                     }
@@ -1536,54 +1613,9 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
     uint64_t idle = __ballot(state == ST_IDLE);
     if (idle) {
         SEC(SEC_REFILL);
-        uint32_t u = kNoUnit;
-        if (a.unit_queues > 1u) {
-            // The units dealt from kQueues counters (one 128-B line each), counter x owning the blocks
-            // j = x (mod kQueues) of kQueueBlock units in order -- so the unit sequence is still taken
-            // roughly front to back -- each wave starting at its block's counter and moving on when
-            // that one is exhausted (the block's LDS mask, so every wave of the block and every lane
-            // sees the same): the refill's atomics spread over kQueues addresses.  Which units a lane
-            // gets never changes what it computes.
-            uint32_t qdone = *reinterpret_cast<volatile const uint32_t*>(lprobe + 1);
-            const uint32_t x0 = blockIdx.x & (kQueues - 1u);
-            for (uint32_t r = 0; r < kQueues && idle && qdone != (1u << kQueues) - 1u; ++r) {
-                const uint32_t x = (x0 + r) & (kQueues - 1u);
-                if (qdone & (1u << x)) continue;
-                const int leader = __ffsll((long long)idle) - 1;
-                uint32_t base = 0;
-                if (lane == leader) base = atomicAdd(a.pixel_counter + kQueueStride * (x + 1u), (uint32_t)__popcll(idle));
-                base = __shfl(base, leader, 64);
-                if (state == ST_IDLE && u == kNoUnit) {
-                    const uint32_t k = base + (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
-                    const uint64_t uq = ((uint64_t)(k / kQueueBlock) * kQueues + x) * kQueueBlock + (k % kQueueBlock);
-                    if (uq < a.nunits) u = (uint32_t)uq;
-                }
-                const uint64_t left = __ballot(state == ST_IDLE && u == kNoUnit);
-                if (left) {   // (a counter only grows: past its class's end for good)
-                    qdone |= 1u << x;
-                    if (lane == leader) atomicOr(const_cast<uint32_t*>(lprobe + 1), 1u << x);
-                }
-                idle = left;
-            }
-            if (state == ST_IDLE && u == kNoUnit) u = a.nunits;   // every counter exhausted
-        } else {
-            const uint32_t need = (uint32_t)__popcll(idle);
-            const int leader = __ffsll((long long)idle) - 1;
-            uint32_t base = 0;
-            if (lane == leader) base = atomicAdd(a.pixel_counter, need);
-            base = __shfl(base, leader, 64);
-            if (state == ST_IDLE) u = base + (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
-        }
+        const uint32_t u = take_unit<kCount>(a, lane, idle, state == ST_IDLE, lprobe, done_rel);
         if (state == ST_IDLE) {
             if (u >= a.nunits) {
-                if (kCount) {   // queue drained; this lane's end after it and since the start (binned at the end)
-                    const unsigned long long now = wall_clock64();
-                    atomicMin(a.counters + CNT_T_DRAINED, now);
-                    const unsigned long long d0 = __hip_atomic_load(a.counters + CNT_T_DRAINED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const unsigned long long s0 = __hip_atomic_load(a.counters + CNT_T_START, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    done_rel[0] = (uint32_t)min(now - min(now, d0), 0xffffffffull);
-                    done_rel[1] = (uint32_t)min(now - min(now, s0), 0xffffffffull);
-                }
                 if (a.lane_times) a.lane_times[R.voff >> 4] = wall_clock64();
                 state = ST_DONE;
             } else {
@@ -1642,11 +1674,6 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
       if (__ballot(again) == 0ull) break;
     }
 
-    // the first visits of every ray begun in this pass (the root and, while the next node is staged
-    // in LDS and no leaf is queued, up to root_first - 1 more), here -- all such lanes together, one
-    // copy of the code -- instead of as walk steps: the walk is that many steps shorter per ray.  (A
-    // fresh walk is the only one at node 0.)  Nothing entered: the walk is over without a candidate,
-    // as a finished walk would be; the lane shades in the next pass.
     if (a.root_first && state == ST_TRACE && w.node == 0u) {
         bool more = walk4_root<kCount>(w, S, kCullRel, a.node_mask, cnt);
         // (up to root_first visits: the next node too while it is staged in LDS and no leaf is queued)
@@ -1662,55 +1689,6 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
 }
 
 
-// The refill's unit dealing (as in shade_lane): lanes `idle` of the wave take the next units of this
-// shard from the unit counters; returns this lane's unit (`me`: this lane is idle), a.nunits once
-// every counter is exhausted.
-template <bool kCount>
-__device__ __forceinline__ uint32_t take_unit(const Args& a, int lane, uint64_t idle, bool me, const uint32_t* lprobe,
-                                              uint32_t* done_rel)
-{
-    uint32_t u = kNoUnit;
-    if (a.unit_queues > 1u) {
-        uint32_t qdone = *reinterpret_cast<volatile const uint32_t*>(lprobe + 1);
-        const uint32_t x0 = blockIdx.x & (kQueues - 1u);
-        for (uint32_t r = 0; r < kQueues && idle && qdone != (1u << kQueues) - 1u; ++r) {
-            const uint32_t x = (x0 + r) & (kQueues - 1u);
-            if (qdone & (1u << x)) continue;
-            const int leader = __ffsll((long long)idle) - 1;
-            uint32_t base = 0;
-            if (lane == leader) base = atomicAdd(a.pixel_counter + kQueueStride * (x + 1u), (uint32_t)__popcll(idle));
-            base = __shfl(base, leader, 64);
-            if (me && u == kNoUnit) {
-                const uint32_t k = base + (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
-                const uint64_t uq = ((uint64_t)(k / kQueueBlock) * kQueues + x) * kQueueBlock + (k % kQueueBlock);
-                if (uq < a.nunits) u = (uint32_t)uq;
-            }
-            const uint64_t left = __ballot(me && u == kNoUnit);
-            if (left) {
-                qdone |= 1u << x;
-                if (lane == leader) atomicOr(const_cast<uint32_t*>(lprobe + 1), 1u << x);
-            }
-            idle = left;
-        }
-        if (me && u == kNoUnit) u = a.nunits;
-    } else {
-        const uint32_t need = (uint32_t)__popcll(idle);
-        const int leader = __ffsll((long long)idle) - 1;
-        uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(a.pixel_counter, need);
-        base = __shfl(base, leader, 64);
-        if (me) u = base + (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
-    }
-    if (kCount && me && u >= a.nunits) {   // queue drained; this lane's end after it and since the start
-        const unsigned long long now = wall_clock64();
-        atomicMin(a.counters + CNT_T_DRAINED, now);
-        const unsigned long long d0 = __hip_atomic_load(a.counters + CNT_T_DRAINED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long s0 = __hip_atomic_load(a.counters + CNT_T_START, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        done_rel[0] = (uint32_t)min(now - min(now, d0), 0xffffffffull);
-        done_rel[1] = (uint32_t)min(now - min(now, s0), 0xffffffffull);
-    }
-    return u;
-}
 // ------------------------------------------------------------------ wavefront kernel, integrator 1
 // radianceAlongSingleStep (kernel.cu:217-415) on the same state machine.  A sample is a fixed data
 // flow of traces: T1 the light subpath's bounce from the area-sampled light vertex x0 (kernel.cu:263-
@@ -1852,10 +1830,7 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
     const uint4 k0 = R.ld4(HW_N);
     if (state == ST_CHECK) {
         SEC(SEC_CHECK);
-        const float4* hr = a.hrec + 3 * (size_t)(uint32_t)htri;
-        const float4 b0 = hr[0], b1 = hr[1];
-        htri = (int32_t)__float_as_uint(b1.w);
-        state = ref_tested_box(b0, b1, __float_as_uint(b1.z), ro, rd, a.rnodes, a.rparent) ? ST_SHADE : ST_SLOW;
+        state = check_winner(a, htri, ro, rd) ? ST_SHADE : ST_SLOW;
     }
     int n = (int)k0.x;
     uint32_t stage = k0.y & 0xffffu, fl = k0.y >> 16;
@@ -1881,22 +1856,6 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
         state = ST_TRACE;
         return false;
     };
-    // a hit is at hand (after a walk, the slow walk or the memo): spheres, primary memo bookkeeping
-    auto take_hit = [&]() {
-        if (a.num_spheres && !(fl & CF_MEMO)) apply_spheres(a, ro, rd, &htri, &ht);
-        fl &= ~CF_MEMO;
-        if (fl & CF_PRIMARY) {
-            fl = (fl | CF_HAVE) & ~CF_PRIMARY;
-            R.st2(HW_MTRI, (uint32_t)htri, __float_as_uint(ht));
-            if (fl & CF_OWNER) {
-                const uint32_t q = R.ld(HW_Q);
-                __hip_atomic_store(reinterpret_cast<uint64_t*>(a.pmemo) + q,
-                                   ((uint64_t)__float_as_uint(ht) << 32) | (uint32_t)(htri + 2), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-                fl &= ~CF_OWNER;
-            }
-        }
-    };
     // start sample n: all of its draws, the light vertex, the camera ray of a lens sample; trace T1
     auto start_sample = [&](uint32_t px, uint32_t py, bool have_rng) -> bool {
         SEC(SEC_START);
@@ -1909,27 +1868,16 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
         float lu1 = 0.0f, lu2 = 0.0f;
         if (lens) { lu1 = rng_uniform(rng); lu2 = rng_uniform(rng); }   // drawPixel's cameraRay (kernel.cu:547)
         // light vertex: the area-CDF pick + uniform point (pick_light, kernel.cu:231-262)
-        float ra = a.total_light_area * rng_uniform(rng);
-        uint32_t sel = a.num_lights;
         const bool staged = a.num_lights < kLdsLights;
         const DLight* const lt = staged ? llt : a.lights;
-        for (uint32_t j = 0; j < a.num_lights && ra > 0; ++j) {
-            const float area = lt[j].area;
-            if (ra < area && ra > 0) sel = j;
-            ra -= area;
-        }
+        const uint32_t sel = light_scan(lt, a.num_lights, a.total_light_area * rng_uniform(rng));
         float u = rng_uniform(rng);
         float v = rng_uniform(rng);
         const DLight* L = lt + sel;
         V3 p, n0;
         int32_t m0;
         if (L->pad != 0.0f) {   // sphere light (d8)
-            const float z = 1.0f - 2.0f * u;
-            const float rxy = sqrtf(__builtin_fmaxf(0.0f, 1.0f - z * z));
-            const float phi = (float)(2 * 3.14159 * (double)v);
-            float si, co;
-            det_sincos(phi, &si, &co);
-            p = v3(L->v0[0], L->v0[1], L->v0[2]) + v3(rxy * co, rxy * si, z) * L->a1[0];
+            p = light_point_sphere(*L, u, v);
             n0 = prim_normal(a, L->tri, p);
             m0 = prim_mat(a, L->tri);
         } else {
@@ -2023,7 +1971,7 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
                        &htri, &ht, kCount ? a.tri_counts : nullptr);
         }
         state = ST_SHADE;
-        take_hit();
+        take_hit(a, R, HW_MTRI, HW_Q, fl, ro, rd, htri, ht);
         for (;;) {   // consume the hit; advance until the lane needs a trace or its unit is done
             SEC(SEC_BOUNCE);
             bool sample_done = false;
@@ -2042,7 +1990,7 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
                 R.st4(HW_N1, __float_as_uint(n2.x), __float_as_uint(n2.y), __float_as_uint(n2.z), 0u);
                 if (camera_stage()) {
                     if (state == ST_SLOW) { again = true; break; }
-                    take_hit();
+                    take_hit(a, R, HW_MTRI, HW_Q, fl, ro, rd, htri, ht);
                     continue;   // the camera hit is at hand (memo or a root miss)
                 }
                 break;
@@ -2070,7 +2018,7 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
                 wave_count(lcnt + 1, lane);
                 if (begin_trace(kMaxFloat, -1.0f)) {
                     if (state == ST_SLOW) { again = true; break; }
-                    take_hit();
+                    take_hit(a, R, HW_MTRI, HW_Q, fl, ro, rd, htri, ht);
                     continue;
                 }
                 break;
@@ -2107,7 +2055,7 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
                     asm volatile("" ::: "memory");
                     if (vis_stage(k, ldv((k >> 1) ? HW_X1 : HW_X0), ldv((k & 1u) ? HW_X3 : HW_X2))) {
                         if (state == ST_SLOW) { again = true; break; }
-                        take_hit();
+                        take_hit(a, R, HW_MTRI, HW_Q, fl, ro, rd, htri, ht);
                         continue;
                     }
                     break;
@@ -2122,7 +2070,7 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
                     const V3 xi = ldv((k2 >> 1) ? HW_X1 : HW_X0), xj = ldv((k2 & 1u) ? HW_X3 : HW_X2);
                     if (vis_stage(k2, xi, xj)) {
                         if (state == ST_SLOW) { again = true; break; }
-                        take_hit();
+                        take_hit(a, R, HW_MTRI, HW_Q, fl, ro, rd, htri, ht);
                         continue;
                     }
                     break;
@@ -2151,34 +2099,11 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
             if (!(fl & CF_SPLIT)) {
                 const uint4 m01 = R.ld4(HW_M);
                 const uint2 m2 = R.ld2(HW_M + 4);
-                const double fn1 = (double)(float)(n - 1), fn = (double)(float)n;
-                const double x0 = dbl(m01.x, m01.y) * fn1, x1 = dbl(m01.z, m01.w) * fn1, x2 = dbl(m2.x, m2.y) * fn1;
-                double m0, mm1, mm2;
-                if (__ballot(!(quot_ok(x0) && quot_ok(x1) && quot_ok(x2) && quot_ok(acc.r) && quot_ok(acc.g) &&
-                               quot_ok(acc.b))) == 0ull) {
-                    const double rf = 1.0 / fn;
-                    m0 = div_mk_d(x0, fn, rf) + div_mk_d(acc.r, fn, rf);
-                    mm1 = div_mk_d(x1, fn, rf) + div_mk_d(acc.g, fn, rf);
-                    mm2 = div_mk_d(x2, fn, rf) + div_mk_d(acc.b, fn, rf);
-                } else {
-                    m0 = x0 / fn + acc.r / fn;
-                    mm1 = x1 / fn + acc.g / fn;
-                    mm2 = x2 / fn + acc.b / fn;
-                }
+                const C3 m = mean_step(n, dbl(m01.x, m01.y), dbl(m01.z, m01.w), dbl(m2.x, m2.y), acc);
+                const double m0 = m.r, mm1 = m.g, mm2 = m.b;
                 if (kAccum ? (uint32_t)n >= r2.y : n >= a.spp) {   // (the unit's end: a plain whole pixel's is spp)
-                    if (kAccum) {   // the slot's mean and stream (c13.y: a whole unit's slot), for the next pass
-                        const size_t P = a.npix;
-                        double* am = a.acc_mean + c13.y;
-                        am[0] = m0; am[P] = mm1; am[2 * P] = mm2;
-                        uint32_t* ar = a.acc_rng + c13.y;
-                        ar[0] = r1.x; ar[P] = r1.y; ar[2 * P] = r1.z; ar[3 * P] = r1.w; ar[4 * P] = r2.x; ar[5 * P] = rng.d;
-                    }
-                    if (!kAccum || a.out) {
-                        float* o3 = a.out + out_pixel(a, px, py) * 3;
-                        o3[0] = (float)m0;
-                        o3[1] = (float)mm1;
-                        o3[2] = (float)mm2;
-                    }
+                    // (c13.y: an accumulating whole unit's slot)
+                    finish_pixel<kAccum>(a, c13.y, px, py, m0, mm1, mm2, r1.x, r1.y, r1.z, r1.w, r2.x, rng.d);
                     state = ST_IDLE;
                     break;
                 }
@@ -2191,11 +2116,8 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
                 Lb[1] = acc.g;
                 Lb[2] = acc.b;
                 if ((uint32_t)n >= r2.y) {
-                    if (kAccum && r2.y == a.acc_n0 + (uint32_t)a.spp) {   // the pixel's last sample of the pass
-                        const size_t P = a.npix;
-                        uint32_t* ar = a.acc_rng + a.nwhole + c13.y;
-                        ar[0] = r1.x; ar[P] = r1.y; ar[2 * P] = r1.z; ar[3 * P] = r1.w; ar[4 * P] = r2.x; ar[5 * P] = rng.d;
-                    }
+                    if (kAccum && r2.y == a.acc_n0 + (uint32_t)a.spp)   // the pixel's last sample of the pass
+                        store_stream(a.npix, a.acc_rng + a.nwhole + c13.y, r1.x, r1.y, r1.z, r1.w, r2.x, rng.d);
                     state = ST_IDLE;
                     break;
                 }
