@@ -22,6 +22,8 @@ PT_FLAG_NO_PRIMARY_CACHE = 0x4
 PT_FLAG_COUNT = 0x8
 PT_FLAG_REFERENCE_BVH = 0x10
 PT_FLAG_TRI_COUNTS = 0x20
+PT_FLAG_JITTER = 0x40        # sub-pixel jitter, box filter over the pixel footprint
+PT_FLAG_JITTER_TENT = 0x80   # with PT_FLAG_JITTER: tent of half-width 1 pixel
 PT_ORDER_SCANLINE, PT_ORDER_MORTON = 0, 1
 PT_LIGHT_SPHERE = 0x80000000     # lights[] entry of an emissive sphere
 ABI_VERSION = 6                 # PT_ABI_VERSION of include/pt/pt.h these bindings mirror
@@ -165,6 +167,9 @@ SIGNATURES = {
     "pt_view_validate": (C.c_int, [C.POINTER(View)]),
     "pt_camera_ray_view": (None, [C.POINTER(Camera), C.POINTER(View), C.c_uint32, C.c_int, C.c_float, C.c_float,
                                   C.POINTER(Vec3), C.POINTER(Vec3)]),
+    "pt_jitter_offset": (C.c_int, [C.c_uint32, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "pt_camera_ray_jitter": (None, [C.POINTER(Camera), C.POINTER(View), C.c_uint32, C.c_float, C.c_float, C.c_int, C.c_float,
+                                    C.c_float, C.POINTER(Vec3), C.POINTER(Vec3)]),
     "pt_write_ppm": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int]),
     "pt_write_ppm_f64": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int]),
     "pt_write_ppm_order": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),

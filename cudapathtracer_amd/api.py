@@ -192,10 +192,22 @@ def _view_ref(view):
     return None if view is None else C.byref(view)
 
 
-def camera_ray(cam, idx, lens=False, u1=0.0, u2=0.0, view=None):
-    """(origin, direction) of pixel `idx` (a Morton index): pt_camera_ray, or pt_camera_ray_view with a view."""
+def jitter_offset(flags, ua, ub):
+    """(jx, jy): the film-point offset of a jittered sample's first two draws (pt_jitter_offset): (ua, ub) for
+    PT_FLAG_JITTER, 0.5 + the tent's inverse CDF with PT_FLAG_JITTER_TENT as well, (0, 0) without the flag."""
+    jx, jy = C.c_float(), C.c_float()
+    L.check(L.lib().pt_jitter_offset(int(flags), float(ua), float(ub), C.byref(jx), C.byref(jy)))
+    return jx.value, jy.value
+
+
+def camera_ray(cam, idx, lens=False, u1=0.0, u2=0.0, view=None, jitter=None):
+    """(origin, direction) of pixel `idx` (a Morton index): pt_camera_ray, or pt_camera_ray_view with a view, or
+    pt_camera_ray_jitter through (px + jx, py + jy) with jitter=(jx, jy)."""
     o, d = L.Vec3(), L.Vec3()
-    if view is None:
+    if jitter is not None:
+        L.lib().pt_camera_ray_jitter(C.byref(cam), _view_ref(view), int(idx), float(jitter[0]), float(jitter[1]),
+                                     int(bool(lens)), float(u1), float(u2), C.byref(o), C.byref(d))
+    elif view is None:
         L.lib().pt_camera_ray(C.byref(cam), int(idx), int(bool(lens)), float(u1), float(u2), C.byref(o), C.byref(d))
     else:
         L.lib().pt_camera_ray_view(C.byref(cam), C.byref(view), int(idx), int(bool(lens)), float(u1), float(u2),
@@ -381,23 +393,24 @@ class Renderer:
             a._noise = NoiseEstimate(a, est.value)
         return a, a._noise
 
-    def features(self, cam, width, height, pixel_order=0, shard_index=0, shard_count=1, tile=0, view=None):
+    def features(self, cam, width, height, pixel_order=0, shard_index=0, shard_count=1, tile=0, view=None, flags=0):
         """Primary-hit feature buffers (pt_render_features): a FEATURE structured array of shape (H, W) -- (W*H,)
         in Morton order -- with albedo, depth, normal, prim and position of each pixel's pinhole camera ray.
-        Pixels outside the shard are all zero with prim = -1.  `tile`: one int or (tile_w, tile_h); 0 = 8."""
+        Pixels outside the shard are all zero with prim = -1.  `tile`: one int or (tile_w, tile_h); 0 = 8.
+        `flags`: the render's; with PT_FLAG_JITTER the ray goes through the centre of the pixel's footprint."""
         tw, th = (tile, tile) if np.isscalar(tile) else tile
-        p = self.params(width, height, 0, 1, 0, 0, 0, shard_index, shard_count, pixel_order, tw, th)
+        p = self.params(width, height, 0, 1, 0, 0, flags, shard_index, shard_count, pixel_order, tw, th)
         shape = (height * width,) if pixel_order == L.PT_ORDER_MORTON else (height, width)
         out = np.zeros(shape, dtype=FEATURE)
         L.check(L.lib().pt_render_features_view(self._h, C.byref(p), C.byref(cam), _view_ref(view), out.ctypes.data))
         return out
 
     def features_device(self, cam, d_feat_ptr, width, height, pixel_order=0, shard_index=0, shard_count=1, tile=0,
-                        stream_ptr=None, view=None):
+                        stream_ptr=None, view=None, flags=0):
         """This shard's features into a caller-owned device buffer of W*H 48-byte records (16-byte aligned);
-        records of other pixels are left untouched."""
+        records of other pixels are left untouched.  `flags` as for features()."""
         tw, th = (tile, tile) if np.isscalar(tile) else tile
-        p = self.params(width, height, 0, 1, 0, 0, 0, shard_index, shard_count, pixel_order, tw, th)
+        p = self.params(width, height, 0, 1, 0, 0, flags, shard_index, shard_count, pixel_order, tw, th)
         L.check(L.lib().pt_render_features_view_device(self._h, C.byref(p), C.byref(cam), _view_ref(view),
                                                        C.c_void_p(int(d_feat_ptr)),
                                                        None if stream_ptr is None else C.c_void_p(int(stream_ptr))))

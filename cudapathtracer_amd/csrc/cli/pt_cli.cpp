@@ -61,6 +61,11 @@
 //                                         looking down -z.  --session writes the view (format version 3); after
 //                                         --resume-session the view is the file's, and a command-line view that differs is
 //                                         an error; --checkpoint cannot hold a view (the library's message says so)
+// --jitter box|tent                       sub-pixel jitter (PT_FLAG_JITTER; tent: PT_FLAG_JITTER_TENT as well): every sample's
+//                                         camera ray goes through its own point of the film, so edges are anti-aliased.
+//                                         With every mode that renders; with --aov the feature rays go through the pixels'
+//                                         centres.  After --resume / --resume-session the flags are the file's, and a
+//                                         --jitter that differs is an error
 // --aov PREFIX                            write the primary-hit feature buffers as PREFIX_albedo.pfm,
 //                                         PREFIX_normal.pfm, PREFIX_position.pfm and PREFIX_depth.pfm (depth
 //                                         replicated to 3 channels)
@@ -91,7 +96,7 @@ struct Obj {
             "              [--width W] [--height H] [--spp N | --num-samples N] [--bounces D]\n"
             "              [--integrator unidir|head] [--seed S] [--cam X,Y,Z] [--dist D] [--focal F]\n"
             "              [--radius R] [--gpus N] [--out image.ppm] [--pfm image.pfm] [--quiet]\n"
-            "              [--look-at X,Y,Z] [--up X,Y,Z] [--vfov DEG | --film W,H]\n"
+            "              [--look-at X,Y,Z] [--up X,Y,Z] [--vfov DEG | --film W,H] [--jitter box|tent]\n"
             "              [--tri-counts out.csv [--reference-walk]] [--morton] [--tile WxH]\n"
             "              [--checkpoint FILE] [--resume FILE] [--pass-spp K]\n"
             "              [--session FILE] [--resume-session FILE]\n"
@@ -111,6 +116,8 @@ struct Obj {
             "  --resume-session FILE  continue the render FILE holds; its estimator window continues; --spp is the samples to add\n"
             "  --look-at X,Y,Z    aim the camera at a point (--up X,Y,Z, default 0,1,0); --vfov DEG: the vertical field of view\n"
             "                     with square pixels; --film W,H: the film's extent (1,1 = the reference's unit square)\n"
+            "  --jitter box|tent  anti-alias: every sample's camera ray through its own point of the pixel's footprint (box), or\n"
+            "                     of the tent of half-width 1 pixel about its centre (tent)\n"
             "  --aov PREFIX       write PREFIX_albedo.pfm, PREFIX_normal.pfm, PREFIX_position.pfm, PREFIX_depth.pfm\n");
     exit(2);
 }
@@ -166,6 +173,7 @@ int main(int argc, char** argv)
     int gpus = 1;
     bool quiet = false, ref_walk = false;
     std::string tri_csv, checkpoint, resume, session, resume_session;
+    uint32_t jitter_flags = 0;   // --jitter: PT_FLAG_JITTER, with PT_FLAG_JITTER_TENT for tent
     int pass_spp = 0;
     bool denoise = false;
     pt_denoise_params dparams;
@@ -237,6 +245,12 @@ int main(int argc, char** argv)
         else if (a == "--sigma-luma") gparams.sigma_luma = strtof(next().c_str(), nullptr);
         else if (a == "--variance-map") variance_map = next();
         else if (a == "--aov") aov = next();
+        else if (a == "--jitter") {
+            const std::string v = next();
+            if (v == "box") jitter_flags = PT_FLAG_JITTER;
+            else if (v == "tent") jitter_flags = PT_FLAG_JITTER | PT_FLAG_JITTER_TENT;
+            else usage("--jitter is box or tent");
+        }
         else if (a == "--until-error") { until_error = true; conv.noise.tol = strtof(next().c_str(), nullptr); }
         else if (a == "--error-quantile") conv.quantile = strtof(next().c_str(), nullptr);
         else if (a == "--min-batches") conv.min_batches = atoi(next().c_str());
@@ -267,6 +281,7 @@ int main(int argc, char** argv)
     // --reference-walk: the reference's own trace() sequence for every sample (its node order, the
     // camera ray traced per sample, dead paths traced), so --tri-counts reproduces its out.csv
     if (ref_walk) p.flags |= PT_FLAG_REFERENCE_TRAVERSAL | PT_FLAG_NO_PRIMARY_CACHE | PT_FLAG_NO_DEAD_PATH_SKIP;
+    p.flags |= jitter_flags;
     cam.pxl_width = p.width;
     cam.pxl_height = p.height;
     const bool estimate = until_error || !error_map.empty() || !variance_map.empty();
@@ -322,6 +337,7 @@ int main(int argc, char** argv)
         conflict("--dist", cam.dist_from_film != fc.dist_from_film);
         conflict("--focal", cam.focal_length != fc.focal_length);
         conflict("--radius", cam.radius != fc.radius);
+        conflict("--jitter", ((p.flags ^ fp.flags) & (PT_FLAG_JITTER | PT_FLAG_JITTER_TENT)) != 0);
         const int add = p.spp;
         p = fp;
         p.spp = add;

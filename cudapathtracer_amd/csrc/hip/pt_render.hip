@@ -604,6 +604,66 @@ __device__ __forceinline__ void camera_ray_view(const Args& a, uint32_t px, uint
         *o = v3(0.0f, 0.0f, 0.0f) + v3(cam.pos[0], cam.pos[1], cam.pos[2]);
 }
 
+// Sub-pixel jitter (PT_FLAG_JITTER, pt.h: no counterpart in the reference).  A sample's first two draws (ua, ub)
+// place its camera ray in the pixel's footprint: the offset itself (box), or 0.5 + the inverse CDF of the tent of
+// half-width 1 pixel (PT_FLAG_JITTER_TENT).  Every operation rounded on its own, IEEE square root.
+__device__ __forceinline__ float jitter_tent(float u)
+{
+    return (u < 0.5f) ? sqrtf(2.0f * u) - 1.0f : 1.0f - sqrtf(2.0f - 2.0f * u);
+}
+__device__ __forceinline__ void jitter_offset(uint32_t flags, float ua, float ub, float* jx, float* jy)
+{
+    if (flags & PT_FLAG_JITTER_TENT) { *jx = 0.5f + jitter_tent(ua); *jy = 0.5f + jitter_tent(ub); }
+    else { *jx = ua; *jy = ub; }
+}
+// The ray of a jittered sample: camera_ray's / camera_ray_view's arithmetic, operation for operation, with
+// (px + jx, py + jy) in the place of the pixel's corner (jx = jy = 0 gives their bits).  The view is taken under the
+// wave-uniform a.oriented -- the jittered kernels are instances of their own (kJit), one set for both cameras -- and
+// only where the two cameras differ (the film's scale, the basis), so the lens offset's sin/cos stands once in them.
+// `lens`: the sample drew a lens pair (u1, u2) -- radius != 0 or Morton index 0, as everywhere.
+template <bool kFresh = true>
+__device__ __forceinline__ void camera_ray_jitter(const Args& a, uint32_t px, uint32_t py, float jx, float jy, bool lens,
+                                                  float u1, float u2, V3* o, V3* d)
+{
+    const Cam& cam = a.cam;
+    auto w = [](float x) { return kFresh ? fresh(x) : x; };
+    const int cw = kFresh ? fresh(cam.w) : cam.w, ch = kFresh ? fresh(cam.h) : cam.h;
+    const uint32_t oriented = kFresh ? fresh(a.oriented) : a.oriented;
+    const float sx = (float)px + jx, sy = (float)py + jy;
+    V3 film = v3(sx / (float)cw - 0.5f, sy / (float)ch - 0.5f, cam.dist);
+    if (oriented) { film.x = film.x * w(a.film_w); film.y = film.y * w(a.film_h); }
+    film = (film * -cam.focal) / cam.dist;
+    V3 lo = v3(0.0f, 0.0f, 0.0f);
+    if (lens) {
+        const float r = cam.radius * sqrtf(u1);
+        const float theta = (float)(2 * 3.14159 * (double)u2);
+        float s, c;
+        det_sincos(theta, &s, &c);
+        lo = v3(r * c, r * s, 0.0f);
+    }
+    const V3 c = film - lo;
+    const V3 pos = v3(cam.pos[0], cam.pos[1], cam.pos[2]);
+    // (one store of each result, after the branch: stores in both arms left the two vectors in scratch)
+    V3 dir = c, org = lo + pos;
+    if (oriented) {
+        const V3 R = v3(w(a.view_right[0]), w(a.view_right[1]), w(a.view_right[2]));
+        const V3 U = v3(w(a.view_up[0]), w(a.view_up[1]), w(a.view_up[2]));
+        const V3 B = v3(w(a.view_back[0]), w(a.view_back[1]), w(a.view_back[2]));
+        dir = v3((R.x * c.x + U.x * c.y) + B.x * c.z, (R.y * c.x + U.y * c.y) + B.y * c.z, (R.z * c.x + U.z * c.y) + B.z * c.z);
+        if (lens) org = v3((R.x * lo.x + U.x * lo.y) + pos.x, (R.y * lo.x + U.y * lo.y) + pos.y, (R.z * lo.x + U.z * lo.y) + pos.z);
+        else org = v3(0.0f, 0.0f, 0.0f) + pos;
+    }
+    *d = normalized(dir);
+    *o = org;
+}
+// A pixel draws a lens pair when the camera has a lens or the pixel is Morton index 0 (the reference's quirk):
+// what CF_LENS says in a plain render.  In a jittered render every unit carries CF_LENS ("the ray is formed per
+// sample"), and the kernels recompute this from the pixel.
+__device__ __forceinline__ bool lens_pixel(const Args& a, uint32_t px, uint32_t py)
+{
+    return ((px | py) == 0u) || (fresh(a.cam.radius) != 0.0f);
+}
+
 __device__ __forceinline__ uint32_t morton2(uint32_t x, uint32_t y)   // camera.h:66-75
 {
     uint32_t r = 0;
@@ -649,8 +709,10 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
 
 // ------------------------------------------------------------------ the render kernel
 // (kView: the camera ray goes through the view, camera_ray_view -- render_tiles_view, kernels of their own launched
-// for an oriented render, so that the plain ones keep their names and compile exactly as they did without it)
-template <int kIntegrator, bool kRefWalk, bool kCount, bool kView>
+// for an oriented render, so that the plain ones keep their names and compile exactly as they did without it;
+// kJit: a jittered render, render_tiles_jitter -- every sample draws its film point first and forms its own ray,
+// through the view or not (a.oriented), and the primary memo is off)
+template <int kIntegrator, bool kRefWalk, bool kCount, bool kView, bool kJit = false>
 __device__ __forceinline__ void render_tiles_body(Args& a)
 {
     extern __shared__ uint32_t lds_stack[];
@@ -664,7 +726,7 @@ __device__ __forceinline__ void render_tiles_body(Args& a)
     tr.reference = 0;
     unsigned long long samples = 0;
     const bool skip_dead = !(a.flags & PT_FLAG_NO_DEAD_PATH_SKIP);
-    const bool memo = !(a.flags & PT_FLAG_NO_PRIMARY_CACHE);
+    const bool memo = !kJit && !(a.flags & PT_FLAG_NO_PRIMARY_CACHE);
     for (;;) {
         uint32_t k = 0;   // the next 8x8 block of this shard's tiles (64 work slots)
         if (lane == 0) k = atomicAdd(a.tile_counter, 1u);
@@ -679,10 +741,15 @@ __device__ __forceinline__ void render_tiles_body(Args& a)
         tr.have = false;
         double m0 = 0.0, m1 = 0.0, m2 = 0.0;
         for (int n = 1; n <= a.spp; ++n) {
-            float u1 = 0.0f, u2 = 0.0f;
+            float u1 = 0.0f, u2 = 0.0f, jx = 0.0f, jy = 0.0f;
+            if (kJit) {   // the sample's film point: its first two draws
+                const float ua = rng_uniform(rng), ub = rng_uniform(rng);
+                jitter_offset(a.flags, ua, ub, &jx, &jy);
+            }
             if (lens) { u1 = rng_uniform(rng); u2 = rng_uniform(rng); }
             V3 o, d;
-            if (kView) camera_ray_view<false>(a, px, py, lens, u1, u2, &o, &d);
+            if (kJit) camera_ray_jitter<false>(a, px, py, jx, jy, lens, u1, u2, &o, &d);
+            else if (kView) camera_ray_view<false>(a, px, py, lens, u1, u2, &o, &d);
             else camera_ray<false>(a.cam, px, py, lens, u1, u2, &o, &d);
             C3 L;
             if (kIntegrator == PT_INTEGRATOR_HEAD) L = radiance_head(a, tr, o, d, rng, memo);
@@ -717,6 +784,11 @@ template <int kIntegrator, bool kRefWalk, bool kCount>
 __global__ __launch_bounds__(64) void render_tiles_view(Args a)
 {
     render_tiles_body<kIntegrator, kRefWalk, kCount, true>(a);
+}
+template <int kIntegrator, bool kRefWalk, bool kCount>
+__global__ __launch_bounds__(64) void render_tiles_jitter(Args a)
+{
+    render_tiles_body<kIntegrator, kRefWalk, kCount, false, true>(a);
 }
 
 // ------------------------------------------------------------------ wavefront kernel
@@ -838,8 +910,10 @@ __device__ __forceinline__ uint32_t slot_chunks(const Args& a, uint32_t t)
 // The XORWOW draws one sample of radianceAlongSingleStep2 consumes, without tracing: the count
 // depends only on the draws themselves (lens pair; per bounce u, then 2 for a cosine direction or
 // 3 for a light sample, which also jumps i to D-2) -- the same replay as the dead-path skip.
-__device__ __forceinline__ void replay_sample(Rng& rng, bool lens, int D)
+// (jitter: the two draws of a jittered sample's film point, before the lens pair)
+__device__ __forceinline__ void replay_sample(Rng& rng, bool lens, int D, bool jitter = false)
 {
+    if (jitter) { rng_next(rng); rng_next(rng); }
     if (lens) { rng_next(rng); rng_next(rng); }
     int i = 0;
     while (i < D) {
@@ -904,7 +978,11 @@ __device__ __forceinline__ void reset_render_counters(const Args& a)
 // of this shard -- curand_init of its pixel, fast-forwarded over the unit's earlier samples --
 // computed in parallel before the render, so that a lane starting a unit inside the state
 // machine loads 20 B instead of running the jump-ahead with its wave waiting.
-__global__ __launch_bounds__(256) void init_pixel_states(Args a, uint32_t* __restrict__ st)
+// (kJit: the set-up of a jittered render, init_pixel_states_jitter.  No pixel of it has a sample-invariant ray, so
+// every unit is marked as a lens unit is -- the ray is formed per sample: no UW_CD direction, no CF_CAMC, no memo --
+// and the replay skips two more draws per sample.)
+template <bool kJit>
+__device__ __forceinline__ void init_pixel_states_body(const Args& a, uint32_t* __restrict__ st)
 {
     // one lane per pixel slot: curand_init, then one pass over the samples that writes the state
     // at the start of every chunk, with everything else a lane needs to start the unit (pixel,
@@ -940,15 +1018,16 @@ __global__ __launch_bounds__(256) void init_pixel_states(Args a, uint32_t* __res
     const uint32_t n_done = a.accum ? a.acc_n0 : 0u;   // samples the pixel has before this render
     slot_stream(a, q, idx, n_done, r);
     const bool lens = (idx == 0) || (a.cam.radius != 0.0f);
-    const V3 d = pinhole_dir(a, px, py, lens);
+    const bool per_sample = kJit || lens;   // the unit's mark: its rays are formed per sample
+    const V3 d = pinhole_dir(a, px, py, per_sample);
     uint32_t done = 0;
     for (uint32_t c = 0; c < nc; ++c) {
         const uint32_t s0 = split ? chunk_first(a, c, nc) : 0u;
-        if (a.head) {   // integrator 1: a fixed 7 draws per sample (+2 lens): light pick 3, rand_ray 2, cosine 2
+        if (a.head) {   // integrator 1: a fixed 7 draws per sample (+2 lens, +2 jitter): light pick 3, rand_ray 2, cosine 2
             for (; done < s0; ++done)
-                for (int k = (lens ? 9 : 7); k > 0; --k) rng_next(r);
+                for (int k = (lens ? 9 : 7) + (kJit ? 2 : 0); k > 0; --k) rng_next(r);
         }
-        for (; done < s0; ++done) replay_sample(r, lens, a.bounces);
+        for (; done < s0; ++done) replay_sample(r, lens, a.bounces, kJit);
         const size_t u = unit(c);
         st[u] = r.v0;
         st[N + u] = r.v1;
@@ -959,7 +1038,7 @@ __global__ __launch_bounds__(256) void init_pixel_states(Args a, uint32_t* __res
         st[UW_PXY * N + u] = px | (py << 16);
         // (an accumulating pass: sample numbers continue from n_done, the pixel's first unit is flagged,
         // and a whole-pixel unit carries its slot -- the row of its stored mean and XORWOW state)
-        st[UW_N0 * N + u] = (n_done + s0 + 1u) | (lens ? 0x80000000u : 0u) | ((a.accum && c == 0u) ? kUnitFirst : 0u);
+        st[UW_N0 * N + u] = (n_done + s0 + 1u) | (per_sample ? 0x80000000u : 0u) | ((a.accum && c == 0u) ? kUnitFirst : 0u);
         st[UW_NEND * N + u] = n_done + (split ? chunk_first(a, c + 1, nc) : (uint32_t)a.spp);
         st[UW_TQ * N + u] = split ? t : (a.accum ? q : 0u);
         st[UW_CD * N + u] = __float_as_uint(d.x);
@@ -967,12 +1046,17 @@ __global__ __launch_bounds__(256) void init_pixel_states(Args a, uint32_t* __res
         st[(UW_CD + 2) * N + u] = __float_as_uint(d.z);
     }
 }
+__global__ __launch_bounds__(256) void init_pixel_states(Args a, uint32_t* __restrict__ st)
+{
+    init_pixel_states_body<false>(a, st);
+}
 
 // The unit set-up of an adaptive pass (pt_accum_add once a pixel is frozen): one lane per entry u of the active
 // list, unit u = the whole pixel of slot q = list[u] -- the words init_pixel_states writes for a whole-pixel
 // accumulating unit, whose UW_TQ names the slot: the row (stride npix, the shard's slot count) the integration
 // kernels load the unit's mean from and store its mean and stream to.  nunits = nwhole = the list's length.
-__global__ __launch_bounds__(256) void init_active_states(Args a, uint32_t* __restrict__ st, const uint32_t* __restrict__ list)
+template <bool kJit>
+__device__ __forceinline__ void init_active_states_body(const Args& a, uint32_t* __restrict__ st, const uint32_t* __restrict__ list)
 {
     const uint32_t u = blockIdx.x * 256u + threadIdx.x;
     if (blockIdx.x == 0) reset_render_counters(a);
@@ -987,7 +1071,7 @@ __global__ __launch_bounds__(256) void init_active_states(Args a, uint32_t* __re
     const uint32_t idx = morton2(px, py);
     Rng r;
     slot_stream(a, q, idx, a.acc_n0, r);
-    const bool lens = (idx == 0) || (a.cam.radius != 0.0f);
+    const bool lens = kJit || (idx == 0) || (a.cam.radius != 0.0f);   // (kJit: every unit's rays are formed per sample)
     const V3 d = pinhole_dir(a, px, py, lens);
     st[u] = r.v0;
     st[N + u] = r.v1;
@@ -1002,6 +1086,10 @@ __global__ __launch_bounds__(256) void init_active_states(Args a, uint32_t* __re
     st[UW_CD * N + u] = __float_as_uint(d.x);
     st[(UW_CD + 1) * N + u] = __float_as_uint(d.y);
     st[(UW_CD + 2) * N + u] = __float_as_uint(d.z);
+}
+__global__ __launch_bounds__(256) void init_active_states(Args a, uint32_t* __restrict__ st, const uint32_t* __restrict__ list)
+{
+    init_active_states_body<false>(a, st, list);
 }
 
 // The per-render table of init_pixel_states: curand_init(seed, s0, 0) for the 256 low bytes s0.
@@ -1286,7 +1374,10 @@ __device__ __forceinline__ void finish_pixel(const Args& a, uint32_t slot, uint3
 // pixel's unit stores its mean.  Sample numbers, and so the divisors of the mean, continue from acc_n0.
 // kView: the lens units' camera ray goes through the view (camera_ray_view); the host launches these instances
 // for an oriented render, so the plain ones compile exactly as they did without the view.
-template <bool kCount, bool kAccum, bool kView = false>
+// kJit: a jittered render (PT_FLAG_JITTER; instances of their own for the same reason).  Every unit arrives as a lens
+// unit (CF_LENS: the ray is formed per sample, so no CF_CAMC and no memo of any kind); a sample draws its film point
+// first, then the lens pair if its pixel is a lens pixel (lens_pixel), and takes the view under a.oriented.
+template <bool kCount, bool kAccum, bool kView = false, bool kJit = false>
 __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, int lane, uint32_t& state, V3& ro, V3& rd,
                                            int32_t& htri, float& ht, W4& w, const Stack4& S,
                                            unsigned long long* lcnt, const uint32_t* lprobe, uint32_t* done_rel,
@@ -1344,11 +1435,19 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
         wgt = c3(1, 1, 1);
         float u1 = 0.0f, u2 = 0.0f;
         const bool lens = (fl & CF_LENS) != 0u;
-        if (lens) { u1 = rng_uniform(rng); u2 = rng_uniform(rng); }
+        float jx = 0.0f, jy = 0.0f;
+        bool pair = lens;   // the sample draws a lens pair
+        if (kJit) {
+            const float ua = rng_uniform(rng), ub = rng_uniform(rng);
+            jitter_offset(fresh(a.flags), ua, ub, &jx, &jy);
+            pair = lens_pixel(a, px, py);
+        }
+        if (pair) { u1 = rng_uniform(rng); u2 = rng_uniform(rng); }
         SEC(SEC_START);
         if (lens || !(fl & CF_CAMC)) {
             SEC(SEC_CAMERA);
-            if (kView) camera_ray_view(a, px, py, lens, u1, u2, &ro, &rd);
+            if (kJit) camera_ray_jitter(a, px, py, jx, jy, pair, u1, u2, &ro, &rd);
+            else if (kView) camera_ray_view(a, px, py, lens, u1, u2, &ro, &rd);
             else camera_ray(a.cam, px, py, lens, u1, u2, &ro, &rd);
             if (!lens) {   // a pinhole ray is the same for every sample of the pixel
                 R.st(CW_CD, __float_as_uint(rd.x)); R.st(CW_CD + 1, __float_as_uint(rd.y)); R.st(CW_CD + 2, __float_as_uint(rd.z));
@@ -1817,7 +1916,8 @@ __device__ __forceinline__ float head_vis_occluded(float len)
     return (len > 0.04f) ? len - 0.03f : -1.0f;
 }
 
-template <bool kCount, bool kAccum>
+// (kJit: a jittered render, as shade_lane's: instances of their own)
+template <bool kCount, bool kAccum, bool kJit = false>
 __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint32_t& state, V3& ro, V3& rd,
                                                 int32_t& htri, float& ht, W4& w, const Stack4& S,
                                                 unsigned long long* lcnt, const uint32_t* lprobe, uint32_t* done_rel,
@@ -1866,7 +1966,14 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
         }
         const bool lens = (fl & CF_LENS) != 0u;
         float lu1 = 0.0f, lu2 = 0.0f;
-        if (lens) { lu1 = rng_uniform(rng); lu2 = rng_uniform(rng); }   // drawPixel's cameraRay (kernel.cu:547)
+        float jx = 0.0f, jy = 0.0f;
+        bool pair = lens;   // the sample draws a lens pair
+        if (kJit) {   // the sample's film point: its first two draws (every unit of a jittered render has CF_LENS)
+            const float ua = rng_uniform(rng), ub = rng_uniform(rng);
+            jitter_offset(fresh(a.flags), ua, ub, &jx, &jy);
+            pair = lens_pixel(a, px, py);
+        }
+        if (pair) { lu1 = rng_uniform(rng); lu2 = rng_uniform(rng); }   // drawPixel's cameraRay (kernel.cu:547)
         // light vertex: the area-CDF pick + uniform point (pick_light, kernel.cu:231-262)
         const bool staged = a.num_lights < kLdsLights;
         const DLight* const lt = staged ? llt : a.lights;
@@ -1906,7 +2013,8 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
         R.st4(HW_N0, __float_as_uint(n0.x), __float_as_uint(n0.y), __float_as_uint(n0.z), 0u);
         if (lens) {   // this sample's camera ray (its draws came first)
             V3 co, cd;
-            if (a.oriented) camera_ray_view(a, px, py, true, lu1, lu2, &co, &cd);
+            if (kJit) camera_ray_jitter(a, px, py, jx, jy, pair, lu1, lu2, &co, &cd);
+            else if (a.oriented) camera_ray_view(a, px, py, true, lu1, lu2, &co, &cd);
             else camera_ray(a.cam, px, py, true, lu1, lu2, &co, &cd);
             R.st4(HW_CD, __float_as_uint(cd.x), __float_as_uint(cd.y), __float_as_uint(cd.z), 0u);
             R.st4(HW_CO, __float_as_uint(co.x), __float_as_uint(co.y), __float_as_uint(co.z), 0u);
@@ -2195,7 +2303,7 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
 // The wavefront kernel's body, shared by both integrators (kHead: integrator 1, shade_lane_head).
 // kLdsWalk: walk steps read the staged top from LDS (integrator 1 always; integrator 0 when the LDS
 // top holds the whole tree) instead of issuing every node's loads to memory.
-template <bool kCount, bool kHead, bool kLdsWalk = kHead, bool kAccum = false, bool kView = false>
+template <bool kCount, bool kHead, bool kLdsWalk = kHead, bool kAccum = false, bool kView = false, bool kJit = false>
 __device__ __forceinline__ void wf_main(const Args& a)
 {
     extern __shared__ uint32_t lds_wf[];
@@ -2336,8 +2444,8 @@ __device__ __forceinline__ void wf_main(const Args& a)
         if (kCount) ++shade_slots;
         // (the lane id is recomputed for the shading pass: one VGPR less live across the walk loop)
         if (state != ST_TRACE && state != ST_DONE) {
-            if (kHead) shade_lane_head<kCount, kAccum>(R, (int)__lane_id(), state, ro, rd, htri, ht, w, S, lcnt, lprobe, done_rel, cnt);
-            else shade_lane<kCount, kAccum, kView>(a, R, (int)__lane_id(), state, ro, rd, htri, ht, w, S, lcnt, lprobe, done_rel, cnt);
+            if (kHead) shade_lane_head<kCount, kAccum, kJit>(R, (int)__lane_id(), state, ro, rd, htri, ht, w, S, lcnt, lprobe, done_rel, cnt);
+            else shade_lane<kCount, kAccum, kView, kJit>(a, R, (int)__lane_id(), state, ro, rd, htri, ht, w, S, lcnt, lprobe, done_rel, cnt);
         }
         if (kCount) shade_clk += clock64() - clk0;
         if (__ballot(state != ST_DONE) == 0ull) break;
@@ -2534,7 +2642,9 @@ __global__ __launch_bounds__(256) void trace_rays(Args a, const float* __restric
 // One lane per work slot, in the wavefront kernels' slot order (unit_pixel: a wave = one 8x8 block, so
 // its rays are coherent); slots outside the image write nothing.
 // (kView: the oriented pinhole ray; primary_features_view is the kernel of a render with a view)
-template <bool kView>
+// (kJit: the guide buffers of a jittered render, primary_features_jitter: the ray through the footprint's centre,
+// jx = jy = 0.5, box and tent alike, so that they sit under the image they guide)
+template <bool kView, bool kJit = false>
 __device__ __forceinline__ void primary_features_body(const Args& a, float4* __restrict__ out)
 {
     extern __shared__ uint32_t lds_tr[];
@@ -2552,7 +2662,8 @@ __device__ __forceinline__ void primary_features_body(const Args& a, float4* __r
         uint32_t px, py;
         if (!unit_pixel(a, q, &px, &py)) continue;
         V3 o, d;
-        if (kView) camera_ray_view<false>(a, px, py, false, 0.0f, 0.0f, &o, &d);
+        if (kJit) camera_ray_jitter<false>(a, px, py, 0.5f, 0.5f, false, 0.0f, 0.0f, &o, &d);
+        else if (kView) camera_ray_view<false>(a, px, py, false, 0.0f, 0.0f, &o, &d);
         else camera_ray<false>(a.cam, px, py, false, 0.0f, 0.0f, &o, &d);
         int32_t htri = -1;
         float ht = kMaxFloat;
@@ -2605,6 +2716,43 @@ __global__ __launch_bounds__(256) void primary_features(Args a, float4* __restri
 __global__ __launch_bounds__(256) void primary_features_view(Args a, float4* __restrict__ out)
 {
     primary_features_body<true>(a, out);
+}
+
+// ------------------------------------------------------------------ sub-pixel jitter (PT_FLAG_JITTER)
+// The kernels of a jittered render: twins of the set-up kernels, of every wavefront instance of both integrators and
+// of the features kernel (render_tiles_jitter stands with render_tiles), defined and first used after every existing
+// instance, so that a render without the flag runs the kernels it always ran, compiled as they always were
+// (DESIGN.md 3.15).  One set serves both cameras: the view is a wave-uniform branch inside them.
+__global__ __launch_bounds__(256) void init_pixel_states_jitter(Args a, uint32_t* __restrict__ st)
+{
+    init_pixel_states_body<true>(a, st);
+}
+__global__ __launch_bounds__(256) void init_active_states_jitter(Args a, uint32_t* __restrict__ st, const uint32_t* __restrict__ list)
+{
+    init_active_states_body<true>(a, st, list);
+}
+template <bool kCount, int kMinWaves, bool kLdsWalk = false>
+__global__ __launch_bounds__(256, kMinWaves) void render_unidir_jitter_wf(Args a)
+{
+    wf_main<kCount, false, kLdsWalk, false, false, true>(a);
+}
+template <bool kLdsWalk>
+__global__ __launch_bounds__(256, 5) void render_unidir_accum_jitter_wf(Args a)
+{
+    wf_main<false, false, kLdsWalk, true, false, true>(a);
+}
+template <bool kCount, int kMinWaves>
+__global__ __launch_bounds__(256, kMinWaves) void render_head_jitter_wf(Args a)
+{
+    wf_main<kCount, true, true, false, false, true>(a);
+}
+__global__ __launch_bounds__(256, 5) void render_head_accum_jitter_wf(Args a)
+{
+    wf_main<false, true, true, true, false, true>(a);
+}
+__global__ __launch_bounds__(256) void primary_features_jitter(Args a, float4* __restrict__ out)
+{
+    primary_features_body<false, true>(a, out);
 }
 
 }  // namespace

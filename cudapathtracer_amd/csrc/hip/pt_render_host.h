@@ -444,7 +444,8 @@ struct LaneTiming {
 }  // namespace
 
 // The integration kernel of a wavefront render: the instance pt::wavefront_variant names.  An oriented render
-// (b.oriented) of integrator 0 takes that instance's view twin; integrator 1's instances serve both.
+// (b.oriented) of integrator 0 takes that instance's view twin; integrator 1's instances serve both.  A jittered
+// render (PT_FLAG_JITTER) takes the instance's jitter twin, which serves both cameras.
 static int launch_wavefront(const pt::WavefrontVariant& v, const WavefrontLaunch& L, hipStream_t stream, const Args& b)
 {
     constexpr auto code = [](bool head, bool count, int min_waves, bool lds_walk, bool accum) {
@@ -485,6 +486,26 @@ static int launch_wavefront(const pt::WavefrontVariant& v, const WavefrontLaunch
                             v.count, v.min_waves, v.lds_walk, v.accum);
         }
     }
+    if (b.flags & PT_FLAG_JITTER) {   // (the jitter twins: below every other instance, for the same reason)
+        switch (v.code()) {
+        case code(true, false, 5, false, true): kernel = render_head_accum_jitter_wf; break;
+        case code(false, false, 5, true, true): kernel = render_unidir_accum_jitter_wf<true>; break;
+        case code(false, false, 5, false, true): kernel = render_unidir_accum_jitter_wf<false>; break;
+        case code(true, true, 5, false, false): kernel = render_head_jitter_wf<true, 5>; break;
+        case code(true, false, 4, false, false): kernel = render_head_jitter_wf<false, 4>; break;
+        case code(true, false, 5, false, false): kernel = render_head_jitter_wf<false, 5>; break;
+        case code(false, true, 4, false, false): kernel = render_unidir_jitter_wf<true, 4>; break;
+        case code(false, true, 5, true, false): kernel = render_unidir_jitter_wf<true, 5, true>; break;
+        case code(false, true, 5, false, false): kernel = render_unidir_jitter_wf<true, 5>; break;
+        case code(false, false, 6, false, false): kernel = render_unidir_jitter_wf<false, 6>; break;
+        case code(false, false, 5, true, false): kernel = render_unidir_jitter_wf<false, 5, true>; break;
+        case code(false, false, 5, false, false): kernel = render_unidir_jitter_wf<false, 5>; break;
+        case code(false, false, 4, false, false): kernel = render_unidir_jitter_wf<false, 4>; break;
+        default:
+            return pt::fail(PT_E_INVALID, "pt_render: no jittered wavefront kernel instance for head %d count %d waves %d lds %d accum %d",
+                            v.head, v.count, v.min_waves, v.lds_walk, v.accum);
+        }
+    }
     hipLaunchKernelGGL(kernel, dim3(L.blocks), dim3(256), L.lds, stream, b);
     HIP_TRY(hipGetLastError());
     return PT_OK;
@@ -504,7 +525,9 @@ static int launch_tiles(const pt_ctx* c, const pt_params* p, pt_ctx::Bufs& B, si
     // (the instances in this order: the order of first use is the order the compiler emits them in)
 #define PT_LAUNCH(I, R, C) hipLaunchKernelGGL((render_tiles<I, R, C>), dim3(grid), dim3(64), lds, stream, a)
 #define PT_LAUNCH_VIEW(I, R, C) hipLaunchKernelGGL((render_tiles_view<I, R, C>), dim3(grid), dim3(64), lds, stream, a)
-    if (!a.oriented) {
+#define PT_LAUNCH_JITTER(I, R, C) hipLaunchKernelGGL((render_tiles_jitter<I, R, C>), dim3(grid), dim3(64), lds, stream, a)
+    const bool jitter = (p->flags & PT_FLAG_JITTER) != 0;
+    if (!a.oriented && !jitter) {
     if (p->integrator == PT_INTEGRATOR_HEAD) {
         if (refwalk) { if (count) PT_LAUNCH(1, true, true); else PT_LAUNCH(1, true, false); }
         else { if (count) PT_LAUNCH(1, false, true); else PT_LAUNCH(1, false, false); }
@@ -512,13 +535,20 @@ static int launch_tiles(const pt_ctx* c, const pt_params* p, pt_ctx::Bufs& B, si
         if (refwalk) { if (count) PT_LAUNCH(0, true, true); else PT_LAUNCH(0, true, false); }
         else { if (count) PT_LAUNCH(0, false, true); else PT_LAUNCH(0, false, false); }
     }
-    } else if (p->integrator == PT_INTEGRATOR_HEAD) {   // (the view's instances: after every plain one)
+    } else if (!jitter && p->integrator == PT_INTEGRATOR_HEAD) {   // (the view's instances: after every plain one)
         if (refwalk) { if (count) PT_LAUNCH_VIEW(1, true, true); else PT_LAUNCH_VIEW(1, true, false); }
         else { if (count) PT_LAUNCH_VIEW(1, false, true); else PT_LAUNCH_VIEW(1, false, false); }
-    } else {
+    } else if (!jitter) {
         if (refwalk) { if (count) PT_LAUNCH_VIEW(0, true, true); else PT_LAUNCH_VIEW(0, true, false); }
         else { if (count) PT_LAUNCH_VIEW(0, false, true); else PT_LAUNCH_VIEW(0, false, false); }
+    } else if (p->integrator == PT_INTEGRATOR_HEAD) {   // (the jittered instances, either camera: after every other one)
+        if (refwalk) { if (count) PT_LAUNCH_JITTER(1, true, true); else PT_LAUNCH_JITTER(1, true, false); }
+        else { if (count) PT_LAUNCH_JITTER(1, false, true); else PT_LAUNCH_JITTER(1, false, false); }
+    } else {
+        if (refwalk) { if (count) PT_LAUNCH_JITTER(0, true, true); else PT_LAUNCH_JITTER(0, true, false); }
+        else { if (count) PT_LAUNCH_JITTER(0, false, true); else PT_LAUNCH_JITTER(0, false, false); }
     }
+#undef PT_LAUNCH_JITTER
 #undef PT_LAUNCH_VIEW
 #undef PT_LAUNCH
     HIP_TRY(hipGetLastError());
@@ -547,10 +577,13 @@ static int enqueue_wavefront(pt_ctx* c, const pt_params* p, const pt::AccumPass*
         b.jump_bytes = c->jump_bytes;
         b.seed_states = B.seed_states;
     }
+    const bool jitter = (b.flags & PT_FLAG_JITTER) != 0;   // (its set-up kernels mark every unit "ray formed per sample")
     if (acc && acc->active)
-        hipLaunchKernelGGL(init_active_states, dim3((b.nunits + 255) / 256), dim3(256), 0, stream, b, B.pix_states, acc->active);
+        hipLaunchKernelGGL(jitter ? init_active_states_jitter : init_active_states, dim3((b.nunits + 255) / 256), dim3(256), 0,
+                           stream, b, B.pix_states, acc->active);
     else
-        hipLaunchKernelGGL(init_pixel_states, dim3((b.npix + 255) / 256), dim3(256), 0, stream, b, B.pix_states);
+        hipLaunchKernelGGL(jitter ? init_pixel_states_jitter : init_pixel_states, dim3((b.npix + 255) / 256), dim3(256), 0, stream,
+                           b, B.pix_states);
     // A render queued on another stream while one is in flight: its seeding pre-pass runs beside the
     // earlier render's last waves (its own buffers), but the integration kernel waits until the earlier
     // render is complete (finalisation included), so a persistent grid never takes the CU slots an
@@ -757,9 +790,9 @@ int pt::accum_check(const pt_ctx* c, const pt_params* p, const pt_camera* cam, c
     if (view)
         if (int rc = validate_view("pt_accum_create", view)) return rc;
     const RenderKnobs& K = c->knobs;
-    if (p->flags & ~(uint32_t)(PT_FLAG_NO_DEAD_PATH_SKIP | PT_FLAG_NO_PRIMARY_CACHE))
-        return pt::fail(PT_E_INVALID, "pt_accum_create: flags 0x%x: only PT_FLAG_NO_DEAD_PATH_SKIP and PT_FLAG_NO_PRIMARY_CACHE "
-                        "accumulate (the reference walks and the counting variants have no accumulating kernel)", p->flags);
+    if (p->flags & ~(uint32_t)(PT_FLAG_NO_DEAD_PATH_SKIP | PT_FLAG_NO_PRIMARY_CACHE | PT_FLAG_JITTER | PT_FLAG_JITTER_TENT))
+        return pt::fail(PT_E_INVALID, "pt_accum_create: flags 0x%x: only PT_FLAG_NO_DEAD_PATH_SKIP, PT_FLAG_NO_PRIMARY_CACHE and "
+                        "the jitter flags accumulate (the reference walks and the counting variants have no accumulating kernel)", p->flags);
     if (!takes_wavefront(p, cam, c->scene_extent, K.head_wf))
         return pt::fail(PT_E_INVALID, "pt_accum_create: this render would take the tile kernel (%s), which does not accumulate",
                         (p->integrator == PT_INTEGRATOR_HEAD && !K.head_wf) ? "integrator 1 with PT_HEAD_WF=0"
@@ -938,7 +971,9 @@ static int features_check(const pt_ctx* c, const pt_params* p, const pt_camera* 
     if (c->fl_n > 0)
         return pt::fail(PT_E_INVALID, "pt_render_features: %d asynchronous renders in flight (pt_render_wait first)", c->fl_n);
     *vp = *p;
-    vp->spp = 0; vp->bounces = 1; vp->integrator = PT_INTEGRATOR_UNIDIR; vp->flags = 0; vp->seed = 0;
+    // (of the flags only the jitter bits matter: PT_FLAG_JITTER moves the ray to the footprint's centre)
+    vp->spp = 0; vp->bounces = 1; vp->integrator = PT_INTEGRATOR_UNIDIR; vp->seed = 0;
+    vp->flags = p->flags & (PT_FLAG_JITTER | PT_FLAG_JITTER_TENT);
     if (int rc = pt::validate_render(vp, cam)) return rc;
     if (view)
         if (int rc = pt::validate_view("pt_render_features", view)) return rc;
@@ -979,7 +1014,9 @@ extern "C" int pt_render_features_view_device(pt_ctx* c, const pt_params* p_in, 
     if (int rc = pt::grow(&c->rb[0].spill, &c->rb[0].spill_words, stack_words_per_lane(c) * (size_t)blocks * 256)) return rc;
     a.spill = c->rb[0].spill;
     a.spill_stride = blocks * 256;
-    hipLaunchKernelGGL(a.oriented ? primary_features_view : primary_features, dim3(blocks), dim3(256), lds, stream, a,
+    a.flags = p->flags;
+    hipLaunchKernelGGL((p->flags & PT_FLAG_JITTER) ? primary_features_jitter : a.oriented ? primary_features_view : primary_features,
+                       dim3(blocks), dim3(256), lds, stream, a,
                        reinterpret_cast<float4*>(d_feat));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));

@@ -29,6 +29,10 @@ void clear_error();
 // `who`'s name otherwise (scene.cpp).
 int validate_view(const char* who, const pt_view* v);
 
+// The jitter bits of pt_params.flags (pt.h): PT_FLAG_JITTER_TENT only together with PT_FLAG_JITTER; PT_E_INVALID under
+// `who`'s name otherwise (scene.cpp).
+int validate_jitter_flags(const char* who, uint32_t flags);
+
 // The HIP device ordinal a render context lives on (pt_render_host.h; used by pt_multi.cpp).
 int ctx_device(const pt_ctx* c);
 

@@ -68,6 +68,7 @@ int validate_render(const pt_params* p, const pt_camera* cam)
     if (p->width <= 0 || p->height <= 0 || p->width > 65535 || p->height > 65535)
         return fail(PT_E_INVALID, "pt_render: image size %dx%d out of range (1..65535)", p->width, p->height);
     if (p->spp < 0) return fail(PT_E_INVALID, "pt_render: spp < 0");
+    if (int rc = validate_jitter_flags("pt_render", p->flags)) return rc;
     if (p->integrator != PT_INTEGRATOR_UNIDIR && p->integrator != PT_INTEGRATOR_HEAD)
         return fail(PT_E_INVALID, "pt_render: unknown integrator %d", p->integrator);
     if (p->integrator == PT_INTEGRATOR_UNIDIR && (p->bounces < 1 || p->bounces > 64))

@@ -51,6 +51,13 @@ void clear_error() { g_error.clear(); }
 
 const char* last_error_cstr() { return g_error.c_str(); }
 
+int validate_jitter_flags(const char* who, uint32_t flags)
+{
+    if ((flags & PT_FLAG_JITTER_TENT) && !(flags & PT_FLAG_JITTER))
+        return fail(PT_E_INVALID, "%s: flags 0x%x: PT_FLAG_JITTER_TENT needs PT_FLAG_JITTER (the tent is a kind of jitter)", who, flags);
+    return PT_OK;
+}
+
 // The condition of pt.h: 11 finite floats, a film > 0, an orthonormal basis to 1e-3 (in double).
 int validate_view(const char* who, const pt_view* v)
 {
@@ -316,6 +323,63 @@ void pt_camera_ray_view(const pt_camera* cam, const pt_view* view, uint32_t idx,
     const float k = -cam->focal_length;
     film = v3(film.x * k / cam->dist_from_film, film.y * k / cam->dist_from_film, film.z * k / cam->dist_from_film);
     const pt_vec3 c = vsub(film, lo);
+    const float* R = view->right;
+    const float* U = view->up;
+    const float* B = view->back;
+    const pt_vec3 w = v3((R[0] * c.x + U[0] * c.y) + B[0] * c.z, (R[1] * c.x + U[1] * c.y) + B[1] * c.z,
+                         (R[2] * c.x + U[2] * c.y) + B[2] * c.z);
+    *dir = vunit(w);
+    if (lens)
+        *origin = v3((R[0] * lo.x + U[0] * lo.y) + cam->pos.x, (R[1] * lo.x + U[1] * lo.y) + cam->pos.y,
+                     (R[2] * lo.x + U[2] * lo.y) + cam->pos.z);
+    else
+        *origin = v3(0.0f + cam->pos.x, 0.0f + cam->pos.y, 0.0f + cam->pos.z);
+}
+
+// ---- sub-pixel jitter (PT_FLAG_JITTER, pt.h): the host's copies of the device functions
+static float jitter_tent(float u)
+{
+    return (u < 0.5f) ? sqrtf(2.0f * u) - 1.0f : 1.0f - sqrtf(2.0f - 2.0f * u);
+}
+
+int pt_jitter_offset(uint32_t flags, float ua, float ub, float* jx, float* jy)
+{
+    pt::clear_error();
+    if (!jx || !jy) return pt::fail(PT_E_INVALID, "pt_jitter_offset: null argument");
+    if (int rc = pt::validate_jitter_flags("pt_jitter_offset", flags)) return rc;
+    if (!(flags & PT_FLAG_JITTER)) { *jx = 0.0f; *jy = 0.0f; }
+    else if (flags & PT_FLAG_JITTER_TENT) { *jx = 0.5f + jitter_tent(ua); *jy = 0.5f + jitter_tent(ub); }
+    else { *jx = ua; *jy = ub; }
+    return PT_OK;
+}
+
+// pt_camera_ray / pt_camera_ray_view with (px + jx, py + jy) in the places of (px, py), one rounded f32 operation at a
+// time; zero offsets give their bits ((float)px + 0.0f is (float)px).
+void pt_camera_ray_jitter(const pt_camera* cam, const pt_view* view, uint32_t idx, float jx, float jy, int lens, float u1, float u2,
+                          pt_vec3* origin, pt_vec3* dir)
+{
+    uint32_t px, py;
+    pt_morton_i_to_pxl(idx, &px, &py);
+    const float sx = static_cast<float>(px) + jx, sy = static_cast<float>(py) + jy;
+    pt_vec3 film = v3(sx / static_cast<float>(cam->pxl_width) - 0.5f, sy / static_cast<float>(cam->pxl_height) - 0.5f,
+                      cam->dist_from_film);
+    if (view) film = v3(film.x * view->film_w, film.y * view->film_h, film.z);
+    pt_vec3 lo = v3(0.0f, 0.0f, 0.0f);
+    if (lens) {
+        float r = cam->radius * sqrtf(u1);
+        float theta = static_cast<float>(2 * 3.14159 * static_cast<double>(u2));
+        float sn, cs;
+        pt::sincos_det(theta, &sn, &cs);
+        lo = v3(r * cs, r * sn, 0.0f);
+    }
+    const float k = -cam->focal_length;
+    film = v3(film.x * k / cam->dist_from_film, film.y * k / cam->dist_from_film, film.z * k / cam->dist_from_film);
+    const pt_vec3 c = vsub(film, lo);
+    if (!view) {
+        *origin = v3(lo.x + cam->pos.x, lo.y + cam->pos.y, lo.z + cam->pos.z);
+        *dir = vunit(c);
+        return;
+    }
     const float* R = view->right;
     const float* U = view->up;
     const float* B = view->back;

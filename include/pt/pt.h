@@ -212,6 +212,58 @@ typedef struct pt_ctx pt_ctx;
 #define PT_FLAG_TRI_COUNTS 0x20u          /* with PT_FLAG_COUNT: also the per-triangle test counts of
                                              kernel.cu:133 (read back with pt_tri_counts; one atomic
                                              per triangle test)                                      */
+#define PT_FLAG_JITTER 0x40u               /* sub-pixel jitter: every sample's camera ray goes through its own
+                                             point of the pixel's footprint (box filter); see below    */
+#define PT_FLAG_JITTER_TENT 0x80u          /* with PT_FLAG_JITTER only: the point is drawn from the tent of
+                                             half-width 1 pixel about the footprint's centre             */
+
+/* ------------------------------------------------- sub-pixel jitter (no counterpart in the reference)
+ * Without PT_FLAG_JITTER every camera ray goes through its pixel's lower corner (px/W, py/H), as the reference's do:
+ * a pinhole render is not anti-aliased however many samples it takes.  With it every sample draws a point of the
+ * film first.  All f32, every operation rounded on its own, no contraction, IEEE division and square root:
+ *
+ *   per sample, before anything else of the sample:  ua = curand_uniform, ub = curand_uniform
+ *   box :  jx = ua                      jy = ub
+ *   tent:  t(u) = u < 0.5f ? sqrt(2.0f*u) - 1.0f : 1.0f - sqrt(2.0f - 2.0f*u)        (PT_FLAG_JITTER_TENT)
+ *          jx = 0.5f + t(ua)            jy = 0.5f + t(ub)
+ *   sx = (float)px + jx                 sy = (float)py + jy
+ *
+ * and the ray is the unjittered one with sx, sy in the places of (float)px, (float)py:
+ *   NULL view (pt_camera_ray's arithmetic):
+ *     film = (sx/(float)W - 0.5f, sy/(float)H - 0.5f, dist)
+ *     film = (film * -focal)/dist
+ *     o    = lo + pos
+ *     d    = normalized(film - lo)
+ *   with a view: the block under "the oriented camera" above, f = ((sx/(float)W - 0.5f) * film_w, ...), unchanged
+ *   otherwise.
+ * The tent is sampled by inverting its CDF (filter importance sampling): each sample still belongs to exactly one
+ * pixel and has weight 1, so pixels stay independent -- frozen pixels, per-pixel counts and "a pixel with n samples
+ * holds the n-sample value" hold as before.
+ *
+ * Draw order of a sample: ua, ub; then the lens pair u1, u2 if the pixel is a lens pixel (radius != 0 or Morton index
+ * 0, unchanged); then the integrator's draws.  Without the flag nothing is drawn and nothing is added: the code and
+ * the bits are what they were.  PT_FLAG_JITTER_TENT without PT_FLAG_JITTER is PT_E_INVALID from every entry point
+ * that validates params.
+ *
+ * Consequences:
+ *   - A jittered pixel has no sample-invariant camera ray, so the primary-hit memo, the memo the chunks of a split
+ *     pixel share and the tile kernel's memo are off, as if PT_FLAG_NO_PRIMARY_CACHE were set (that flag stays legal
+ *     and changes nothing).  pt_stats.rays_reference keeps its meaning.
+ *   - pt_render_features*: with PT_FLAG_JITTER in params->flags the feature ray goes through the footprint's centre,
+ *     jx = jy = 0.5f in the arithmetic above, box and tent alike, so the guide buffers sit under the image they guide
+ *     and not half a pixel off.  Without the flag the ray is the corner ray, as before (no other flag is looked at).
+ *   - Everything that takes pt_params takes the two flags: pt_render*, _device, _async; pt_render_group / _multi;
+ *     pt_accum_create*; pt_accum_save / _load and pt_session_save / _load through the stored params (the file
+ *     formats do not change); all of these with a view as well.
+ *
+ * Host helpers (no device; the host's copies of the device functions, as pt_camera_ray_view is):
+ *   pt_jitter_offset      (jx, jy) of the draws (ua, ub) for `flags` (only the two jitter bits are looked at):
+ *                         (0, 0) without PT_FLAG_JITTER; PT_E_INVALID for PT_FLAG_JITTER_TENT alone or a null out.
+ *   pt_camera_ray_jitter  the ray of pixel `idx` (Morton) through (px + jx, py + jy); jx = jy = 0 is
+ *                         pt_camera_ray_view exactly (with a NULL view, the signs of zeros included). */
+int pt_jitter_offset(uint32_t flags, float ua, float ub, float* jx, float* jy);
+void pt_camera_ray_jitter(const pt_camera* cam, const pt_view* view /* NULL ok */, uint32_t idx, float jx, float jy,
+                          int lens, float u1, float u2, pt_vec3* origin, pt_vec3* dir);
 
 typedef struct {
     int32_t width, height;   /* image size (IMAGE_WIDTH/HEIGHT, kernel.cu:28-29)                    */
@@ -341,8 +393,8 @@ int pt_render_wait(pt_ctx* ctx, pt_stats* stats);
  *
  * pt_accum_create fixes everything in `params` except spp (ignored) and the camera, validates them
  * as pt_render_device_async does, and allocates the state with 0 samples done.  Accumulation runs on
- * the wavefront kernels only: both integrators, flags drawn from 0, PT_FLAG_NO_DEAD_PATH_SKIP and
- * PT_FLAG_NO_PRIMARY_CACHE.  Whatever would take another kernel is refused here with PT_E_INVALID
+ * the wavefront kernels only: both integrators, flags drawn from 0, PT_FLAG_NO_DEAD_PATH_SKIP,
+ * PT_FLAG_NO_PRIMARY_CACHE, PT_FLAG_JITTER and PT_FLAG_JITTER_TENT.  Whatever would take another kernel is refused here with PT_E_INVALID
  * (never a silent fall-back): PT_FLAG_REFERENCE_TRAVERSAL, PT_FLAG_REFERENCE_BVH, PT_FLAG_COUNT, a
  * camera farther than 64 scene extents from the origin, integrator 1 with PT_HEAD_WF=0, a
  * non-default PT_WF_MIN_WAVES / PT_HEAD_MIN_WAVES.  An accumulator belongs to one context (one
@@ -779,6 +831,8 @@ void pt_denoise_defaults(pt_denoise_params* p);   /* {5, 5, 0.02f, 0.0f, 0} */
 int pt_render_features_device(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, pt_feature* d_feat, void* stream);
 int pt_render_features(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, pt_feature* feat /* host */);
 /* With a view the ray is pt_camera_ray_view(cam, view, ..., lens = 0, ...): the oriented pinhole ray. */
+/* With PT_FLAG_JITTER in params->flags: pt_camera_ray_jitter(cam, view, ..., 0.5f, 0.5f, lens = 0, ...), the ray
+ * through the centre of the pixel's footprint (params->flags is otherwise ignored here). */
 int pt_render_features_view_device(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, const pt_view* view,
                                    pt_feature* d_feat, void* stream);
 int pt_render_features_view(pt_ctx* ctx, const pt_params* params, const pt_camera* cam, const pt_view* view,
