@@ -105,6 +105,10 @@ class DenoiseGuidedParams(C.Structure):
     _fields_ = [("base", DenoiseParams), ("sigma_luma", C.c_float)]
 
 
+class TemporalParams(C.Structure):   # pt_temporal_params, 16 B
+    _fields_ = [("max_history", C.c_int32), ("normal_min", C.c_float), ("plane_tol", C.c_float), ("flags", C.c_uint32)]
+
+
 class NoiseParams(C.Structure):
     _fields_ = [("tol", C.c_float), ("y_floor", C.c_float)]
 
@@ -258,6 +262,17 @@ SIGNATURES = {
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pt_denoise_guided": (C.c_int, [C.c_void_p, C.POINTER(DenoiseGuidedParams), C.c_int, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_project_view": (C.c_int, [C.POINTER(Camera), C.POINTER(View), Vec3, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "pt_temporal_defaults": (None, [C.POINTER(TemporalParams)]),
+    "pt_temporal_create": (C.c_void_p, [C.c_void_p, C.POINTER(TemporalParams), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "pt_temporal_push_device": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(View), C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_temporal_push": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(View), C.c_uint32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    "pt_temporal_length": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pt_temporal_frames": (C.c_int, [C.c_void_p]),
+    "pt_temporal_reset": (C.c_int, [C.c_void_p]),
+    "pt_temporal_destroy": (None, [C.c_void_p]),
     "pt_destroy": (None, [C.c_void_p]),
 }
 

@@ -215,6 +215,24 @@ def camera_ray(cam, idx, lens=False, u1=0.0, u2=0.0, view=None, jitter=None):
     return (o.x, o.y, o.z), (d.x, d.y, d.z)
 
 
+def project(cam, P, view=None):
+    """(front, sx, sy): the continuous pixel coordinates at which the pinhole ray of `cam` / `view` passes through the
+    world point P (pt_project_view, the inverse of camera_ray with lens=False); front is False for a point that is
+    not in front of the camera (sx, sy are then unspecified)."""
+    sx, sy = C.c_float(), C.c_float()
+    rc = L.lib().pt_project_view(C.byref(cam), _view_ref(view), L.Vec3(*[float(c) for c in P]), C.byref(sx), C.byref(sy))
+    if rc < 0:
+        L.check(rc)
+    return bool(rc), sx.value, sy.value
+
+
+def temporal_defaults():
+    """pt_temporal_defaults as a dict (max_history, normal_min, plane_tol, flags)."""
+    tp = L.TemporalParams()
+    L.lib().pt_temporal_defaults(C.byref(tp))
+    return {k: getattr(tp, k) for k, _ in tp._fields_}
+
+
 def morton_pxl_to_i(x, y):
     return int(L.lib().pt_morton_pxl_to_i(int(x), int(y)))
 
@@ -490,6 +508,18 @@ class Renderer:
                                                  C.c_void_p(int(d_in_ptr)), C.c_void_p(int(d_feat_ptr)),
                                                  C.c_void_p(int(d_var_ptr)), C.c_void_p(int(d_out_ptr)),
                                                  None if stream_ptr is None else C.c_void_p(int(stream_ptr))))
+
+    def temporal(self, width, height, max_history=32, normal_min=0.9, plane_tol=0.02, pixel_order=0):
+        """A temporal history for width x height images (pt_temporal_create): Temporal.push(img, features, cam, view)
+        reprojects what it holds through the previous push's camera and accumulates the new frame into it, so the
+        samples survive a camera move.  Close it before its renderer."""
+        tp = L.TemporalParams()
+        tp.max_history, tp.normal_min, tp.plane_tol, tp.flags = int(max_history), float(normal_min), float(plane_tol), 0
+        err = C.c_int(0)
+        h = L.lib().pt_temporal_create(self._h, C.byref(tp), int(width), int(height), int(pixel_order), C.byref(err))
+        if not h:
+            L.check(err.value if err.value != 0 else L.PT_E_HIP)
+        return Temporal(self, h, int(width), int(height), int(pixel_order))
 
     def tonemap(self, img):
         """Output step on the GPU: (H, W, 3) float32 mean image -> int32 codes equal to
@@ -783,6 +813,76 @@ class NoiseEstimate:
         """variance() into a device buffer of W*H float32; pixels outside the shard are left untouched."""
         L.check(L.lib().pt_noise_variance_device(self._h, C.c_void_p(int(d_var_ptr)),
                                                  None if stream_ptr is None else C.c_void_p(int(stream_ptr))))
+
+
+class Temporal:
+    """A temporal history of the image on the renderer's device (pt_temporal_*): every push reprojects it through the
+    previous push's camera, folds the new frame in and returns the accumulated image with the variance of each pixel's
+    mean luminance (inf = unknown), which Renderer.denoise_guided takes as it stands."""
+
+    def __init__(self, renderer, handle, width, height, pixel_order):
+        self._renderer = renderer   # (keeps the context alive as long as the history)
+        self._h = handle
+        self.width, self.height, self.pixel_order = width, height, pixel_order
+
+    def close(self):
+        if self._h:
+            L.lib().pt_temporal_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _shape(self):
+        return (self.height * self.width,) if self.pixel_order == L.PT_ORDER_MORTON else (self.height, self.width)
+
+    def push(self, img, features, cam, view=None, flags=0):
+        """(out, var) of the frame `img` with its `features` (features() through the same cam, view and flags), both
+        in the history's pixel order: the accumulated image, shaped like img, and the variance of each pixel's mean
+        luminance (float32, img's shape without the channel axis; inf where fewer than 2 samples are held).  Of
+        `flags` only PT_FLAG_JITTER counts: the features were taken through the pixels' centres."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        feat = np.ascontiguousarray(features, dtype=FEATURE)
+        n = self.width * self.height
+        if feat.size != n or img.size != n * 3:
+            raise ValueError("push: image or features are not %dx%d" % (self.width, self.height))
+        out = np.empty_like(img)
+        var = np.empty(self._shape(), dtype=np.float32)
+        L.check(L.lib().pt_temporal_push(self._h, C.byref(cam), _view_ref(view), int(flags), img.ctypes.data, feat.ctypes.data,
+                                         out.ctypes.data, var.ctypes.data))
+        return out, var
+
+    def push_device(self, d_in_ptr, d_feat_ptr, d_out_ptr, cam, view=None, flags=0, d_var_ptr=None, stream_ptr=None):
+        """pt_temporal_push_device on raw device pointers (d_out_ptr may equal d_in_ptr, d_var_ptr may be None);
+        blocking."""
+        L.check(L.lib().pt_temporal_push_device(self._h, C.byref(cam), _view_ref(view), int(flags), C.c_void_p(int(d_in_ptr)),
+                                                C.c_void_p(int(d_feat_ptr)), C.c_void_p(int(d_out_ptr)),
+                                                None if d_var_ptr is None else C.c_void_p(int(d_var_ptr)),
+                                                None if stream_ptr is None else C.c_void_p(int(stream_ptr))))
+
+    def history_length(self):
+        """The history length n' of every pixel as of the last push, float32 (all 0 before the first)."""
+        out = np.zeros(self._shape(), dtype=np.float32)
+        L.check(L.lib().pt_temporal_length(self._h, out.ctypes.data))
+        return out
+
+    @property
+    def frames(self):
+        """The pushes since the history was created or reset."""
+        return int(L.lib().pt_temporal_frames(self._h))
+
+    def reset(self):
+        """Forget the history: the next push is a first push."""
+        L.check(L.lib().pt_temporal_reset(self._h))
 
 
 class Group:

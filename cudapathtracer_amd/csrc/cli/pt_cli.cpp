@@ -66,6 +66,15 @@
 //                                         With every mode that renders; with --aov the feature rays go through the pixels'
 //                                         centres.  After --resume / --resume-session the flags are the file's, and a
 //                                         --jitter that differs is an error
+// --camera-path FILE --temporal           a moving camera: FILE has one pose per line, "px py pz tx ty tz" (position, target;
+//   [--temporal-max N]                    blank lines and lines starting with # are skipped).  Each line is one frame through
+//                                         pt_view_look_at with --up / --vfov / --film as above, rendered at --spp with seed
+//                                         --seed + frame (frames are independent) and pushed with its feature buffers through
+//                                         a temporal history (pt_temporal_*, history length capped at N, default 32), which
+//                                         reprojects what it holds into every new frame.  The image files hold the last
+//                                         frame's temporal image; --denoise-guided filters it with the temporal variance (no
+//                                         estimator needed), --variance-map writes that variance.  --gpus 1 only; not with the
+//                                         accumulating modes, --look-at or --cam (the poses place and aim the camera)
 // --aov PREFIX                            write the primary-hit feature buffers as PREFIX_albedo.pfm,
 //                                         PREFIX_normal.pfm, PREFIX_position.pfm and PREFIX_depth.pfm (depth
 //                                         replicated to 3 channels)
@@ -101,6 +110,7 @@ struct Obj {
             "              [--checkpoint FILE] [--resume FILE] [--pass-spp K]\n"
             "              [--session FILE] [--resume-session FILE]\n"
             "              [--denoise [ITERS]] [--aov PREFIX]\n"
+            "              [--camera-path FILE --temporal [--temporal-max N]]\n"
             "              [--until-error TOL [--error-quantile Q] [--min-batches B] [--adaptive]] [--error-map FILE.pfm]\n"
             "              [--count-map FILE.pfm] [--denoise-guided [ITERS] [--sigma-luma S]] [--variance-map FILE.pfm]\n"
             "  --until-error TOL  with --pass-spp: stop once the fraction Q (default 0.95) of the pixels has a relative\n"
@@ -118,6 +128,10 @@ struct Obj {
             "                     with square pixels; --film W,H: the film's extent (1,1 = the reference's unit square)\n"
             "  --jitter box|tent  anti-alias: every sample's camera ray through its own point of the pixel's footprint (box), or\n"
             "                     of the tent of half-width 1 pixel about its centre (tent)\n"
+            "  --camera-path FILE --temporal  one frame per line of FILE (px py pz tx ty tz: position, target), each rendered at\n"
+            "                     --spp with seed --seed + frame and pushed through a temporal history (--temporal-max N caps its\n"
+            "                     length, default 32); the files hold the last frame's temporal image; --denoise-guided and\n"
+            "                     --variance-map use the temporal variance\n"
             "  --aov PREFIX       write PREFIX_albedo.pfm, PREFIX_normal.pfm, PREFIX_position.pfm, PREFIX_depth.pfm\n");
     exit(2);
 }
@@ -154,6 +168,34 @@ std::string dir_of(const std::string& p)
     return k == std::string::npos ? std::string("./") : p.substr(0, k + 1);
 }
 
+struct Pose {
+    pt_vec3 pos, target;
+};
+
+// The poses of a --camera-path file; false with a message on stderr.
+bool read_camera_path(const std::string& path, std::vector<Pose>* poses)
+{
+    FILE* f = fopen(path.c_str(), "r");
+    if (!f) { fprintf(stderr, "pt_cli: --camera-path: cannot read %s\n", path.c_str()); return false; }
+    char line[512];
+    for (int no = 1; fgets(line, sizeof line, f); ++no) {
+        const char* c = line;
+        while (*c == ' ' || *c == '\t' || *c == '\r' || *c == '\n') ++c;
+        if (!*c || *c == '#') continue;
+        Pose q;
+        char tail = 0;
+        if (sscanf(c, "%f %f %f %f %f %f %c", &q.pos.x, &q.pos.y, &q.pos.z, &q.target.x, &q.target.y, &q.target.z, &tail) != 6) {
+            fprintf(stderr, "pt_cli: --camera-path: %s line %d is not \"px py pz tx ty tz\"\n", path.c_str(), no);
+            fclose(f);
+            return false;
+        }
+        poses->push_back(q);
+    }
+    fclose(f);
+    if (poses->empty()) { fprintf(stderr, "pt_cli: --camera-path: %s holds no pose\n", path.c_str()); return false; }
+    return true;
+}
+
 int die(const char* what)
 {
     fprintf(stderr, "pt_cli: %s: %s\n", what, pt_last_error());
@@ -183,6 +225,10 @@ int main(int argc, char** argv)
     pt_denoise_guided_defaults(&gparams);
     std::string variance_map;
     std::string aov;
+    std::string camera_path;   // --camera-path FILE --temporal [--temporal-max N]
+    bool temporal = false;
+    pt_temporal_params tparams;
+    pt_temporal_defaults(&tparams);
     bool until_error = false, adaptive = false;
     std::string error_map, count_map;
     pt_converge_params conv{};
@@ -245,6 +291,9 @@ int main(int argc, char** argv)
         else if (a == "--sigma-luma") gparams.sigma_luma = strtof(next().c_str(), nullptr);
         else if (a == "--variance-map") variance_map = next();
         else if (a == "--aov") aov = next();
+        else if (a == "--camera-path") camera_path = next();
+        else if (a == "--temporal") temporal = true;
+        else if (a == "--temporal-max") { tparams.max_history = atoi(next().c_str()); if (tparams.max_history < 1) usage("--temporal-max must be >= 1"); }
         else if (a == "--jitter") {
             const std::string v = next();
             if (v == "box") jitter_flags = PT_FLAG_JITTER;
@@ -284,8 +333,12 @@ int main(int argc, char** argv)
     p.flags |= jitter_flags;
     cam.pxl_width = p.width;
     cam.pxl_height = p.height;
-    const bool estimate = until_error || !error_map.empty() || !variance_map.empty();
-    if (guided && !estimate) usage("--denoise-guided needs an estimator: --until-error TOL with --pass-spp K");
+    if (temporal && camera_path.empty()) usage("--temporal needs --camera-path FILE (the poses of the frames)");
+    if (!camera_path.empty() && !temporal) usage("--camera-path needs --temporal");
+    if (temporal && (until_error || !error_map.empty())) usage("--temporal has no estimator: not with --until-error / --error-map");
+    // (with --temporal the variance map is the history's, and needs no estimator)
+    const bool estimate = !temporal && (until_error || !error_map.empty() || !variance_map.empty());
+    if (guided && !estimate && !temporal) usage("--denoise-guided needs an estimator: --until-error TOL with --pass-spp K");
     if (guided && denoise) usage("--denoise and --denoise-guided: choose one");
     if (!(gparams.sigma_luma > 0.0f) || !std::isfinite(gparams.sigma_luma)) usage("--sigma-luma must be finite and > 0");
     if (estimate && gpus != 1) usage("--until-error / --error-map / --variance-map need --gpus 1 (one estimator per accumulator)");
@@ -305,6 +358,15 @@ int main(int argc, char** argv)
     if (accumulate && gpus != 1)
         usage("--checkpoint / --resume / --session / --resume-session / --pass-spp need --gpus 1 (one accumulator per shard)");
     if (accumulate && (!tri_csv.empty() || ref_walk)) usage("--tri-counts and --reference-walk do not accumulate");
+    std::vector<Pose> poses;
+    if (temporal) {
+        if (accumulate) usage("--temporal renders independent frames: not with --checkpoint / --resume / --session / --resume-session / --pass-spp");
+        if (gpus != 1) usage("--temporal needs --gpus 1 (one history per context)");
+        if (!tri_csv.empty()) usage("--temporal: not with --tri-counts");
+        if (have_target) usage("--temporal: the poses of --camera-path aim the camera, not --look-at");
+        for (const std::string& g : given) if (g == "--cam") usage("--temporal: the poses of --camera-path place the camera, not --cam");
+        if (!read_camera_path(camera_path, &poses)) return 2;
+    }
     const std::string& resumed = resume.empty() ? resume_session : resume;   // the file a render continues, if any
     if (!resumed.empty()) {
         // the file fixes the render; what the command line says as well must say the same
@@ -533,6 +595,42 @@ int main(int argc, char** argv)
         }
         pt_noise_destroy(noise);
         pt_accum_destroy(acc);
+    } else if (temporal) {
+        // one frame per pose: render, features, push; `img` and `var` end as the last frame's temporal image and variance
+        int err = 0;
+        pt_temporal* hist = pt_temporal_create(ctx[0], &tparams, p.width, p.height, p.pixel_order, &err);
+        if (!hist) return die("pt_temporal_create");
+        const size_t npix = (size_t)p.width * p.height;
+        std::vector<float> frame(n);
+        feat.resize(npix);
+        var.resize(npix);
+        for (size_t k = 0; k < poses.size(); ++k) {
+            cam.pos = poses[k].pos;
+            if (pt_view_look_at(cam.pos, poses[k].target, up, &view_store) != PT_OK) return die("--camera-path");
+            if (have_vfov && pt_view_set_fov(&view_store, &cam, vfov, p.width, p.height) != PT_OK) return die("--vfov");
+            if (have_film) { view_store.film_w = film_w; view_store.film_h = film_h; }
+            cam_view = &view_store;
+            pt_params fp = p;
+            fp.seed = p.seed + k;
+            pt_stats ps{};
+            if (pt_render_view(ctx[0], &fp, &cam, cam_view, frame.data(), &ps) != PT_OK) return die("pt_render");
+            st.samples += ps.samples; st.rays_traced += ps.rays_traced; st.rays_reference += ps.rays_reference;
+            st.rays_nominal += ps.rays_nominal;
+            if (pt_render_features_view(ctx[0], &fp, &cam, cam_view, feat.data()) != PT_OK) return die("pt_render_features");
+            if (pt_temporal_push(hist, &cam, cam_view, p.flags, frame.data(), feat.data(), img.data(), var.data()) != PT_OK)
+                return die("pt_temporal_push");
+            if (!quiet) printf("frame %zu of %zu\n", k + 1, poses.size());
+        }
+        pt_temporal_destroy(hist);
+        if (!variance_map.empty()) {
+            std::vector<float> grey(npix * 3);
+            for (int y = 0; y < p.height; ++y)
+                for (int x = 0; x < p.width; ++x) {
+                    const float v = var[p.pixel_order == PT_ORDER_MORTON ? (size_t)pt_morton_pxl_to_i(x, y) : (size_t)y * p.width + x];
+                    for (int k = 0; k < 3; ++k) grey[((size_t)y * p.width + x) * 3 + k] = v;
+                }
+            if (pt_write_pfm(variance_map.c_str(), grey.data(), p.width, p.height) != PT_OK) return die("--variance-map");
+        }
     } else {
         // one GPU: pt_render; N GPUs: image-tile shards on devices 0..N-1 summed by one RCCL reduce
         const int rc = (gpus == 1) ? pt_render_view(ctx[0], &p, &cam, cam_view, img.data(), &st)

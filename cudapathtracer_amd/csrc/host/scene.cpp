@@ -8,6 +8,7 @@
 #include <thread>
 
 #include "host_internal.h"
+#include "project_view.h"
 
 namespace pt {
 
@@ -391,6 +392,15 @@ void pt_camera_ray_jitter(const pt_camera* cam, const pt_view* view, uint32_t id
                      (R[2] * lo.x + U[2] * lo.y) + cam->pos.z);
     else
         *origin = v3(0.0f + cam->pos.x, 0.0f + cam->pos.y, 0.0f + cam->pos.z);
+}
+
+// ---- the inverse of the pinhole camera (pt.h): the host's copy of what the temporal kernel runs (project_view.h)
+int pt_project_view(const pt_camera* cam, const pt_view* view, pt_vec3 P, float* sx, float* sy)
+{
+    pt::clear_error();
+    if (!cam || !sx || !sy) return pt::fail(PT_E_INVALID, "pt_project_view: null argument");
+    const pt_view v = view ? *view : pt::identity_view();
+    return pt::project_view(*cam, v, P.x, P.y, P.z, sx, sy) ? 1 : 0;
 }
 
 // kernel.cu:771 -> color.h:59-62 normalized, color.h:68-71 gammaCorrect(c, 1/2.2), (int)(c*255)

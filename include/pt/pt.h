@@ -29,6 +29,8 @@
  *                           buffers and an edge-avoiding a-trous filter: a preview from a few samples per pixel
  *        pt_noise_variance / pt_denoise_guided  (no counterpart) the estimator's variance map and an a-trous filter
  *                           guided by it, which leaves converged pixels alone: its result converges to the render
+ *        pt_project_view / pt_temporal_*  (no counterpart) temporal reprojection: a history of the image that follows
+ *                           a moving camera through the feature buffers, and the variance map of what it holds
  *        pt_destroy      <- cudaFree (kernel.cu:782-783)
  *        pt_last_error   <- checkError (kernel.cu:37-42), but returned instead of printed
  *
@@ -884,6 +886,97 @@ int pt_denoise_guided_device(pt_ctx* ctx, const pt_denoise_guided_params* gp, in
                              const float* d_in, const pt_feature* d_feat, const float* d_var, float* d_out, void* stream);
 int pt_denoise_guided(pt_ctx* ctx, const pt_denoise_guided_params* gp, int width, int height, int pixel_order,
                       const float* in, const pt_feature* feat, const float* var, float* out /* host */);
+
+/* ------------------------------------------------- temporal reprojection: keep the samples when the camera moves
+ * An accumulator keeps its camera and view for life, so a moving camera starts from 1-spp noise every frame.  Every
+ * material here is Lambertian (albedo plus emission), so the radiance leaving a surface point does not depend on where
+ * the camera stands: last frame's colour at the same world point is a valid sample of this frame's pixel.  A
+ * pt_temporal is the temporal stage of an SVGF-style preview pipeline: it reprojects its history through the previous
+ * push's camera, accumulates the new frame into it and returns, beside the image, a per-pixel variance of the result
+ * that pt_denoise_guided takes as it stands (hand-written gfx950 kernel, pt_temporal.hip; no render kernel is touched).
+ *
+ * pt_project_view: the inverse of the pinhole camera (lens = 0).  The continuous pixel coordinates (sx, sy) at which
+ * the pinhole ray of cam / view passes through the world point P: the corner ray of pixel px gives sx ~ px, the ray
+ * through the footprint's centre (the feature ray under PT_FLAG_JITTER) px + 0.5.  All f32, every operation rounded
+ * on its own, no contraction, IEEE division; W = pxl_width, H = pxl_height:
+ *   q   = P - pos                                           (componentwise)
+ *   c.x = (right[0]*q.x + right[1]*q.y) + right[2]*q.z      c.y, c.z likewise with up, back
+ *   front = c.z < 0
+ *   gx  = (c.x * dist) / c.z            gy = (c.y * dist) / c.z
+ *   sx  = (gx / film_w + 0.5f) * (float)W                   sy = (gy / film_h + 0.5f) * (float)H
+ * A NULL view projects as right = +x, up = +y, back = +z, film 1 x 1 (the sign-of-zero caveat of the forward camera
+ * does not arise: a zero of either sign gives the same sx).  Returns 1 when `front` holds, 0 when not (*sx, *sy are
+ * then unspecified), PT_E_INVALID for a null cam, sx or sy.  The view is not validated, as in pt_camera_ray_view.  The
+ * kernel runs the same function (one definition, host/project_view.h).
+ *
+ * pt_temporal_create: a history for width x height images in `pixel_order` on the context's device, destroyed before
+ * the context; several may live on one context.  It holds two sets of planes, read one and write the other, all in
+ * scanline order, 56 B per pixel and set: G0 = {P.xyz, prim}, G1 = {n.xyz, depth}, C = {r, g, b, n} (16 B each) and
+ * M = {m1, m2} (8 B); and the camera, the view and `off` of its previous push.  PT_E_INVALID: a null ctx or params,
+ * max_history < 1, a normal_min that is not finite or outside [-1, 1], a plane_tol that is not finite or <= 0, flags
+ * != 0, a size outside 1..65535, an unknown pixel order, Morton order on a non-square or non-power-of-two image,
+ * asynchronous renders in flight.
+ *
+ * pt_temporal_push*: takes whole images, as pt_denoise does: `in` W*H*3 fp32, `feat` W*H records of the same frame
+ * (pt_render_features* through the same cam, view and PT_FLAG_JITTER; _device: 16-byte aligned), `out` W*H*3 and
+ * `var` W*H (may be NULL), all in pixel_order; out may equal in.  Blocking; refused while asynchronous renders are in
+ * flight.  In `flags` only PT_FLAG_JITTER is looked at: this frame's features were taken through the footprint's
+ * centre, off = 0.5f; otherwise off = 0.0f.  PT_E_INVALID: null arguments; an invalid view; a cam whose pxl_width /
+ * pxl_height differ from the object's or whose dist_from_film or focal_length is not finite and > 0; a d_feat that
+ * is not 16-byte aligned.  The host variant stages through device buffers the object keeps.
+ *
+ * The arithmetic per pixel p of the new frame, with its feature record F_p and input colour in_p (all f32, every
+ * operation rounded on its own, no contraction, IEEE division; max(a, b) is `b > a ? b : a`); prev cam, prev view and
+ * off_prev are the previous push's:
+ *   lum(c) = (0.2126f*c[0] + 0.7152f*c[1]) + 0.0722f*c[2]
+ *   reset  := first push since create / reset, or prim_p < 0, or pt_project_view(prev cam, prev view, position_p)
+ *             says not front
+ *   fx = sx - off_prev;  fy = sy - off_prev
+ *   snap:  r = floorf(fx + 0.5f);  if (fabsf(fx - r) <= 0.015625f) fx = r;      likewise fy
+ *   reset |= !(fx > -1.0f && fx < (float)W) || !(fy > -1.0f && fy < (float)H)   (NaN resets)
+ *   x0 = (int)floorf(fx);  tx = fx - (float)x0;   y0, ty likewise
+ *   taps in this order: (x0,y0) w = (1-tx)*(1-ty); (x0+1,y0) w = tx*(1-ty); (x0,y0+1) w = (1-tx)*ty;
+ *                       (x0+1,y0+1) w = tx*ty
+ *   a tap q counts iff it is inside the image, its stored prim_q >= 0, its stored n_q > 0,
+ *       (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z >= normal_min, and
+ *       fabsf((n_p.x*(P_q.x-P_p.x) + n_p.y*(P_q.y-P_p.y)) + n_p.z*(P_q.z-P_p.z)) <= plane_tol * depth_p
+ *   for counting taps:  ws += w;  hc[k] += w*C_q[k];  hn += w*n_q;  h1 += w*m1_q;  h2 += w*m2_q
+ *   ws > 0 and not reset:  hc[k] /= ws; hn /= ws; h1 /= ws; h2 /= ws     else: all 0  (hn = 0)
+ *   n' = min(hn + 1.0f, (float)max_history);   a = 1.0f / n'
+ *   out[k] = hc[k] + (in_p[k] - hc[k]) * a
+ *   l = lum(in_p);  m1' = h1 + (l - h1)*a;  m2' = h2 + (l*l - h2)*a
+ *   var_p = n' < 2.0f ? +inf : max(0.0f, m2' - m1'*m1') / (n' - 1.0f)
+ *   store G0, G1 from F_p, C = {out, n'}, M = {m1', m2'} into the write planes;  then swap
+ * n' is the history length: below max_history the output is the running mean of the reprojected samples, from there
+ * on an exponential average.  +inf is pt_noise_variance's "unknown" value and pt_denoise_guided treats it as such.  A
+ * pixel with prim_p < 0 (a miss) stores n' = 1 and its prim, so next frame it is nobody's history; emissive pixels are
+ * ordinary pixels here.  The snap is a condition, not a measurement: a still camera re-projects a pixel onto itself
+ * only up to about 1e-3 pixel, from the rounding of position = o + d*depth; 1/64 pixel is far above that and far below
+ * any real motion, and with it a still camera reads exactly one tap with weight 1.  Inputs are expected to be free of
+ * NaN.  Out of scope: moving geometry, lens (depth-of-field) reprojection -- the features and the history are the
+ * pinhole's --, per-shard histories (push the reduced image, as with pt_denoise).
+ *
+ * pt_temporal_length: the history length n' of every pixel as of the last push (host, W*H, pixel_order; all 0 before
+ * the first push).  pt_temporal_frames: the pushes since create / reset (0 for a null object).  pt_temporal_reset: the
+ * next push is a first push again. */
+typedef struct pt_temporal pt_temporal;
+typedef struct {
+    int32_t max_history;   /* >= 1: the history length is capped here (then an exponential average) */
+    float normal_min;      /* a tap is consistent when n_p.n_q >= normal_min; finite, in [-1, 1]     */
+    float plane_tol;       /* ... and |n_p.(P_q - P_p)| <= plane_tol * depth_p; finite, > 0          */
+    uint32_t flags;        /* 0 */
+} pt_temporal_params;
+int pt_project_view(const pt_camera* cam, const pt_view* view /* NULL ok */, pt_vec3 P, float* sx, float* sy);
+void pt_temporal_defaults(pt_temporal_params* p);   /* {32, 0.9f, 0.02f, 0}: design choices, not measurements */
+pt_temporal* pt_temporal_create(pt_ctx* ctx, const pt_temporal_params* tp, int width, int height, int pixel_order, int* err);
+int pt_temporal_push_device(pt_temporal* t, const pt_camera* cam, const pt_view* view /* NULL ok */, uint32_t flags,
+                            const float* d_in, const pt_feature* d_feat, float* d_out, float* d_var /* NULL ok */, void* stream);
+int pt_temporal_push(pt_temporal* t, const pt_camera* cam, const pt_view* view /* NULL ok */, uint32_t flags,
+                     const float* in, const pt_feature* feat, float* out, float* var /* NULL ok */);
+int pt_temporal_length(pt_temporal* t, float* n_out /* host, W*H, pixel_order */);
+int pt_temporal_frames(const pt_temporal* t);
+int pt_temporal_reset(pt_temporal* t);
+void pt_temporal_destroy(pt_temporal* t);
 
 /* ----------------------------------------------------------- one process, N GPUs
  * A group of contexts on distinct devices with one RCCL communicator per device
