@@ -568,6 +568,34 @@ class Renderer:
                                  L.PT_FLAG_REFERENCE_BVH if reference_bvh else 0))
         return tri, t
 
+    def trace_device(self, d_rays_ptr, n, d_tri_ptr, d_t_ptr, reference_bvh=False, stream_ptr=None):
+        """pt_trace_device on raw device pointers: trace() for n rays {o.xyz, d.xyz} (float32[6n]) into int32[n]
+        triangle ids and float32[n] distances, bit for bit what trace() returns; blocking."""
+        L.check(L.lib().pt_trace_device(self._h, int(n), C.c_void_p(int(d_rays_ptr)), C.c_void_p(int(d_tri_ptr)),
+                                        C.c_void_p(int(d_t_ptr)), L.PT_FLAG_REFERENCE_BVH if reference_bvh else 0,
+                                        None if stream_ptr is None else C.c_void_p(int(stream_ptr))))
+
+    def occluded(self, origins, directions, tmax=None):
+        """Is the segment of ray i up to tmax[i] blocked?  bool[n]: (tri >= 0) & (t < tmax) of trace(), in float32,
+        answered without computing the closest hit.  tmax=None: any hit (1e5)."""
+        rays, n = self._rays(origins, directions)
+        occ = np.zeros(n, dtype=np.uint8)
+        tm = None
+        if tmax is not None:
+            tm = np.ascontiguousarray(tmax, dtype=np.float32).reshape(-1)
+            if len(tm) != n:
+                raise ValueError("tmax needs one entry per ray")
+        L.check(L.lib().pt_occluded(self._h, n, rays.ctypes.data, None if tm is None else tm.ctypes.data, occ.ctypes.data, 0))
+        return occ.astype(bool)
+
+    def occluded_device(self, d_rays_ptr, n, d_occ_ptr, d_tmax_ptr=None, stream_ptr=None):
+        """pt_occluded_device on raw device pointers: uint8[n] answers (0 or 1) for n rays (float32[6n]) and their
+        float32[n] bounds (None: 1e5 for every ray); blocking."""
+        L.check(L.lib().pt_occluded_device(self._h, int(n), C.c_void_p(int(d_rays_ptr)),
+                                           None if d_tmax_ptr is None else C.c_void_p(int(d_tmax_ptr)),
+                                           C.c_void_p(int(d_occ_ptr)), 0,
+                                           None if stream_ptr is None else C.c_void_p(int(stream_ptr))))
+
 
 def accum_file_info(path):
     """Header of a checkpoint file (pt_accum_file_info, host-only): dict of params (spp = 0), camera,

@@ -2755,6 +2755,140 @@ __global__ __launch_bounds__(256) void primary_features_jitter(Args a, float4* _
     primary_features_body<false, true>(a, out);
 }
 
+// ------------------------------------------------------------------ ray queries on device buffers
+// pt_trace_device / pt_occluded*: a caller's rays, classified ray by ray as trace_rays<false, *> classifies them (the
+// BVH4 walk plus winner check, trace_slow, or the reference's walk for a ray outside ray_regular), on a persistent
+// grid.  A wave owns the 64 ray indices a grid-stride loop would give it, chunk after chunk; a lane that ends its ray
+// takes the chunk's next index (one ballot of the idle lanes, base plus rank each; no atomic) once `refill_at` lanes
+// of the wave are idle, instead of waiting for the wave's slowest ray.  refill_at == 64 is trace_rays' lock-step
+// loop.  (A global ray counter, per refill or per 1024 indices, was measured and lost: DESIGN.md 3.17, 8.)  Which
+// lane traces a ray never changes what the ray computes.  Defined after every other kernel, which therefore compile
+// as they did.
+// kOccluded: occ[r] = (tri >= 0 && t < tmax[r]) of that trace, without computing the closest hit: the walk starts
+// with best_t = min(tmax, MAX_FLOAT), so its strict acceptance 0 < t < best_t is the condition, and it ends at the
+// first accepted hit.  That hit counts only if the reference would have tested it (ref_tested); otherwise the exact
+// slow walk's closest hit is compared.  Spheres are tested only if no triangle decided.
+enum : uint32_t { QS_IDLE = 0, QS_WALK, QS_WALKED };
+template <bool kOccluded>
+__global__ __launch_bounds__(256) void query_rays(Args a, const float* __restrict__ rays, const float* __restrict__ tmax,
+                                                  uint32_t n, uint32_t refill_at,
+                                                  int32_t* __restrict__ tri_out, float* __restrict__ t_out,
+                                                  uint8_t* __restrict__ occ_out)
+{
+    extern __shared__ uint32_t lds_tr[];
+    const int lane = threadIdx.x & 63;
+    Counters cnt;
+    Stack4 S;
+    S.ring = lds_tr + (threadIdx.x >> 6) * kWaveLdsWords + lane;
+    S.stride = a.spill_stride;
+    const uint32_t lane_off = (blockIdx.x * blockDim.x + threadIdx.x) * 4u;
+    S.spill_base = a.spill;
+    S.lane_off = &lane_off;
+    S.off_mask = ~0u;
+    uint32_t state = QS_IDLE;
+    uint32_t r = 0;
+    V3 o = v3(0, 0, 0), d = v3(0, 0, 1);
+    float tm = kMaxFloat;   // kOccluded: min(tmax, MAX_FLOAT) of the lane's ray
+    W4 w;
+    walk4_reset(w);
+    // (wave-uniform) the wave's chunk of ray indices, and whether the rays have run out
+    uint32_t chunk_next = 0, chunk_end = 0;
+    uint32_t stride_base = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 64u;   // the chunk after this one
+    bool drained = false;
+    // the end of a ray whose triangles gave (htri, ht): the spheres, the result
+    auto finish = [&](int32_t htri, float ht) {
+        if (kOccluded) {
+            bool occ = htri >= 0 && ht < tm;
+            if (!occ)
+                for (uint32_t k = 0; k < a.num_spheres; ++k) {
+                    const float t = sphere_t(o, d, a.spheres[k]);
+                    if (0.0f < t && t < tm) { occ = true; break; }
+                }
+            occ_out[r] = occ ? 1 : 0;
+        } else {
+            if (a.num_spheres) apply_spheres(a, o, d, &htri, &ht);
+            tri_out[r] = htri;
+            t_out[r] = ht;
+        }
+        state = QS_IDLE;
+    };
+    for (;;) {
+        // ---- the lanes whose walk ended: the winner check (or the exact slow walk), the result
+        if (state == QS_WALKED) {
+            int32_t htri = -1;
+            float ht = kMaxFloat;
+            if (w.best_slot != kNone) {
+                const float4 C = a.acc_tris[w.best_slot].c;
+                htri = (int32_t)__float_as_uint(C.y);
+                ht = w.best_t;
+                if (!ref_tested(__float_as_uint(C.w), o, d, a.rnodes, a.rparent))
+                    trace_slow(o, d, a.root, a.nodes, a.tris_leaf, S.spill(), S.stride, a.cull_rel, a.cull_abs, &htri, &ht);
+            }
+            finish(htri, ht);
+        }
+        // ---- refill: the idle lanes take the chunk's next indices (those it cannot serve wait for the next chunk)
+        const uint64_t idle = __ballot(state == QS_IDLE);
+        if (idle != 0ull && !drained) {
+            if (chunk_next == chunk_end) {
+                chunk_next = stride_base;   // (n <= 2^29 per launch: no index wraps)
+                chunk_end = chunk_next + 64u;
+                stride_base += gridDim.x * blockDim.x;
+                if (chunk_next >= n) { drained = true; chunk_end = chunk_next; }
+                else if (chunk_end > n) chunk_end = n;
+            }
+            const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
+            const uint32_t take = min((uint32_t)__popcll(idle), chunk_end - chunk_next);
+            if (state == QS_IDLE && rank < take) {
+                r = chunk_next + rank;
+                const float* p = rays + (size_t)r * 6;
+                o = v3(p[0], p[1], p[2]);
+                d = v3(p[3], p[4], p[5]);
+                bool live = true;
+                if (kOccluded) {
+                    const float tx = tmax ? tmax[r] : kMaxFloat;
+                    live = tx > 0.0f;   // (false for NaN, +-0 and negative bounds: nothing lies before them)
+                    tm = __builtin_fminf(tx, kMaxFloat);
+                }
+                int32_t htri = -1;
+                float ht = kMaxFloat;
+                if (!live) {
+                    occ_out[r] = 0;
+                } else if (a.num_tris == 0) {
+                    finish(htri, ht);
+                } else if (!ray_regular(o, d, a.origin_max)) {
+                    // a far origin or a long direction: the reference's walk, its stack in this lane's spill column
+                    const Hit h = trace_reference<false>(o, d, a.rnodes, a.tris_orig, S.spill(), 0, cnt, (int)S.stride);
+                    finish(h.tri, h.t);
+                } else if (!((a.scene_fast != 0u) && ray_fast(o, d))) {
+                    trace_slow(o, d, a.root, a.nodes, a.tris_leaf, S.spill(), S.stride, a.cull_rel, a.cull_abs, &htri, &ht);
+                    finish(htri, ht);
+                } else if (walk4_begin(w, o, d, a.acc_root, a.cull_abs)) {
+                    if (kOccluded) w.best_t = tm;   // the walk's bound: only hits with 0 < t < tm are accepted
+                    state = QS_WALK;
+                } else {
+                    finish(htri, ht);
+                }
+            }
+            chunk_next += take;
+        }
+        // ---- walk: one BVH4 step per walking lane, until refill_at lanes are idle again
+        if (__ballot(state == QS_WALK) == 0ull) {
+            if (drained) break;   // (no lane walks and none can begin: all are idle)
+            continue;
+        }
+        for (;;) {
+            if (state == QS_WALK) {
+                bool more = walk4_step<false>(w, o, d, a.nodes4, a.acc_tris, S, a.cull_rel, a.cull_abs, a.node_mask, cnt);
+                if (kOccluded && w.best_slot != kNone) more = false;   // any accepted hit decides
+                if (!more) state = QS_WALKED;
+            }
+            const uint64_t walking = __ballot(state == QS_WALK);
+            if (walking == 0ull) break;
+            if (!drained && 64u - (uint32_t)__popcll(walking) >= refill_at) break;
+        }
+    }
+}
+
 }  // namespace
 
 #include "pt_render_host.h"

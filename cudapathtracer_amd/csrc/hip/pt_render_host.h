@@ -78,6 +78,8 @@ struct pt_ctx : pt::SceneInfo {            // (the scene's scalars: pt_scene_pac
     int fl_head = 0, fl_n = 0;                 // oldest in-flight slot, number in flight
     pt::DenoiseScratch denoise;       // pt_denoise*'s device scratch (pt_denoise.hip), grown on demand
     pt::SessionScratch session;       // pt_session_save / _load's staging (pt_session.cpp), grown on demand
+    uint8_t* query_stage = nullptr;   // pt_occluded's device staging (rays, bounds, answers), grown on demand
+    size_t query_stage_bytes = 0;
 };
 
 int pt::ctx_device(const pt_ctx* c) { return c->device; }
@@ -194,7 +196,7 @@ void pt_destroy(pt_ctx* c)
     void* bufs[] = {c->nodes, c->rnodes, c->tris_leaf, c->tris_orig, c->shade, c->mats,
                     c->lights, c->jump, c->jump_bytes, c->shade_m, c->scratch_out,
                     c->nodes4, c->acc_tris, c->rparent, c->hrec,
-                    c->tone_thr, c->spheres, c->tri_counts, c->emis, c->denoise.mem, c->session.dev};
+                    c->tone_thr, c->spheres, c->tri_counts, c->emis, c->denoise.mem, c->session.dev, c->query_stage};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     pt::free_pinned(c->session.host);
@@ -960,6 +962,130 @@ extern "C" int pt_trace_counts(pt_ctx* c, uint32_t n, const float* rays, int32_t
         HIP_TRY(hipMemcpy(&v, c->rb[0].counters + CNT_SPILL, sizeof(v), hipMemcpyDeviceToHost));
         *spill_entries = v;
     }
+    return PT_OK;
+}
+
+// ---- ray queries on device buffers (pt_trace_device, pt_occluded_device, pt_occluded; query_rays)
+
+// An integer knob of the queries, read on every call: the variable's value clamped to lo..hi, or dflt when unset.
+static uint32_t query_knob(const char* name, uint32_t lo, uint32_t hi, uint32_t dflt)
+{
+    const char* e = getenv(name);
+    if (!e || !*e) return dflt;
+    return (uint32_t)std::min<long long>(std::max<long long>(atoll(e), (long long)lo), (long long)hi);
+}
+
+// Rays per launch: no ray index wraps and 6 * index stays below 2^32 (trace_rays indexes in 32 bits).
+constexpr uint32_t kQueryLaunchRays = 1u << 29;
+constexpr uint32_t kQueryRefillAt = 32;   // idle lanes of a wave at which it refills
+
+// What the three calls check, in this order: the context; n == 0 (PT_OK, nothing else looked at); the flags; the
+// buffers; renders in flight; the LDS stack (as pt_trace).
+static int query_check(const pt_ctx* c, const char* who, uint32_t n, uint32_t flags, uint32_t allowed, bool buffers, bool* done)
+{
+    *done = true;
+    if (!c) return pt::fail(PT_E_INVALID, "%s: null context", who);
+    if (n == 0) return PT_OK;
+    if (flags & ~allowed) return pt::fail(PT_E_INVALID, "%s: unknown flags 0x%x (allowed: 0x%x)", who, flags & ~allowed, allowed);
+    if (!buffers) return pt::fail(PT_E_INVALID, "%s: null buffer", who);
+    if (c->fl_n > 0) return pt::fail(PT_E_INVALID, "%s: %d asynchronous renders in flight (pt_render_wait first)", who, c->fl_n);
+    if ((size_t)std::max<uint32_t>((uint32_t)(c->depth + 2) * 64, (uint32_t)kWaveLdsWords) * 16 > 160 * 1024)
+        return pt::fail(PT_E_BVH_DEPTH, "%s: BVH depth %d too deep for the LDS stack", who, c->depth);
+    *done = false;
+    return PT_OK;
+}
+
+// Enqueue the query of n rays on `stream` and wait for it.  occluded: d_occ (and d_tmax or null); else d_tri, d_t.
+static int query_run(pt_ctx* c, bool occluded, bool ref, uint32_t n, const float* d_rays, const float* d_tmax, int32_t* d_tri,
+                     float* d_t, uint8_t* d_occ, hipStream_t stream)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    if (!alloc_bufs(c->rb[0])) return pt::fail(PT_E_HIP, "ray query: device allocation failed");
+    Args a;
+    memset(&a, 0, sizeof(a));
+    fill_scene_args(a, c);
+    a.counters = c->rb[0].counters;
+    a.node_mask = c->node4_mask;
+    // PT_QUERY_REFILL: the idle lanes at which a wave refills (64: lock-step; tools/query_cost.py)
+    const uint32_t refill_at = query_knob("PT_QUERY_REFILL", 1, 64, kQueryRefillAt);
+    const void* kernel = occluded ? (const void*)query_rays<true> : (const void*)query_rays<false>;
+    size_t lds = (size_t)kWaveLdsWords * 4 * 4;
+    uint32_t cap = (uint32_t)c->num_cus * 8u;   // trace_rays' grid (pt_trace)
+    // PT_QUERY_LOCKSTEP=1: pt_trace_device runs pt_trace's own kernel, trace_rays<false, false>, on the caller's buffers
+    // (the same bits; the baseline tools/query_cost.py measures query_rays against)
+    const bool lockstep = !occluded && !ref && query_knob("PT_QUERY_LOCKSTEP", 0, 1, 0) != 0;
+    if (ref || lockstep) {
+        a.stack_words = std::max<uint32_t>((uint32_t)(c->depth + 2) * 64, (uint32_t)kWaveLdsWords);
+        lds = (size_t)a.stack_words * 4 * 4;
+    } else {
+        // a persistent grid: the blocks the device holds at once, or PT_QUERY_BLOCKS of them
+        int per_cu = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, lds));
+        cap = (uint32_t)c->num_cus * (uint32_t)std::max(per_cu, 1);
+        cap = query_knob("PT_QUERY_BLOCKS", 1, cap, cap);
+    }
+    for (uint64_t first = 0; first < n; first += kQueryLaunchRays) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(n - first, kQueryLaunchRays);
+        const uint32_t blocks = std::min((m + 255u) / 256u, cap);
+        if (int rc = pt::grow(&c->rb[0].spill, &c->rb[0].spill_words, stack_words_per_lane(c) * (size_t)blocks * 256)) return rc;
+        a.spill = c->rb[0].spill;
+        a.spill_stride = blocks * 256;
+        const float* rays = d_rays + first * 6;
+        if (ref) {
+            hipLaunchKernelGGL((trace_rays<true, false>), dim3(blocks), dim3(256), lds, stream, a, rays, m, d_tri + first, d_t + first);
+        } else if (lockstep) {
+            hipLaunchKernelGGL((trace_rays<false, false>), dim3(blocks), dim3(256), lds, stream, a, rays, m, d_tri + first, d_t + first);
+        } else {
+            const float* tmax = d_tmax ? d_tmax + first : nullptr;
+            if (!occluded)
+                hipLaunchKernelGGL((query_rays<false>), dim3(blocks), dim3(256), lds, stream, a, rays, tmax, m, refill_at,
+                                   d_tri + first, d_t + first, (uint8_t*)nullptr);
+            else
+                hipLaunchKernelGGL((query_rays<true>), dim3(blocks), dim3(256), lds, stream, a, rays, tmax, m, refill_at,
+                                   (int32_t*)nullptr, (float*)nullptr, d_occ + first);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(stream));   // (the next launch reuses the spill columns)
+    }
+    return PT_OK;
+}
+
+extern "C" int pt_trace_device(pt_ctx* c, uint32_t n, const float* d_rays, int32_t* d_tri, float* d_t, uint32_t flags, void* stream)
+{
+    pt::clear_error();
+    bool done;
+    if (int rc = query_check(c, "pt_trace_device", n, flags, PT_FLAG_REFERENCE_BVH, d_rays && d_tri && d_t, &done)) return rc;
+    if (done) return PT_OK;
+    return query_run(c, false, (flags & PT_FLAG_REFERENCE_BVH) != 0, n, d_rays, nullptr, d_tri, d_t, nullptr,
+                     reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int pt_occluded_device(pt_ctx* c, uint32_t n, const float* d_rays, const float* d_tmax, uint8_t* d_occ, uint32_t flags,
+                                  void* stream)
+{
+    pt::clear_error();
+    bool done;
+    if (int rc = query_check(c, "pt_occluded_device", n, flags, 0u, d_rays && d_occ, &done)) return rc;
+    if (done) return PT_OK;
+    return query_run(c, true, false, n, d_rays, d_tmax, nullptr, nullptr, d_occ, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int pt_occluded(pt_ctx* c, uint32_t n, const float* rays, const float* tmax, uint8_t* occ, uint32_t flags)
+{
+    pt::clear_error();
+    bool done;
+    if (int rc = query_check(c, "pt_occluded", n, flags, 0u, rays && occ, &done)) return rc;
+    if (done) return PT_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    // the context's staging buffer: the rays (24 n bytes), the bounds (4 n), the answers (n)
+    if (int rc = pt::grow(&c->query_stage, &c->query_stage_bytes, (size_t)n * 29)) return rc;
+    float* const d_rays = reinterpret_cast<float*>(c->query_stage);
+    float* const d_tmax = d_rays + (size_t)n * 6;
+    uint8_t* const d_occ = c->query_stage + (size_t)n * 28;
+    HIP_TRY(hipMemcpy(d_rays, rays, (size_t)n * 24, hipMemcpyHostToDevice));
+    if (tmax) HIP_TRY(hipMemcpy(d_tmax, tmax, (size_t)n * 4, hipMemcpyHostToDevice));
+    if (int rc = query_run(c, true, false, n, d_rays, tmax ? d_tmax : nullptr, nullptr, nullptr, d_occ, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(occ, d_occ, n, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

@@ -757,6 +757,37 @@ int pt_trace_counts(pt_ctx* ctx, uint32_t n, const float* rays, int32_t* tri_out
  * last triangle's slot, which the reference's numTris-1 buffer lacks). */
 int pt_tri_counts(pt_ctx* ctx, uint32_t* counts, uint32_t n);
 
+/* ------------------------------------------------------------------ ray queries on device buffers
+ * A caller's own rays, in DEVICE memory on a stream: the closest hit, and "is anything between these two
+ * points?".  Rays are d_rays[6n] = {o.xyz, d.xyz} as pt_trace's.  All three calls block: they wait for their
+ * own work on `stream` (NULL = the default stream), as every _device call does.  No device memory is allocated
+ * per call: the walks' spill columns grow inside the context as they do for renders.
+ *
+ * pt_trace_device: pt_trace exactly -- d_tri[i], d_t[i] = (tri, t) of the reference's trace() for every ray with
+ * finite components and a non-zero direction, spheres included (ids num_tris + i), t = 1e5 and tri = -1 on a
+ * miss.  flags: 0 or PT_FLAG_REFERENCE_BVH, as pt_trace's; with 0 each ray takes the walk pt_trace gives it.
+ *
+ * pt_occluded*: is the segment of ray i up to tmax[i] blocked?  A definition, not a measurement:
+ *     occ[i] = (tri_i >= 0 && t_i < tmax_i) ? 1 : 0          (an f32 compare)
+ * with (tri_i, t_i) what pt_trace returns for ray i.  A NaN, zero or negative tmax gives 0; +inf or anything
+ * above 1e5 means "any hit"; tmax = NULL means 1e5 for every ray.  The closest hit is not computed: the walk is
+ * bounded at tmax and ends at the first hit the reference would also have tested (a first hit it would not have
+ * tested sends the ray to the exact walk, whose closest hit is compared); rays outside the fast walk's ranges
+ * take their exact walks and compare at the end; spheres are tested only if no triangle decided.  flags must be
+ * 0.  Every entry below n is written as a 0 or 1 byte.  pt_occluded: host buffers, staged through a device
+ * buffer the context keeps, grows on demand and frees in pt_destroy.
+ *
+ * Order of the checks, for all three: a null context is PT_E_INVALID; then n == 0 is PT_OK and nothing else is
+ * looked at or touched (entries at index n and beyond are never written for any n); then PT_E_INVALID for
+ * unknown flag bits, a null buffer (d_tmax / tmax may be NULL) or asynchronous renders in flight; then
+ * PT_E_BVH_DEPTH as pt_trace returns it.
+ * PT_QUERY_BLOCKS in the environment (read on every call) forces the persistent grid to 1..default blocks; no
+ * bit of any answer depends on it. */
+int pt_trace_device(pt_ctx* ctx, uint32_t n, const float* d_rays, int32_t* d_tri, float* d_t, uint32_t flags, void* stream);
+int pt_occluded_device(pt_ctx* ctx, uint32_t n, const float* d_rays, const float* d_tmax /* n floats, or NULL */,
+                       uint8_t* d_occ, uint32_t flags, void* stream);
+int pt_occluded(pt_ctx* ctx, uint32_t n, const float* rays, const float* tmax /* or NULL */, uint8_t* occ, uint32_t flags);
+
 /* Output step on the GPU (kernel.cu:763-778, color.h:59-71): codes = pt_tonemap_u8(rgb) per
  * channel, identical to the host function (threshold table bisected with the host's libm at
  * pt_create).  _device: device pointers on `stream`, blocking; negative inputs (which the
