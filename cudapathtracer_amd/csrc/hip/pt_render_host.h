@@ -156,6 +156,10 @@ pt_ctx* pt_create(const pt_scene* sc, int device, int* err)
                              "(got %u tris, %u nodes, %u spheres)", sc->num_tris, sc->bvh_size, sc->num_spheres));
     if (sc->bvh_depth >= PT_MAX_BVH_DEPTH)
         return bail(pt::fail(PT_E_BVH_DEPTH, "Critical Error: BVH depth is too big (%d)", sc->bvh_depth));
+    // the scene's indices and its BVH (host only: a scene the walks cannot take is refused with or without a device)
+    pt::SceneCheck checked;
+    if (int rc = pt::check_scene(*sc, &checked)) return bail(rc);
+    timer.lap("scene validation");
     // the device
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return bail(pt::fail(PT_E_NODEV, "pt_create: no HIP device"));
@@ -168,7 +172,8 @@ pt_ctx* pt_create(const pt_scene* sc, int device, int* err)
     // the scene as the kernels read it
     const pt::RenderKnobs knobs = pt::read_render_knobs(kQueues, kTopNodesMax);
     pt::PackedScene P;
-    if (int rc = pt::pack_scene(*sc, knobs, &timer, &P)) return bail(rc);
+    timer.lap("device query");
+    if (int rc = pt::pack_scene(*sc, knobs, &timer, &P, &checked)) return bail(rc);
     pt_ctx* c = new (std::nothrow) pt_ctx();
     if (!c) return bail(pt::fail(PT_E_OOM, "pt_create: out of host memory"));
     static_cast<pt::SceneInfo&>(*c) = P;
@@ -642,6 +647,8 @@ static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, c
     const uint32_t levels = (uint32_t)c->depth + 2;
     a.stack_words = std::max<uint32_t>(levels * 128, (uint32_t)kWaveLdsWords);   // (culled walk's stack, or the BVH4 rings)
     const size_t lds = (size_t)a.stack_words * 4;
+    // (not reachable while pt_create caps bvh_depth at PT_MAX_BVH_DEPTH - 1 = 63: this limit starts at depth 319)
+    static_assert((size_t)(PT_MAX_BVH_DEPTH - 1 + 2) * 128 * 4 <= 160 * 1024, "every depth pt_create accepts fits the LDS stack");
     if (lds > 160 * 1024) return pt::fail(PT_E_BVH_DEPTH, "pt_render: BVH depth %d needs %zu B of LDS stack", c->depth, lds);
     a.pixel_counter = B.pixel_counter;
     a.nunits = a.npix;
@@ -923,6 +930,8 @@ extern "C" int pt_trace_counts(pt_ctx* c, uint32_t n, const float* rays, int32_t
     a.stack_words = (uint32_t)(c->depth + 2) * 64;
     if (a.stack_words < (uint32_t)kWaveLdsWords) a.stack_words = kWaveLdsWords;
     const size_t lds = (size_t)a.stack_words * 4 * 4;
+    // (not reachable while pt_create caps bvh_depth at 63: this limit starts at depth 159)
+    static_assert((size_t)(PT_MAX_BVH_DEPTH - 1 + 2) * 64 * 16 <= 160 * 1024, "every depth pt_create accepts fits the LDS stack");
     if (lds > 160 * 1024) return pt::fail(PT_E_BVH_DEPTH, "pt_trace: BVH depth %d too deep for the LDS stack", c->depth);
     uint32_t blocks = (n + 255) / 256;
     const uint32_t cap = (uint32_t)c->num_cus * 8u;
@@ -989,6 +998,7 @@ static int query_check(const pt_ctx* c, const char* who, uint32_t n, uint32_t fl
     if (flags & ~allowed) return pt::fail(PT_E_INVALID, "%s: unknown flags 0x%x (allowed: 0x%x)", who, flags & ~allowed, allowed);
     if (!buffers) return pt::fail(PT_E_INVALID, "%s: null buffer", who);
     if (c->fl_n > 0) return pt::fail(PT_E_INVALID, "%s: %d asynchronous renders in flight (pt_render_wait first)", who, c->fl_n);
+    // (not reachable while pt_create caps bvh_depth at 63, as in pt_trace: kept for a larger PT_MAX_BVH_DEPTH)
     if ((size_t)std::max<uint32_t>((uint32_t)(c->depth + 2) * 64, (uint32_t)kWaveLdsWords) * 16 > 160 * 1024)
         return pt::fail(PT_E_BVH_DEPTH, "%s: BVH depth %d too deep for the LDS stack", who, c->depth);
     *done = false;

@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <utility>
 
 using namespace ptd;
@@ -93,6 +94,9 @@ static int check_indices(const pt_scene& sc)
 
 // The reference BVH is a tree over the triangles: every reference in range, every triangle reached once.
 // leaf_order = the triangles in left-first DFS order (the order trace() meets leaves), leaf_rank its inverse.
+// The same walk checks what the device walks rely on (pt.h, pt_scene): finite boxes, every child box within its
+// parent's, every triangle's vertices within its parent node's box, and the tree's true depth (a leaf counts 1, a
+// node 1 + its deeper child) below PT_MAX_BVH_DEPTH and not above sc.bvh_depth.  check_indices comes first.
 static int check_bvh(const pt_scene& sc, std::vector<uint32_t>* leaf_rank, std::vector<uint32_t>* leaf_order)
 {
     const uint32_t nt = sc.num_tris, nn = sc.bvh_size;
@@ -100,26 +104,57 @@ static int check_bvh(const pt_scene& sc, std::vector<uint32_t>* leaf_rank, std::
     leaf_order->clear();
     leaf_order->reserve(nt);
     if (nt == 0) return PT_OK;
-    std::vector<uint32_t> st;
-    st.push_back(0);
+    struct Entry { uint32_t ref, parent; int32_t level; };   // level: 1 for the root; parent of the root: itself
+    std::vector<Entry> st;
+    st.push_back({0u, 0u, 1});
     size_t visits = 0;
+    int32_t depth = 0;
     while (!st.empty()) {
-        const uint32_t e = st.back();
+        const Entry e = st.back();
         st.pop_back();
         if (++visits > 4ull * nt + 8) return fail(PT_E_SCENE, "pt_create: BVH is not a tree");
-        if (e & PT_BVH_LEAF_FLAG) {
-            const uint32_t k = e ^ PT_BVH_LEAF_FLAG;
+        if (e.level > depth) depth = e.level;
+        if (e.ref & PT_BVH_LEAF_FLAG) {
+            const uint32_t k = e.ref ^ PT_BVH_LEAF_FLAG;
             if (k >= nt || (*leaf_rank)[k] != 0xffffffffu) return fail(PT_E_SCENE, "pt_create: bad BVH leaf %u", k);
             (*leaf_rank)[k] = (uint32_t)leaf_order->size();
             leaf_order->push_back(k);
+            const pt_bvh_node& p = sc.bvh[e.parent];
+            const pt_triangle& t = sc.tris[k];
+            for (int32_t vi : {t.v0, t.v1, t.v2}) {
+                const pt_vec3& v = sc.verts[vi];
+                if (!(v.x >= p.lo.x && v.x <= p.hi.x && v.y >= p.lo.y && v.y <= p.hi.y && v.z >= p.lo.z && v.z <= p.hi.z))
+                    return fail(PT_E_SCENE, "pt_create: triangle %u has vertex %d (%.9g %.9g %.9g) outside the box of its BVH node %u",
+                                k, vi, (double)v.x, (double)v.y, (double)v.z, e.parent);
+            }
         } else {
-            if (e >= nn) return fail(PT_E_SCENE, "pt_create: BVH child %u out of range", e);
-            st.push_back(sc.bvh[e].right);
-            st.push_back(sc.bvh[e].left);
+            if (e.ref >= nn) return fail(PT_E_SCENE, "pt_create: BVH child %u out of range", e.ref);
+            const pt_bvh_node& x = sc.bvh[e.ref];
+            const float b[6] = {x.lo.x, x.lo.y, x.lo.z, x.hi.x, x.hi.y, x.hi.z};
+            for (int q = 0; q < 6; ++q)
+                if (!std::isfinite(b[q])) return fail(PT_E_SCENE, "pt_create: BVH node %u has a box coordinate that is not finite", e.ref);
+            if (e.level > 1) {
+                const pt_bvh_node& p = sc.bvh[e.parent];
+                if (!(x.lo.x >= p.lo.x && x.lo.y >= p.lo.y && x.lo.z >= p.lo.z && x.hi.x <= p.hi.x && x.hi.y <= p.hi.y && x.hi.z <= p.hi.z))
+                    return fail(PT_E_SCENE, "pt_create: the box of BVH node %u is not within the box of its parent, node %u", e.ref, e.parent);
+            }
+            st.push_back({x.right, e.ref, e.level + 1});
+            st.push_back({x.left, e.ref, e.level + 1});
         }
     }
     if (leaf_order->size() != nt) return fail(PT_E_SCENE, "pt_create: BVH reaches %zu of %u triangles", leaf_order->size(), nt);
+    if (depth >= PT_MAX_BVH_DEPTH)
+        return fail(PT_E_BVH_DEPTH, "pt_create: the BVH is %d levels deep (bvh_depth says %d), the limit is %d", depth, sc.bvh_depth,
+                    PT_MAX_BVH_DEPTH - 1);
+    if (sc.bvh_depth < depth)
+        return fail(PT_E_SCENE, "pt_create: bvh_depth is %d but the BVH is %d levels deep (the stacks are sized by it)", sc.bvh_depth, depth);
     return PT_OK;
+}
+
+int check_scene(const pt_scene& sc, SceneCheck* out)
+{
+    if (int rc = check_indices(sc)) return rc;
+    return check_bvh(sc, &out->leaf_rank, &out->leaf_order);
 }
 
 // what the scene is, for pt_accum_save / pt_accum_load: every array the caller passed
@@ -258,15 +293,18 @@ static int pack_bvh4(const pt_scene& sc, const RenderKnobs& knobs, PhaseTimer* t
     return PT_OK;
 }
 
-int pack_scene(const pt_scene& scene, const RenderKnobs& knobs, PhaseTimer* timer, PackedScene* P)
+int pack_scene(const pt_scene& scene, const RenderKnobs& knobs, PhaseTimer* timer, PackedScene* P, const SceneCheck* checked)
 {
     const pt_scene* sc = &scene;
     *P = PackedScene();
     const uint32_t nt = sc->num_tris, nn = sc->bvh_size;
-    if (int rc = check_indices(scene)) return rc;
-    timer->lap("device query");
-    std::vector<uint32_t> leaf_rank, leaf_order;
-    if (int rc = check_bvh(scene, &leaf_rank, &leaf_order)) return rc;
+    SceneCheck own;
+    if (!checked) {
+        if (int rc = check_scene(scene, &own)) return rc;
+        checked = &own;
+        timer->lap("scene validation");
+    }
+    const std::vector<uint32_t>&leaf_rank = checked->leaf_rank, &leaf_order = checked->leaf_order;
 
     P->num_tris = nt;
     P->scene_digest = scene_digest(scene);
@@ -329,8 +367,18 @@ int pack_scene(const pt_scene& scene, const RenderKnobs& knobs, PhaseTimer* time
         const pt_bvh_node& r = sc->bvh[0];
         P->root[0] = r.lo.x; P->root[1] = r.lo.y; P->root[2] = r.lo.z;
         P->root[3] = r.hi.x; P->root[4] = r.hi.y; P->root[5] = r.hi.z;
-        for (int q = 0; q < 3; ++q) { lo_all[q] = P->root[q]; hi_all[q] = P->root[3 + q]; }
     }
+    // The scene extent is that of the geometry: the vertices the triangles use (build_accel's `ext`, which sizes the
+    // BVH4 boxes' margin) and the spheres.  Not the root box: a caller's may be looser, and origin_max, near_camera()
+    // and cull_abs scale with the extent (64 extents is as far as that margin covers the BVH4 walk's box test).
+    for (uint32_t i = 0; i < nt; ++i)
+        for (int32_t vi : {sc->tris[i].v0, sc->tris[i].v1, sc->tris[i].v2}) {
+            const float cc[3] = {sc->verts[vi].x, sc->verts[vi].y, sc->verts[vi].z};
+            for (int q = 0; q < 3; ++q) {
+                lo_all[q] = std::fmin(lo_all[q], cc[q]);
+                hi_all[q] = std::fmax(hi_all[q], cc[q]);
+            }
+        }
     for (uint32_t k = 0; k < sc->num_spheres; ++k) {   // the scene extent covers the spheres too
         const pt_sphere& sp = sc->spheres[k];
         const float cc[3] = {sp.pos.x, sp.pos.y, sp.pos.z};
@@ -348,16 +396,17 @@ int pack_scene(const pt_scene& scene, const RenderKnobs& knobs, PhaseTimer* time
         P->scene_extent = (ext > 0.0f && std::isfinite(ext)) ? ext : 1.0f;
     }
     {
-        // Markstein-quotient precondition on the scene (pt_device.h div_mk): every vertex
-        // coordinate is 0 or has magnitude in [2^-50, 2^20].  Boxes are min/max of vertices.
+        // Markstein-quotient precondition on the scene (pt_device.h div_mk): every vertex and box
+        // coordinate is 0 or has magnitude in [2^-50, 2^20].  (A caller's boxes need not be min/max of vertices.)
         bool ok = true;
-        for (uint32_t v = 0; v < sc->num_verts && ok; ++v) {
-            const float q[3] = {sc->verts[v].x, sc->verts[v].y, sc->verts[v].z};
-            for (int k = 0; k < 3; ++k) {
-                const float m = std::fabs(q[k]);
-                if (!(m == 0.0f || (m >= 0x1p-50f && m <= 0x1p20f))) ok = false;
-            }
-        }
+        auto in_range = [&](float c) {
+            const float m = std::fabs(c);
+            if (!(m == 0.0f || (m >= 0x1p-50f && m <= 0x1p20f))) ok = false;
+        };
+        for (uint32_t v = 0; v < sc->num_verts && ok; ++v)
+            for (float c : {sc->verts[v].x, sc->verts[v].y, sc->verts[v].z}) in_range(c);
+        for (uint32_t i = 0; i < nn && ok; ++i)
+            for (float c : {sc->bvh[i].lo.x, sc->bvh[i].lo.y, sc->bvh[i].lo.z, sc->bvh[i].hi.x, sc->bvh[i].hi.y, sc->bvh[i].hi.z}) in_range(c);
         P->scene_fast = ok;
         P->node_mask = index_mask(nn);
     }

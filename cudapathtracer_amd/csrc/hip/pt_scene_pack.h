@@ -62,8 +62,17 @@ struct PhaseTimer {
     void lap(const char* what);
 };
 
-// Validates the scene's indices, lights, spheres and BVH and fills every record.  The scene's null / count /
-// depth checks are pt_create's, before it.
-int pack_scene(const pt_scene& sc, const RenderKnobs& knobs, PhaseTimer* timer, PackedScene* out);
+// What check_scene learns of a valid scene's reference BVH and pack_scene needs again.
+struct SceneCheck {
+    std::vector<uint32_t> leaf_rank, leaf_order;   // the triangles in left-first DFS order, and the inverse
+};
+
+// Validates the scene's indices, lights, spheres and BVH (pt.h, pt_scene: a tree over the triangles with finite,
+// nested, bounding boxes, no deeper than bvh_depth says), in one walk of the tree.  Host only, no device needed:
+// pt_create runs it before it looks for one.  The scene's null / count checks are pt_create's, before it.
+int check_scene(const pt_scene& sc, SceneCheck* out);
+
+// Fills every record of a scene that passed check_scene (checked = its result; null: runs check_scene itself).
+int pack_scene(const pt_scene& sc, const RenderKnobs& knobs, PhaseTimer* timer, PackedScene* out, const SceneCheck* checked = nullptr);
 
 }  // namespace pt

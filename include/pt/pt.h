@@ -84,7 +84,22 @@ typedef struct {                                                                
  * {diffuse, emission}; emissive spheres are area lights of area 4*3.14159*rad^2. */
 typedef struct { pt_vec3 pos; float rad; double diffuse[3]; double emission[3]; } pt_sphere;
 
-/* Read-only view of a scene: sceneDesc (modelLoader.h:29-41) + BVH_array (BVH.h:116-121). */
+/* Read-only view of a scene: sceneDesc (modelLoader.h:29-41) + BVH_array (BVH.h:116-121).
+ *
+ * The arrays may be pt_scene_view's or the caller's own, BVH included.  pt_create checks, on the host and before it
+ * looks for a device, what the device walks rely on, and refuses anything else with PT_E_SCENE (the message names the
+ * node or triangle):
+ *   - the nodes are a binary tree, root = node 0, that reaches every triangle exactly once (any node order: a child
+ *     may have a smaller index than its parent); every index of tris, lights and the tree is in range;
+ *   - every box coordinate is finite;
+ *   - every child node's box lies within its parent's (lo >= lo and hi <= hi per axis, compared as floats);
+ *   - the three vertices of every triangle lie within the box of the node whose leaf it is;
+ *   - bvh_depth >= the tree's true depth (a leaf counts 1, a node 1 + its deeper child): every traversal stack is
+ *     sized from the field.  A larger value changes no result.  A true depth >= PT_MAX_BVH_DEPTH is PT_E_BVH_DEPTH.
+ * pt_scene_build_bvh's trees meet all of it.  Boxes may be looser than the vertices (the scene's extent, by which
+ * far origins and cameras are told, is that of the triangles' vertices and the spheres, not of the boxes).  Hits at equal distance go to the
+ * triangle met first in left-first depth-first order of this tree, as in the reference's trace().  norm, lights and
+ * total_light_area are used as given. */
 typedef struct {
     uint32_t num_verts, num_tris, num_mats, num_lights;
     const pt_vec3* verts;
@@ -92,9 +107,9 @@ typedef struct {
     const pt_material* mats;
     const uint32_t* lights;
     float total_light_area;
-    const pt_bvh_node* bvh;    /* breadth-first array, node 0 = root            */
+    const pt_bvh_node* bvh;    /* node 0 = root (pt_scene_build_bvh: breadth-first) */
     uint32_t bvh_size;         /* = num_tris - 1 (0 for a scene of spheres only) */
-    int32_t bvh_depth;         /* BVH_node::depth of the root (BVH.h:322, :346)  */
+    int32_t bvh_depth;         /* BVH_node::depth of the root (BVH.h:322, :346), or more */
     const pt_sphere* spheres;  /* sphere primitives (hit ids num_tris + i)      */
     uint32_t num_spheres;
 } pt_scene;
