@@ -87,6 +87,11 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class RayClasses(C.Structure):   # pt_ray_classes, 32 B
+    _fields_ = [("regular", C.c_uint64), ("irregular", C.c_uint64), ("invalid", C.c_uint64),
+                ("first_invalid", C.c_uint32), ("pad", C.c_uint32)]
+
+
 PT_FEATURE_EMISSIVE = 0x40000000   # pt_feature.prim bit: the hit material emits
 PT_DENOISE_NO_DEMODULATE = 0x1
 
@@ -199,6 +204,9 @@ SIGNATURES = {
     "pt_trace_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "pt_occluded_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "pt_occluded": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "pt_render_rays_device": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "pt_render_rays": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "pt_rays_classify_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(RayClasses)]),
     "pt_tonemap_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pt_tonemap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "pt_write_ppm_codes": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int]),

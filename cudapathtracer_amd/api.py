@@ -596,6 +596,53 @@ class Renderer:
                                            C.c_void_p(int(d_occ_ptr)), 0,
                                            None if stream_ptr is None else C.c_void_p(int(stream_ptr))))
 
+    def render_rays(self, origins, directions, width, height, spp, bounces=3, integrator=0, seed=1234, flags=0,
+                    shard_index=0, shard_count=1, pixel_order=0, tile_w=0, tile_h=0, out=None):
+        """Render along the caller's rays instead of a camera's (pt_render_rays): any projection, probes, baking.
+        origins, directions: W*H float32 triples, the ray of pixel (x, y) at its index in `pixel_order` (y*W + x, or
+        the Morton index); cudapathtracer_amd.rays builds common sets.  Returns (image, stats) as render().  Pixel
+        (x, y) is the mean of spp samples of the integrator down its ray, seeded as render() seeds the pixel; no sample
+        draws a lens pair, so the camera's own rays (rays.camera_rays) give render()'s image bit for bit except at
+        pixel (0, 0).  A ray with a non-finite component or a zero direction is refused (PtError PT_E_INVALID naming
+        the pixel).  A ray farther out than 64 scene extents, or a direction longer than a normalised one (d.d > 1 +
+        2^-10), sends THE WHOLE RENDER to the tile kernel with the reference's own walk: exact, but much slower
+        (stats["work_units"] == 0 shows that it happened).  flags: 0, PT_FLAG_NO_DEAD_PATH_SKIP,
+        PT_FLAG_NO_PRIMARY_CACHE, PT_FLAG_REFERENCE_TRAVERSAL, PT_FLAG_REFERENCE_BVH."""
+        rays, n = self._rays(origins, directions)
+        if n != int(width) * int(height):
+            raise ValueError("render_rays: %d rays for a %dx%d image" % (n, width, height))
+        p = self.params(width, height, spp, bounces, integrator, seed, flags, shard_index, shard_count,
+                        pixel_order, tile_w, tile_h)
+        shape = (height * width, 3) if pixel_order == L.PT_ORDER_MORTON else (height, width, 3)
+        if out is None:
+            out = np.zeros(shape, dtype=np.float32)
+        elif out.dtype != np.float32 or out.size != width * height * 3 or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous float32 array of W*H*3 values")
+        st = L.Stats()
+        L.check(L.lib().pt_render_rays(self._h, C.byref(p), rays.ctypes.data, out.ctypes.data, C.byref(st)))
+        return out, st.as_dict()
+
+    def render_rays_device(self, d_rays_ptr, d_out_ptr, width, height, spp, bounces=3, integrator=0, seed=1234, flags=0,
+                           shard_index=0, shard_count=1, pixel_order=0, tile_w=0, tile_h=0, stream_ptr=None):
+        """pt_render_rays_device on raw device pointers (e.g. torch tensors): W*H rays {o.xyz, d.xyz} (float32[6*W*H],
+        8-byte aligned) into this shard's pixels of a caller-owned float32[W*H*3] buffer; blocking; returns the stats.
+        Everything else as render_rays(), the whole-render fall-back for far or unnormalised rays included."""
+        p = self.params(width, height, spp, bounces, integrator, seed, flags, shard_index, shard_count,
+                        pixel_order, tile_w, tile_h)
+        st = L.Stats()
+        L.check(L.lib().pt_render_rays_device(self._h, C.byref(p), C.c_void_p(int(d_rays_ptr)), C.c_void_p(int(d_out_ptr)),
+                                              None if stream_ptr is None else C.c_void_p(int(stream_ptr)), C.byref(st)))
+        return st.as_dict()
+
+    def classify_rays_device(self, d_rays_ptr, n, stream_ptr=None):
+        """The classes of n rays on the device (pt_rays_classify_device), as render_rays* sorts them: a dict of
+        regular, irregular, invalid (counts) and first_invalid (lowest invalid index, 0xffffffff for none)."""
+        rc = L.RayClasses()
+        L.check(L.lib().pt_rays_classify_device(self._h, int(n), None if not d_rays_ptr else C.c_void_p(int(d_rays_ptr)),
+                                                None if stream_ptr is None else C.c_void_p(int(stream_ptr)), C.byref(rc)))
+        return dict(regular=int(rc.regular), irregular=int(rc.irregular), invalid=int(rc.invalid),
+                    first_invalid=int(rc.first_invalid))
+
 
 def accum_file_info(path):
     """Header of a checkpoint file (pt_accum_file_info, host-only): dict of params (spp = 0), camera,

@@ -75,6 +75,13 @@
 //                                         frame's temporal image; --denoise-guided filters it with the temporal variance (no
 //                                         estimator needed), --variance-map writes that variance.  --gpus 1 only; not with the
 //                                         accumulating modes, --look-at or --cam (the poses place and aim the camera)
+// --rays FILE                             render along the caller's rays instead of a camera's (pt_render_rays): FILE is raw
+//                                         little-endian float32, 6 * W * H values {o.xyz, d.xyz} in scanline order, with
+//                                         --width / --height / --spp and the usual output options (--morton permutes the
+//                                         rays into the Morton-indexed buffer's order).  Not with the camera, view, jitter,
+//                                         checkpoint, session, temporal, adaptive, denoising or --aov options, --tri-counts
+//                                         or --gpus above 1: an error.  A ray far outside the scene or with an unnormalised
+//                                         direction sends the whole render to the slow exact walk (pt.h)
 // --aov PREFIX                            write the primary-hit feature buffers as PREFIX_albedo.pfm,
 //                                         PREFIX_normal.pfm, PREFIX_position.pfm and PREFIX_depth.pfm (depth
 //                                         replicated to 3 channels)
@@ -110,7 +117,7 @@ struct Obj {
             "              [--checkpoint FILE] [--resume FILE] [--pass-spp K]\n"
             "              [--session FILE] [--resume-session FILE]\n"
             "              [--denoise [ITERS]] [--aov PREFIX]\n"
-            "              [--camera-path FILE --temporal [--temporal-max N]]\n"
+            "              [--camera-path FILE --temporal [--temporal-max N]] [--rays FILE]\n"
             "              [--until-error TOL [--error-quantile Q] [--min-batches B] [--adaptive]] [--error-map FILE.pfm]\n"
             "              [--count-map FILE.pfm] [--denoise-guided [ITERS] [--sigma-luma S]] [--variance-map FILE.pfm]\n"
             "  --until-error TOL  with --pass-spp: stop once the fraction Q (default 0.95) of the pixels has a relative\n"
@@ -132,6 +139,8 @@ struct Obj {
             "                     --spp with seed --seed + frame and pushed through a temporal history (--temporal-max N caps its\n"
             "                     length, default 32); the files hold the last frame's temporal image; --denoise-guided and\n"
             "                     --variance-map use the temporal variance\n"
+            "  --rays FILE        render along the rays of FILE (raw float32, 6*W*H values {o.xyz, d.xyz}, scanline order) instead\n"
+            "                     of a camera's; not with the camera, view, jitter, accumulating, temporal or denoising options\n"
             "  --aov PREFIX       write PREFIX_albedo.pfm, PREFIX_normal.pfm, PREFIX_position.pfm, PREFIX_depth.pfm\n");
     exit(2);
 }
@@ -225,6 +234,7 @@ int main(int argc, char** argv)
     pt_denoise_guided_defaults(&gparams);
     std::string variance_map;
     std::string aov;
+    std::string rays_path;     // --rays FILE
     std::string camera_path;   // --camera-path FILE --temporal [--temporal-max N]
     bool temporal = false;
     pt_temporal_params tparams;
@@ -291,6 +301,7 @@ int main(int argc, char** argv)
         else if (a == "--sigma-luma") gparams.sigma_luma = strtof(next().c_str(), nullptr);
         else if (a == "--variance-map") variance_map = next();
         else if (a == "--aov") aov = next();
+        else if (a == "--rays") rays_path = next();
         else if (a == "--camera-path") camera_path = next();
         else if (a == "--temporal") temporal = true;
         else if (a == "--temporal-max") { tparams.max_history = atoi(next().c_str()); if (tparams.max_history < 1) usage("--temporal-max must be >= 1"); }
@@ -325,6 +336,40 @@ int main(int argc, char** argv)
     }
     if (objs.empty()) usage("at least one --obj is required");
     if (gpus < 1) usage("--gpus must be >= 1");
+    std::vector<float> rays;   // --rays: the buffer in the render's pixel order
+    if (!rays_path.empty()) {
+        // a render along rays takes no camera and has neither accumulator nor features (pt.h): every option of those is an error
+        for (const std::string& g : given)
+            for (const char* o : {"--cam", "--dist", "--focal", "--radius", "--look-at", "--up", "--vfov", "--film", "--jitter",
+                                  "--checkpoint", "--resume", "--session", "--resume-session", "--pass-spp", "--camera-path",
+                                  "--temporal", "--temporal-max", "--until-error", "--error-quantile", "--min-batches", "--error-map",
+                                  "--adaptive", "--count-map", "--denoise", "--denoise-guided", "--sigma-luma", "--variance-map",
+                                  "--aov", "--tri-counts"})
+                if (g == o) usage(("--rays cannot be combined with " + g).c_str());
+        if (gpus != 1) usage("--rays needs --gpus 1");
+        if (p.width <= 0 || p.height <= 0 || p.width > 65535 || p.height > 65535) usage("--rays: bad --width / --height");
+        const size_t npx = (size_t)p.width * p.height;
+        FILE* f = fopen(rays_path.c_str(), "rb");
+        if (!f) { fprintf(stderr, "pt_cli: --rays: cannot read %s\n", rays_path.c_str()); return 2; }
+        std::vector<float> scan(npx * 6);
+        const size_t got = fread(scan.data(), sizeof(float), scan.size(), f);
+        const bool more = got == scan.size() && fgetc(f) != EOF;
+        fclose(f);
+        if (got != scan.size() || more) {
+            fprintf(stderr, "pt_cli: --rays: %s does not hold %zu float32 values (6 per pixel of %dx%d)\n", rays_path.c_str(), scan.size(),
+                    p.width, p.height);
+            return 2;
+        }
+        if (p.pixel_order == PT_ORDER_MORTON) {
+            rays.assign(scan.size(), 0.0f);   // (a size the library refuses leaves the zeros: its message is the error)
+            const bool square = p.width == p.height && (p.width & (p.width - 1)) == 0;
+            for (int y = 0; square && y < p.height; ++y)
+                for (int x = 0; x < p.width; ++x)
+                    memcpy(&rays[(size_t)pt_morton_pxl_to_i(x, y) * 6], &scan[((size_t)y * p.width + x) * 6], 24);
+        } else {
+            rays.swap(scan);
+        }
+    }
     if (!tri_csv.empty() && gpus != 1) usage("--tri-counts needs --gpus 1");
     if (!tri_csv.empty()) p.flags |= PT_FLAG_COUNT | PT_FLAG_TRI_COUNTS;
     // --reference-walk: the reference's own trace() sequence for every sample (its node order, the
@@ -631,6 +676,8 @@ int main(int argc, char** argv)
                 }
             if (pt_write_pfm(variance_map.c_str(), grey.data(), p.width, p.height) != PT_OK) return die("--variance-map");
         }
+    } else if (!rays.empty()) {
+        if (pt_render_rays(ctx[0], &p, rays.data(), img.data(), &st) != PT_OK) return die("pt_render_rays");
     } else {
         // one GPU: pt_render; N GPUs: image-tile shards on devices 0..N-1 summed by one RCCL reduce
         const int rc = (gpus == 1) ? pt_render_view(ctx[0], &p, &cam, cam_view, img.data(), &st)

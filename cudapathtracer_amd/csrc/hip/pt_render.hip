@@ -138,6 +138,12 @@ struct Args {
     float view_right[3], view_up[3], view_back[3];   // world-space images of camera +x, +y, +z
     float film_w, film_h;           // film extent (1, 1 = the reference's unit square)
 };
+// A render along a caller's rays (pt_render_rays*): Args with the ray buffer appended at its end.  Only the kRays
+// kernels take it -- as their one struct argument, so what they share with the other kernels reads it as the Args it
+// begins with -- and every other kernel keeps its argument block, byte for byte.
+struct RayArgs : Args {
+    const float* rays;              // {o.xyz, d.xyz} of pixel (x, y) at its out_pixel index
+};
 // Slots of Args::counters: the kernels add to them; pt_render_wait (pt_stats, PT_SECTION_DUMP) and
 // pt_trace_counts read them.
 enum : uint32_t {
@@ -151,6 +157,7 @@ enum : uint32_t {
 };
 static_assert(offsetof(Args, origin_max) + 4 == offsetof(Args, acc_rng), "origin_max sits in Args' padding");
 static_assert(offsetof(Args, oriented) == offsetof(Args, acc_mean) + 8, "the view's words follow everything else");
+static_assert(sizeof(Args) % 8 == 0 && sizeof(RayArgs) == sizeof(Args) + 8, "the ray buffer directly follows Args");
 constexpr int kCounterWords = 96;
 // Unit words of an accumulating pass: UW_N0 bit 30 marks a pixel's first unit of the pass (chunk 0, or the
 // whole pixel) -- `n == 1` no longer does; its sample numbers are the 30 bits below.
@@ -700,6 +707,19 @@ __device__ __forceinline__ size_t out_pixel(const Args& a, uint32_t px, uint32_t
     return a.morton_out ? (size_t)morton2(px, py) : (size_t)py * (size_t)a.w + px;
 }
 
+// A render along a caller's rays (the kRays kernels, whose argument block `a` is the head of a RayArgs): the origin
+// and the direction of pixel (px, py), as given.
+__device__ __forceinline__ V3 ray_origin(const Args& a, uint32_t px, uint32_t py)
+{
+    const float* r = static_cast<const RayArgs&>(a).rays + out_pixel(a, px, py) * 6;
+    return v3(r[0], r[1], r[2]);
+}
+__device__ __forceinline__ V3 ray_direction(const Args& a, uint32_t px, uint32_t py)
+{
+    const float* r = static_cast<const RayArgs&>(a).rays + out_pixel(a, px, py) * 6 + 3;
+    return v3(r[0], r[1], r[2]);
+}
+
 __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
 {
 #pragma unroll
@@ -711,8 +731,10 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
 // (kView: the camera ray goes through the view, camera_ray_view -- render_tiles_view, kernels of their own launched
 // for an oriented render, so that the plain ones keep their names and compile exactly as they did without it;
 // kJit: a jittered render, render_tiles_jitter -- every sample draws its film point first and forms its own ray,
-// through the view or not (a.oriented), and the primary memo is off)
-template <int kIntegrator, bool kRefWalk, bool kCount, bool kView, bool kJit = false>
+// through the view or not (a.oriented), and the primary memo is off;
+// kRays: a render along the caller's rays, render_tiles_rays -- the pixel's ray is read from RayArgs::rays, no sample
+// draws a lens pair, Morton index 0 included, and the ray is the same for every sample, so the memo works)
+template <int kIntegrator, bool kRefWalk, bool kCount, bool kView, bool kJit = false, bool kRays = false>
 __device__ __forceinline__ void render_tiles_body(Args& a)
 {
     extern __shared__ uint32_t lds_stack[];
@@ -737,7 +759,7 @@ __device__ __forceinline__ void render_tiles_body(Args& a)
         const uint32_t idx = morton2(px, py);
         Rng rng;
         rng_init(rng, a.seed, idx, a.jump);
-        const bool lens = (idx == 0) || (a.cam.radius != 0.0f);
+        const bool lens = !kRays && ((idx == 0) || (a.cam.radius != 0.0f));
         tr.have = false;
         double m0 = 0.0, m1 = 0.0, m2 = 0.0;
         for (int n = 1; n <= a.spp; ++n) {
@@ -748,7 +770,8 @@ __device__ __forceinline__ void render_tiles_body(Args& a)
             }
             if (lens) { u1 = rng_uniform(rng); u2 = rng_uniform(rng); }
             V3 o, d;
-            if (kJit) camera_ray_jitter<false>(a, px, py, jx, jy, lens, u1, u2, &o, &d);
+            if (kRays) { o = ray_origin(a, px, py); d = ray_direction(a, px, py); }
+            else if (kJit) camera_ray_jitter<false>(a, px, py, jx, jy, lens, u1, u2, &o, &d);
             else if (kView) camera_ray_view<false>(a, px, py, lens, u1, u2, &o, &d);
             else camera_ray<false>(a.cam, px, py, lens, u1, u2, &o, &d);
             C3 L;
@@ -980,8 +1003,10 @@ __device__ __forceinline__ void reset_render_counters(const Args& a)
 // machine loads 20 B instead of running the jump-ahead with its wave waiting.
 // (kJit: the set-up of a jittered render, init_pixel_states_jitter.  No pixel of it has a sample-invariant ray, so
 // every unit is marked as a lens unit is -- the ray is formed per sample: no UW_CD direction, no CF_CAMC, no memo --
-// and the replay skips two more draws per sample.)
-template <bool kJit>
+// and the replay skips two more draws per sample.
+// kRays: the set-up of a render along the caller's rays, init_pixel_states_rays.  Every unit is a pinhole unit whose
+// direction is the pixel's in RayArgs::rays -- Morton index 0 too: no sample draws a lens pair -- so the memos work.)
+template <bool kJit, bool kRays = false>
 __device__ __forceinline__ void init_pixel_states_body(const Args& a, uint32_t* __restrict__ st)
 {
     // one lane per pixel slot: curand_init, then one pass over the samples that writes the state
@@ -1017,9 +1042,9 @@ __device__ __forceinline__ void init_pixel_states_body(const Args& a, uint32_t* 
     Rng r;
     const uint32_t n_done = a.accum ? a.acc_n0 : 0u;   // samples the pixel has before this render
     slot_stream(a, q, idx, n_done, r);
-    const bool lens = (idx == 0) || (a.cam.radius != 0.0f);
+    const bool lens = !kRays && ((idx == 0) || (a.cam.radius != 0.0f));
     const bool per_sample = kJit || lens;   // the unit's mark: its rays are formed per sample
-    const V3 d = pinhole_dir(a, px, py, per_sample);
+    const V3 d = kRays ? ray_direction(a, px, py) : pinhole_dir(a, px, py, per_sample);
     uint32_t done = 0;
     for (uint32_t c = 0; c < nc; ++c) {
         const uint32_t s0 = split ? chunk_first(a, c, nc) : 0u;
@@ -1377,7 +1402,9 @@ __device__ __forceinline__ void finish_pixel(const Args& a, uint32_t slot, uint3
 // kJit: a jittered render (PT_FLAG_JITTER; instances of their own for the same reason).  Every unit arrives as a lens
 // unit (CF_LENS: the ray is formed per sample, so no CF_CAMC and no memo of any kind); a sample draws its film point
 // first, then the lens pair if its pixel is a lens pixel (lens_pixel), and takes the view under a.oriented.
-template <bool kCount, bool kAccum, bool kView = false, bool kJit = false>
+// kRays: a render along the caller's rays (RayArgs::rays; instances of their own again).  Every unit arrives as a
+// pinhole unit with its direction present (CF_CAMC); a sample's origin is read from the buffer by the pixel's index.
+template <bool kCount, bool kAccum, bool kView = false, bool kJit = false, bool kRays = false>
 __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, int lane, uint32_t& state, V3& ro, V3& rd,
                                            int32_t& htri, float& ht, W4& w, const Stack4& S,
                                            unsigned long long* lcnt, const uint32_t* lprobe, uint32_t* done_rel,
@@ -1434,7 +1461,7 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
         fl |= CF_ACC0;   // acc = 0 (stored on the sample's first emission)
         wgt = c3(1, 1, 1);
         float u1 = 0.0f, u2 = 0.0f;
-        const bool lens = (fl & CF_LENS) != 0u;
+        const bool lens = !kRays && (fl & CF_LENS) != 0u;
         float jx = 0.0f, jy = 0.0f;
         bool pair = lens;   // the sample draws a lens pair
         if (kJit) {
@@ -1444,7 +1471,7 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
         }
         if (pair) { u1 = rng_uniform(rng); u2 = rng_uniform(rng); }
         SEC(SEC_START);
-        if (lens || !(fl & CF_CAMC)) {
+        if (!kRays && (lens || !(fl & CF_CAMC))) {
             SEC(SEC_CAMERA);
             if (kJit) camera_ray_jitter(a, px, py, jx, jy, pair, u1, u2, &ro, &rd);
             else if (kView) camera_ray_view(a, px, py, lens, u1, u2, &ro, &rd);
@@ -1454,7 +1481,8 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
                 fl |= CF_CAMC;
             }
         } else {
-            ro = v3(0.0f, 0.0f, 0.0f) + v3(fresh(a.cam.pos[0]), fresh(a.cam.pos[1]), fresh(a.cam.pos[2]));   // as camera_ray forms it
+            if (kRays) ro = ray_origin(a, px, py);   // (12 bytes per sample start; the direction is the record's)
+            else ro = v3(0.0f, 0.0f, 0.0f) + v3(fresh(a.cam.pos[0]), fresh(a.cam.pos[1]), fresh(a.cam.pos[2]));   // as camera_ray forms it
             const uint4 cd = have_cells ? c8 : R.ld4(CW_CD);
             rd = v3(__uint_as_float(cd.x), __uint_as_float(cd.y), __uint_as_float(cd.z));
         }
@@ -1917,7 +1945,10 @@ __device__ __forceinline__ float head_vis_occluded(float len)
 }
 
 // (kJit: a jittered render, as shade_lane's: instances of their own)
-template <bool kCount, bool kAccum, bool kJit = false>
+// (kRays: a render along the caller's rays, instances of their own too.  A unit is a pinhole unit whose camera vertex
+// is the ray's origin: written to HW_CO once, when the unit is taken, beside the direction in HW_CD, and read from
+// there by every sample's camera stage -- so the memo path is the pinhole unit's.)
+template <bool kCount, bool kAccum, bool kJit = false, bool kRays = false>
 __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint32_t& state, V3& ro, V3& rd,
                                                 int32_t& htri, float& ht, W4& w, const Stack4& S,
                                                 unsigned long long* lcnt, const uint32_t* lprobe, uint32_t* done_rel,
@@ -1964,7 +1995,7 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
             rng.v0 = k1.x; rng.v1 = k1.y; rng.v2 = k1.z; rng.v3 = k1.w;
             rng.v4 = R.ld(HW_RNG_V4);
         }
-        const bool lens = (fl & CF_LENS) != 0u;
+        const bool lens = !kRays && (fl & CF_LENS) != 0u;
         float lu1 = 0.0f, lu2 = 0.0f;
         float jx = 0.0f, jy = 0.0f;
         bool pair = lens;   // the sample draws a lens pair
@@ -2029,8 +2060,8 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
         wave_count(lcnt + 1, lane);
         const uint4 cd = R.ld4(HW_CD);
         rd = v3(__uint_as_float(cd.x), __uint_as_float(cd.y), __uint_as_float(cd.z));
-        const bool lens = (fl & CF_LENS) != 0u;
-        if (lens) {
+        const bool lens = !kRays && (fl & CF_LENS) != 0u;
+        if (kRays || lens) {
             const uint4 co = R.ld4(HW_CO);
             ro = v3(__uint_as_float(co.x), __uint_as_float(co.y), __uint_as_float(co.z));
         } else {
@@ -2268,6 +2299,10 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
                       if (!(fl & CF_LENS))
                           R.st4(HW_CD, a.pix_states[UW_CD * N + u], a.pix_states[(UW_CD + 1) * N + u],
                                 a.pix_states[(UW_CD + 2) * N + u], 0u);
+                      if (kRays) {   // the unit's camera vertex: the ray's origin, once
+                          const V3 co = ray_origin(a, pxy & 0xffffu, pxy >> 16);
+                          R.st4(HW_CO, __float_as_uint(co.x), __float_as_uint(co.y), __float_as_uint(co.z), 0u);
+                      }
                       if (split) fl |= CF_SPLIT;
                       if (split && !(fl & CF_LENS) && !(a.flags & PT_FLAG_NO_PRIMARY_CACHE))
                           fl |= first ? CF_OWNER : CF_SHARE;
@@ -2303,7 +2338,8 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
 // The wavefront kernel's body, shared by both integrators (kHead: integrator 1, shade_lane_head).
 // kLdsWalk: walk steps read the staged top from LDS (integrator 1 always; integrator 0 when the LDS
 // top holds the whole tree) instead of issuing every node's loads to memory.
-template <bool kCount, bool kHead, bool kLdsWalk = kHead, bool kAccum = false, bool kView = false, bool kJit = false>
+template <bool kCount, bool kHead, bool kLdsWalk = kHead, bool kAccum = false, bool kView = false, bool kJit = false,
+          bool kRays = false>
 __device__ __forceinline__ void wf_main(const Args& a)
 {
     extern __shared__ uint32_t lds_wf[];
@@ -2444,8 +2480,8 @@ __device__ __forceinline__ void wf_main(const Args& a)
         if (kCount) ++shade_slots;
         // (the lane id is recomputed for the shading pass: one VGPR less live across the walk loop)
         if (state != ST_TRACE && state != ST_DONE) {
-            if (kHead) shade_lane_head<kCount, kAccum, kJit>(R, (int)__lane_id(), state, ro, rd, htri, ht, w, S, lcnt, lprobe, done_rel, cnt);
-            else shade_lane<kCount, kAccum, kView, kJit>(a, R, (int)__lane_id(), state, ro, rd, htri, ht, w, S, lcnt, lprobe, done_rel, cnt);
+            if (kHead) shade_lane_head<kCount, kAccum, kJit, kRays>(R, (int)__lane_id(), state, ro, rd, htri, ht, w, S, lcnt, lprobe, done_rel, cnt);
+            else shade_lane<kCount, kAccum, kView, kJit, kRays>(a, R, (int)__lane_id(), state, ro, rd, htri, ht, w, S, lcnt, lprobe, done_rel, cnt);
         }
         if (kCount) shade_clk += clock64() - clk0;
         if (__ballot(state != ST_DONE) == 0ull) break;
@@ -2887,6 +2923,29 @@ __global__ __launch_bounds__(256) void query_rays(Args a, const float* __restric
             if (!drained && 64u - (uint32_t)__popcll(walking) >= refill_at) break;
         }
     }
+}
+
+// ------------------------------------------------------------------ renders along caller-supplied rays
+// pt_render_rays*: the kernels of a render whose rays come from RayArgs::rays (kRays) -- the set-up kernel, the two
+// integrators' wavefront kernels at the default occupancy (integrator 0's with its LDS-walk twin) and the tile kernel
+// -- defined and first used after every other kernel, which therefore compile as they did.
+__global__ __launch_bounds__(256) void init_pixel_states_rays(RayArgs a, uint32_t* __restrict__ st)
+{
+    init_pixel_states_body<false, true>(a, st);
+}
+template <bool kLdsWalk>
+__global__ __launch_bounds__(256, 5) void render_unidir_rays_wf(RayArgs a)
+{
+    wf_main<false, false, kLdsWalk, false, false, false, true>(a);
+}
+__global__ __launch_bounds__(256, 5) void render_head_rays_wf(RayArgs a)
+{
+    wf_main<false, true, true, false, false, false, true>(a);
+}
+template <int kIntegrator, bool kRefWalk, bool kCount>
+__global__ __launch_bounds__(64) void render_tiles_rays(RayArgs a)
+{
+    render_tiles_body<kIntegrator, kRefWalk, kCount, false, false, true>(a);
 }
 
 }  // namespace

@@ -80,6 +80,10 @@ struct pt_ctx : pt::SceneInfo {            // (the scene's scalars: pt_scene_pac
     pt::SessionScratch session;       // pt_session_save / _load's staging (pt_session.cpp), grown on demand
     uint8_t* query_stage = nullptr;   // pt_occluded's device staging (rays, bounds, answers), grown on demand
     size_t query_stage_bytes = 0;
+    uint32_t* ray_classes = nullptr;  // classify_rays' four words (pt_render_rays*, pt_rays_classify_device)
+    size_t ray_classes_words = 0;
+    float* rays_stage = nullptr;      // pt_render_rays' device staging of the host ray buffer, grown on demand
+    size_t rays_stage_floats = 0;
 };
 
 int pt::ctx_device(const pt_ctx* c) { return c->device; }
@@ -201,7 +205,8 @@ void pt_destroy(pt_ctx* c)
     void* bufs[] = {c->nodes, c->rnodes, c->tris_leaf, c->tris_orig, c->shade, c->mats,
                     c->lights, c->jump, c->jump_bytes, c->shade_m, c->scratch_out,
                     c->nodes4, c->acc_tris, c->rparent, c->hrec,
-                    c->tone_thr, c->spheres, c->tri_counts, c->emis, c->denoise.mem, c->session.dev, c->query_stage};
+                    c->tone_thr, c->spheres, c->tri_counts, c->emis, c->denoise.mem, c->session.dev, c->query_stage,
+                    c->ray_classes, c->rays_stage};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     pt::free_pinned(c->session.host);
@@ -453,7 +458,10 @@ struct LaneTiming {
 // The integration kernel of a wavefront render: the instance pt::wavefront_variant names.  An oriented render
 // (b.oriented) of integrator 0 takes that instance's view twin; integrator 1's instances serve both.  A jittered
 // render (PT_FLAG_JITTER) takes the instance's jitter twin, which serves both cameras.
-static int launch_wavefront(const pt::WavefrontVariant& v, const WavefrontLaunch& L, hipStream_t stream, const Args& b)
+// A render along a caller's rays (rays != null) takes the ray-source instance, whose argument block is b with the
+// buffer appended (RayArgs).
+static int launch_wavefront(const pt::WavefrontVariant& v, const WavefrontLaunch& L, hipStream_t stream, const Args& b,
+                            const float* rays = nullptr)
 {
     constexpr auto code = [](bool head, bool count, int min_waves, bool lds_walk, bool accum) {
         return pt::WavefrontVariant{head, count, min_waves, lds_walk, accum}.code();
@@ -513,13 +521,34 @@ static int launch_wavefront(const pt::WavefrontVariant& v, const WavefrontLaunch
                             v.head, v.count, v.min_waves, v.lds_walk, v.accum);
         }
     }
+    if (rays) {   // (the ray-source instances, default occupancy only: below every other instance again)
+        void (*rkernel)(RayArgs) = nullptr;
+        switch (v.code()) {
+        case code(true, false, 5, false, false): rkernel = render_head_rays_wf; break;
+        case code(false, false, 5, true, false): rkernel = render_unidir_rays_wf<true>; break;
+        case code(false, false, 5, false, false): rkernel = render_unidir_rays_wf<false>; break;
+        default:
+            return pt::fail(PT_E_INVALID, "pt_render_rays: no ray-source wavefront kernel instance for head %d count %d waves %d lds %d "
+                            "accum %d (only the default PT_WF_MIN_WAVES / PT_HEAD_MIN_WAVES have one)",
+                            v.head, v.count, v.min_waves, v.lds_walk, v.accum);
+        }
+        RayArgs rb;
+        static_cast<Args&>(rb) = b;
+        rb.rays = rays;
+        hipLaunchKernelGGL(rkernel, dim3(L.blocks), dim3(256), L.lds, stream, rb);
+        HIP_TRY(hipGetLastError());
+        return PT_OK;
+    }
     hipLaunchKernelGGL(kernel, dim3(L.blocks), dim3(256), L.lds, stream, b);
     HIP_TRY(hipGetLastError());
     return PT_OK;
 }
 
 // The tile kernel of a render the wavefront kernels do not take: one wave per 8x8 block of the shard's tiles.
-static int launch_tiles(const pt_ctx* c, const pt_params* p, pt_ctx::Bufs& B, size_t lds, hipStream_t stream, Args& a)
+// (rays: a render along a caller's rays; rays_refwalk: it takes the reference's own walk -- an irregular buffer or
+// one of the two reference flags)
+static int launch_tiles(const pt_ctx* c, const pt_params* p, pt_ctx::Bufs& B, size_t lds, hipStream_t stream, Args& a,
+                        const float* rays, bool rays_refwalk)
 {
     uint32_t grid = (uint32_t)c->num_cus * 16;   // waves per CU
     if (grid > a.ntiles_shard * a.tile_blocks) grid = a.ntiles_shard > 0 ? a.ntiles_shard * a.tile_blocks : 1;
@@ -533,8 +562,11 @@ static int launch_tiles(const pt_ctx* c, const pt_params* p, pt_ctx::Bufs& B, si
 #define PT_LAUNCH(I, R, C) hipLaunchKernelGGL((render_tiles<I, R, C>), dim3(grid), dim3(64), lds, stream, a)
 #define PT_LAUNCH_VIEW(I, R, C) hipLaunchKernelGGL((render_tiles_view<I, R, C>), dim3(grid), dim3(64), lds, stream, a)
 #define PT_LAUNCH_JITTER(I, R, C) hipLaunchKernelGGL((render_tiles_jitter<I, R, C>), dim3(grid), dim3(64), lds, stream, a)
+#define PT_LAUNCH_RAYS(I, R) hipLaunchKernelGGL((render_tiles_rays<I, R, false>), dim3(grid), dim3(64), lds, stream, ra)
     const bool jitter = (p->flags & PT_FLAG_JITTER) != 0;
-    if (!a.oriented && !jitter) {
+    if (rays) {
+        // (the ray-source instances: run only here, and first used below every other instance)
+    } else if (!a.oriented && !jitter) {
     if (p->integrator == PT_INTEGRATOR_HEAD) {
         if (refwalk) { if (count) PT_LAUNCH(1, true, true); else PT_LAUNCH(1, true, false); }
         else { if (count) PT_LAUNCH(1, false, true); else PT_LAUNCH(1, false, false); }
@@ -555,6 +587,14 @@ static int launch_tiles(const pt_ctx* c, const pt_params* p, pt_ctx::Bufs& B, si
         if (refwalk) { if (count) PT_LAUNCH_JITTER(0, true, true); else PT_LAUNCH_JITTER(0, true, false); }
         else { if (count) PT_LAUNCH_JITTER(0, false, true); else PT_LAUNCH_JITTER(0, false, false); }
     }
+    if (rays) {
+        RayArgs ra;
+        static_cast<Args&>(ra) = a;
+        ra.rays = rays;
+        if (p->integrator == PT_INTEGRATOR_HEAD) { if (rays_refwalk) PT_LAUNCH_RAYS(1, true); else PT_LAUNCH_RAYS(1, false); }
+        else { if (rays_refwalk) PT_LAUNCH_RAYS(0, true); else PT_LAUNCH_RAYS(0, false); }
+    }
+#undef PT_LAUNCH_RAYS
 #undef PT_LAUNCH_JITTER
 #undef PT_LAUNCH_VIEW
 #undef PT_LAUNCH
@@ -569,8 +609,9 @@ struct WavefrontDone {
 };
 
 // The wavefront path of one render, from its plan to finalize_pixels.  a: the render's Args; F: its flight slot.
+// (rays: a render along a caller's rays, or null)
 static int enqueue_wavefront(pt_ctx* c, const pt_params* p, const pt::AccumPass* acc, const Args& a, pt_ctx::Flight& F,
-                             pt_ctx::Bufs& B, hipStream_t stream, WavefrontDone* done)
+                             pt_ctx::Bufs& B, hipStream_t stream, WavefrontDone* done, const float* rays)
 {
     const pt::RenderKnobs& K = c->knobs;
     Args b = a;
@@ -588,9 +629,15 @@ static int enqueue_wavefront(pt_ctx* c, const pt_params* p, const pt::AccumPass*
     if (acc && acc->active)
         hipLaunchKernelGGL(jitter ? init_active_states_jitter : init_active_states, dim3((b.nunits + 255) / 256), dim3(256), 0,
                            stream, b, B.pix_states, acc->active);
-    else
+    else if (!rays)
         hipLaunchKernelGGL(jitter ? init_pixel_states_jitter : init_pixel_states, dim3((b.npix + 255) / 256), dim3(256), 0, stream,
                            b, B.pix_states);
+    else {   // (a render along rays: the set-up that reads each unit's direction from the buffer)
+        RayArgs rb;
+        static_cast<Args&>(rb) = b;
+        rb.rays = rays;
+        hipLaunchKernelGGL(init_pixel_states_rays, dim3((b.npix + 255) / 256), dim3(256), 0, stream, rb, B.pix_states);
+    }
     // A render queued on another stream while one is in flight: its seeding pre-pass runs beside the
     // earlier render's last waves (its own buffers), but the integration kernel waits until the earlier
     // render is complete (finalisation included), so a persistent grid never takes the CU slots an
@@ -601,7 +648,7 @@ static int enqueue_wavefront(pt_ctx* c, const pt_params* p, const pt::AccumPass*
     done->split = b.ntail;
     const pt::WavefrontVariant v = pt::wavefront_variant(b.head != 0, (p->flags & PT_FLAG_COUNT) != 0, acc != nullptr, L.lds_tree,
                                                          K.wf_min_waves, K.head_min_waves);
-    if (int rc = launch_wavefront(v, L, stream, b)) return rc;
+    if (int rc = launch_wavefront(v, L, stream, b, rays)) return rc;
     HIP_TRY(hipEventRecord(F.ek1, stream));
     if (b.ntail > 0) hipLaunchKernelGGL(finalize_pixels, dim3((b.ntail + 255) / 256), dim3(256), 0, stream, b);
     HIP_TRY(hipGetLastError());
@@ -612,8 +659,11 @@ static int enqueue_wavefront(pt_ctx* c, const pt_params* p, const pt::AccumPass*
 // acc: the render is a pass of an accumulator (pt::accum_pass) -- p->spp more samples of every pixel on top
 // of its acc->n0, from and to the accumulator's state; d_out may then be null.  Everything else -- the
 // unit split, the buffers' growth, the jump and seed tables, the flight slots -- is the plain render's.
+// d_rays: a render along the caller's rays (pt_render_rays_device, which has classified them; cam is then a
+// stand-in that only carries the image size); rays_irregular: the buffer holds an irregular ray, so the whole render
+// takes the tile kernel with the reference's own walk.
 static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view, float* d_out, void* stream_v,
-                          const pt::AccumPass* acc)
+                          const pt::AccumPass* acc, const float* d_rays = nullptr, bool rays_irregular = false)
 {
     if (!c || !p || !cam || (!d_out && !acc)) return pt::fail(PT_E_INVALID, "pt_render: null argument");
     if (c->fl_n >= pt_ctx::kFlights)
@@ -660,8 +710,12 @@ static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, c
     // the tile kernel traces with the render-path BVH4 walk under the wavefront kernel's conditions
     // (PT_TILE_FAST4=0: the reference-BVH culled walk, as before)
     a.tile_fast4 = (!(p->flags & (PT_FLAG_REFERENCE_TRAVERSAL | PT_FLAG_REFERENCE_BVH)) && pt::near_camera(cam, c->scene_extent) &&
-                    K.tile_fast4 && c->num_tris > 0) ? 1u : 0u;
-    const bool wavefront = pt::takes_wavefront(p, cam, c->scene_extent, K.head_wf);
+                    !rays_irregular && K.tile_fast4 && c->num_tris > 0) ? 1u : 0u;
+    const bool wavefront = pt::takes_wavefront(p, cam, c->scene_extent, K.head_wf) && !rays_irregular;
+    const bool rays_refwalk = d_rays && (rays_irregular || (p->flags & (PT_FLAG_REFERENCE_TRAVERSAL | PT_FLAG_REFERENCE_BVH)) != 0);
+    if (d_rays && wavefront && (K.wf_min_waves != 5 || K.head_min_waves != 5))   // (never another kernel in silence)
+        return pt::fail(PT_E_INVALID, "pt_render_rays: only the default-occupancy wavefront kernels take a ray buffer "
+                        "(PT_WF_MIN_WAVES / PT_HEAD_MIN_WAVES are set)");
     if (acc) {   // (pt_accum_create refused these already: never a silent fall-back to another kernel)
         if (!wavefront || count || K.wf_min_waves != 5 || K.head_min_waves != 5)
             return pt::fail(PT_E_INVALID, "pt_accum_add: this mode has no accumulating kernel");
@@ -682,9 +736,9 @@ static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, c
     HIP_TRY(hipEventRecord(F.ev0, stream));
     WavefrontDone wf;
     if (has_work && wavefront) {
-        if (int rc = enqueue_wavefront(c, p, acc, a, F, B, stream, &wf)) return rc;
+        if (int rc = enqueue_wavefront(c, p, acc, a, F, B, stream, &wf, d_rays)) return rc;
     } else if (has_work) {
-        if (int rc = launch_tiles(c, p, B, lds, stream, a)) return rc;
+        if (int rc = launch_tiles(c, p, B, lds, stream, a, d_rays, rays_refwalk)) return rc;
     }
     HIP_TRY(hipEventRecord(F.ev1, stream));
     HIP_TRY(hipMemcpyAsync(F.hcnt, B.counters, kCounterWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
@@ -1097,6 +1151,75 @@ extern "C" int pt_occluded(pt_ctx* c, uint32_t n, const float* rays, const float
     if (int rc = query_run(c, true, false, n, d_rays, tmax ? d_tmax : nullptr, nullptr, nullptr, d_occ, nullptr)) return rc;
     HIP_TRY(hipMemcpy(occ, d_occ, n, hipMemcpyDeviceToHost));
     return PT_OK;
+}
+
+// ---- renders along caller-supplied rays (pt_render_rays_device, pt_render_rays, pt_rays_classify_device)
+
+// The classes of n rays at d_rays, through the context's four words: what both entry points below run first.
+static int classify_ctx_rays(pt_ctx* c, const char* who, uint32_t n, const float* d_rays, hipStream_t stream, pt_ray_classes* out)
+{
+    if (reinterpret_cast<uintptr_t>(d_rays) % 8 != 0) return pt::fail(PT_E_INVALID, "%s: the ray buffer must be 8-byte aligned", who);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = pt::grow(&c->ray_classes, &c->ray_classes_words, 4)) return rc;
+    return pt::classify_ray_buffer(d_rays, n, 64.0f * c->scene_extent, c->num_cus, c->ray_classes, stream, out);
+}
+
+extern "C" int pt_rays_classify_device(pt_ctx* c, uint32_t n, const float* d_rays, void* stream, pt_ray_classes* out)
+{
+    pt::clear_error();
+    if (!c || !out) return pt::fail(PT_E_INVALID, "pt_rays_classify_device: null argument");
+    if (n > 0 && !d_rays) return pt::fail(PT_E_INVALID, "pt_rays_classify_device: null buffer");
+    if (c->fl_n > 0)
+        return pt::fail(PT_E_INVALID, "pt_rays_classify_device: %d asynchronous renders in flight (pt_render_wait first)", c->fl_n);
+    return classify_ctx_rays(c, "pt_rays_classify_device", n, d_rays, reinterpret_cast<hipStream_t>(stream), out);
+}
+
+extern "C" int pt_render_rays_device(pt_ctx* c, const pt_params* p, const float* d_rays, float* d_out, void* stream, pt_stats* st)
+{
+    pt::clear_error();
+    if (!c || !p || !d_rays || !d_out) return pt::fail(PT_E_INVALID, "pt_render_rays: null argument");
+    if (c->fl_n > 0)
+        return pt::fail(PT_E_INVALID, "pt_render_rays: %d asynchronous renders in flight (pt_render_wait first)", c->fl_n);
+    constexpr uint32_t allowed = PT_FLAG_NO_DEAD_PATH_SKIP | PT_FLAG_NO_PRIMARY_CACHE | PT_FLAG_REFERENCE_TRAVERSAL | PT_FLAG_REFERENCE_BVH;
+    if (p->flags & ~allowed)
+        return pt::fail(PT_E_INVALID, "pt_render_rays: flags 0x%x: a render along rays takes only PT_FLAG_NO_DEAD_PATH_SKIP, "
+                        "PT_FLAG_NO_PRIMARY_CACHE, PT_FLAG_REFERENCE_TRAVERSAL and PT_FLAG_REFERENCE_BVH (no counting variants, and "
+                        "no film to jitter on)", p->flags & ~allowed);
+    // a stand-in camera: it carries the image size for the checks and sits at the origin, within any scene's reach
+    pt_camera cam;
+    memset(&cam, 0, sizeof(cam));
+    cam.dist_from_film = 1.0f; cam.focal_length = 1.0f;
+    cam.pxl_width = p->width; cam.pxl_height = p->height;
+    if (int rc = pt::validate_render(p, &cam)) return rc;
+    pt_ray_classes cls;
+    const uint32_t n = (uint32_t)p->width * (uint32_t)p->height;   // (both <= 65535)
+    if (int rc = classify_ctx_rays(c, "pt_render_rays", n, d_rays, reinterpret_cast<hipStream_t>(stream), &cls)) return rc;
+    if (cls.invalid != 0) {
+        uint32_t x = cls.first_invalid % (uint32_t)p->width, y = cls.first_invalid / (uint32_t)p->width;
+        if (p->pixel_order == PT_ORDER_MORTON) pt_morton_i_to_pxl(cls.first_invalid, &x, &y);
+        return pt::fail(PT_E_INVALID, "pt_render_rays: %llu invalid rays (a non-finite component or a zero direction), the first at "
+                        "index %u, pixel (%u, %u)", (unsigned long long)cls.invalid, cls.first_invalid, x, y);
+    }
+    if (int rc = render_enqueue(c, p, &cam, nullptr, d_out, stream, nullptr, d_rays, cls.irregular != 0)) return rc;
+    return pt_render_wait(c, st);
+}
+
+extern "C" int pt_render_rays(pt_ctx* c, const pt_params* p, const float* rays, float* out_rgb, pt_stats* st)
+{
+    pt::clear_error();
+    if (!c || !p || !rays || !out_rgb) return pt::fail(PT_E_INVALID, "pt_render_rays: null argument");
+    if (p->width <= 0 || p->height <= 0 || p->width > 65535 || p->height > 65535)
+        return pt::fail(PT_E_INVALID, "pt_render_rays: image size %dx%d out of range (1..65535)", p->width, p->height);
+    if (c->fl_n > 0)
+        return pt::fail(PT_E_INVALID, "pt_render_rays: %d asynchronous renders in flight (pt_render_wait first)", c->fl_n);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t npx = (size_t)p->width * (size_t)p->height, bytes = npx * 3 * sizeof(float);
+    if (int rc = pt::grow(&c->rays_stage, &c->rays_stage_floats, npx * 6)) return rc;
+    if (int rc = pt::grow(&c->scratch_out, &c->scratch_floats, npx * 3)) return rc;
+    HIP_TRY(hipMemcpy(c->rays_stage, rays, npx * 24, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(c->scratch_out, 0, bytes, nullptr));
+    if (int rc = pt_render_rays_device(c, p, c->rays_stage, c->scratch_out, nullptr, st)) return rc;
+    return pt::copy_to_host(out_rgb, c->scratch_out, bytes, nullptr, &c->pinned, &c->pinned_bytes);
 }
 
 // What pt_render_features* checks before touching the device; *vp = params with the ignored fields neutral.

@@ -1,0 +1,114 @@
+"""Ray sets for Renderer.render_rays (pt_render_rays): host only, numpy.
+
+Every helper returns (origins, directions), two float32 arrays of shape (W*H, 3) in scanline order (the ray of pixel
+(x, y) at y*W + x), the directions normalised in float32 -- so every ray is "regular" for a scene the origins lie
+within 64 extents of, and the render takes the wavefront kernels.  For a Morton-ordered render permute the rows to
+Morton order first.
+
+The image orientation is the pinhole camera's: a set built at the camera's pose shows the scene the way
+Renderer.render does (film x and y grow against the view's right and up, as camera.h's film does).
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+from . import api, shard
+
+F = np.float32
+
+
+def _normalised(d):
+    """Rows of d (float32) divided by their float32 length: x*x + y*y + z*z summed left to right, one square root."""
+    d = np.ascontiguousarray(d, dtype=F)
+    l2 = d[:, 0] * d[:, 0]
+    l2 = l2 + d[:, 1] * d[:, 1]
+    l2 = l2 + d[:, 2] * d[:, 2]
+    ln = np.sqrt(l2)
+    return np.ascontiguousarray(d / ln[:, None], dtype=F)
+
+
+def _basis(pos, target, up):
+    """(right, up, back), float64 unit vectors: the camera at pos looks along -back at target."""
+    pos, target, up = (np.asarray(v, dtype=np.float64) for v in (pos, target, up))
+    back = pos - target
+    nb = np.linalg.norm(back)
+    if not nb > 0:
+        raise ValueError("rays: pos and target coincide")
+    back = back / nb
+    right = np.cross(up, back)
+    nr = np.linalg.norm(right)
+    if not nr > 0:
+        raise ValueError("rays: up is parallel to the viewing direction")
+    right = right / nr
+    return right, np.cross(back, right), back
+
+
+def _film(W, H):
+    """The film coordinates of the pixel centres, (W*H,) each: ((x + 0.5) / W - 0.5, (y + 0.5) / H - 0.5), scanline."""
+    W, H = int(W), int(H)
+    if W <= 0 or H <= 0:
+        raise ValueError("rays: bad image size %dx%d" % (W, H))
+    x = (np.arange(W, dtype=np.float64) + 0.5) / W - 0.5
+    y = (np.arange(H, dtype=np.float64) + 0.5) / H - 0.5
+    return np.tile(x, H), np.repeat(y, W)
+
+
+def camera_rays(cam, view=None):
+    """The camera's own pinhole rays: pt_camera_ray_view(cam, view, morton(x, y), lens = 0) per pixel of its
+    pxl_width x pxl_height image, element for element.  render_rays over them equals render(cam, view=view) in every
+    bit for a radius == 0 camera, except at pixel (0, 0) (there render() draws the reference's two quirk lens
+    numbers per sample)."""
+    W, H = int(cam.pxl_width), int(cam.pxl_height)
+    if W <= 0 or H <= 0 or W > 65535 or H > 65535:
+        raise ValueError("rays: bad image size %dx%d" % (W, H))
+    ys, xs = np.divmod(np.arange(W * H, dtype=np.uint64), np.uint64(W))
+    idx = shard.morton_index(xs, ys).tolist()
+    # (one library call per pixel, into one pair of vec3s: about a second per million pixels)
+    call, cref, vref = L.lib().pt_camera_ray_view, C.byref(cam), api._view_ref(view)
+    ov, dv = L.Vec3(), L.Vec3()
+    oref, dref = C.byref(ov), C.byref(dv)
+    rays = np.empty((W * H, 6), dtype=F)
+    for k, i in enumerate(idx):
+        call(cref, vref, i, 0, 0.0, 0.0, oref, dref)
+        rays[k] = (ov.x, ov.y, ov.z, dv.x, dv.y, dv.z)
+    return np.ascontiguousarray(rays[:, :3]), np.ascontiguousarray(rays[:, 3:])
+
+
+def ortho_rays(pos, target, up, film_w, film_h, W, H):
+    """An orthographic projection: parallel rays along pos -> target from a film_w x film_h rectangle (scene units)
+    centred on pos."""
+    right, upv, back = _basis(pos, target, up)
+    sx, sy = _film(W, H)
+    o = np.asarray(pos, dtype=np.float64)[None, :] - sx[:, None] * float(film_w) * right - sy[:, None] * float(film_h) * upv
+    d = np.broadcast_to(0.0 - back, o.shape)
+    return np.ascontiguousarray(o, dtype=F), _normalised(d)
+
+
+def panorama_rays(pos, W, H):
+    """An equirectangular panorama from pos: longitude -pi..pi across the image (-z in the middle column, as the
+    reference camera looks), latitude from straight up (row 0) to straight down."""
+    sx, sy = _film(W, H)
+    lon = 2.0 * np.pi * sx
+    lat = np.pi * sy
+    d = np.stack([-np.cos(lat) * np.sin(lon), -np.sin(lat), -np.cos(lat) * np.cos(lon)], axis=1)
+    o = np.broadcast_to(np.asarray(pos, dtype=np.float64), d.shape)
+    return np.ascontiguousarray(o, dtype=F), _normalised(d)
+
+
+def fisheye_rays(pos, target, up, fov_deg, W, H):
+    """An equidistant fisheye looking from pos at target: the angle from the axis grows linearly with the distance
+    from the image centre and reaches fov_deg / 2 on the circle inscribed in the image; beyond pi it stays pi."""
+    right, upv, back = _basis(pos, target, up)
+    sx, sy = _film(W, H)
+    m = float(min(int(W), int(H)))
+    ux, uy = sx * (int(W) / m), sy * (int(H) / m)
+    r = np.sqrt(ux * ux + uy * uy)
+    ang = np.minimum(2.0 * r * np.radians(float(fov_deg)) / 2.0, np.pi)
+    rs = np.where(r > 0, r, 1.0)
+    lat = (-(ux / rs)[:, None] * right - (uy / rs)[:, None] * upv)   # unit vector in the film plane (0 at the centre)
+    d = np.cos(ang)[:, None] * (0.0 - back) + np.sin(ang)[:, None] * lat
+    o = np.broadcast_to(np.asarray(pos, dtype=np.float64), d.shape)
+    return np.ascontiguousarray(o, dtype=F), _normalised(d)

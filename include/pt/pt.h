@@ -803,6 +803,61 @@ int pt_occluded_device(pt_ctx* ctx, uint32_t n, const float* d_rays, const float
                        uint8_t* d_occ, uint32_t flags, void* stream);
 int pt_occluded(pt_ctx* ctx, uint32_t n, const float* rays, const float* tmax /* or NULL */, uint8_t* occ, uint32_t flags);
 
+/* ------------------------------------------------------------------ renders along caller-supplied rays
+ * The integrators run down a ray buffer instead of a camera: any projection (orthographic, fisheye, panorama),
+ * irradiance probes, light baking.  No pt_camera and no pt_view is taken.
+ *
+ * rays holds width * height * 6 floats, {o.xyz, d.xyz} per pixel as pt_trace's, indexed like the image: the ray of
+ * pixel (x, y) sits at its index in params->pixel_order (y * width + x, or the Morton index).  Device buffers must
+ * be 8-byte aligned.  d_out / out_rgb behave as pt_render_device's / pt_render's: the device call writes only this
+ * shard's pixels, the host call writes the others as 0; both block.  The host call stages the rays through a
+ * device buffer the context keeps, grows on demand and frees in pt_destroy.
+ *
+ * Arithmetic (a definition): pixel (x, y) is
+ *     rng = curand_init(seed, morton(x, y), 0)
+ *     for n = 1..spp:  L = integrator(o, d, rng);  m = m*(n-1)/n + L/n
+ * the reference's loop with the camera ray replaced.  No lens draws happen anywhere -- Morton index 0 is not a lens
+ * pixel here -- so the integrator's own draws are a sample's only draws.  Rays built with
+ * pt_camera_ray(cam, idx, lens = 0, ...) from a radius == 0 camera give pt_render's image in every bit for every
+ * pixel except Morton index 0, which in pt_render consumes the reference's two quirk lens draws per sample.  A ray
+ * is the same for every sample, so the primary-hit memo works as for a pinhole pixel (PT_FLAG_NO_PRIMARY_CACHE
+ * turns it off).  pt_stats keeps its meanings; rays_reference counts the trace() calls of the loop above.
+ *
+ * Ray classes.  Every one of the width * height rays (not only the shard's) is classified before a render, by the
+ * kernel pt_rays_classify_device makes public:
+ *     invalid    a non-finite component, or a direction of exactly (0, 0, 0)
+ *     regular    max |o_k| <= 64 * the scene's extent and d.x*d.x + d.y*d.y + d.z*d.z <= 1 + 2^-10 in float
+ *                (pt_trace's rule)
+ *     irregular  every other valid ray
+ * A buffer with an invalid ray is refused: PT_E_INVALID, the message names the lowest such pixel, nothing is
+ * written.  A buffer with at least one irregular ray sends THE WHOLE RENDER to the tile kernel with the reference's
+ * own stack walk, which is exact for every valid ray but much slower -- as a plain render with its camera beyond 64
+ * scene extents does; stats->work_units == 0 shows that it happened.  Otherwise the render takes the wavefront
+ * kernels, a regular ray outside the Markstein ranges (see pt_trace) taking the exact culled walk per lane.
+ * first_invalid is the lowest index of an invalid ray, 0xffffffff when there is none.  pt_rays_classify_device
+ * blocks; n == 0 gives all zeros; it is refused while asynchronous renders are in flight.
+ *
+ * flags: 0, PT_FLAG_NO_DEAD_PATH_SKIP, PT_FLAG_NO_PRIMARY_CACHE, PT_FLAG_REFERENCE_TRAVERSAL and
+ * PT_FLAG_REFERENCE_BVH (the last two select the tile kernel, with the reference's walk).  PT_E_INVALID:
+ * PT_FLAG_COUNT, PT_FLAG_TRI_COUNTS, PT_FLAG_JITTER, PT_FLAG_JITTER_TENT (there is no film to jitter on), unknown
+ * bits.  Both integrators; PT_HEAD_WF=0 puts integrator 1 on the tile kernel.  Shard fields, tile sizes, Morton
+ * order, empty shards and split units work as in pt_render_device; every shard of a multi-GPU job is given the whole
+ * buffer.  spp == 0 or an empty shard launches no render (invalid rays are still refused first).  Both calls are
+ * refused while asynchronous renders are in flight, and there is no asynchronous variant: the classes must reach
+ * the host before the launch.  Only the default PT_WF_MIN_WAVES / PT_HEAD_MIN_WAVES have kernels: a context created
+ * with other values is refused (PT_E_INVALID) where the render would take the wavefront kernels.
+ *
+ * Out of scope: accumulators and everything on top of them (noise estimates, adaptive sampling, sessions) over a
+ * ray buffer; pt_render_group / pt_render_multi; features, denoising and temporal reprojection for ray renders; a
+ * per-sample ray source (anti-aliasing or depth of field for custom projections); masked or empty pixels -- a
+ * caller compacts its rays or pads them with any valid ray. */
+typedef struct { uint64_t regular, irregular, invalid; uint32_t first_invalid; uint32_t pad; } pt_ray_classes;
+int pt_render_rays_device(pt_ctx* ctx, const pt_params* params, const float* d_rays, float* d_out, void* stream,
+                          pt_stats* stats);
+int pt_render_rays(pt_ctx* ctx, const pt_params* params, const float* rays /* host */, float* out_rgb /* host */,
+                   pt_stats* stats);
+int pt_rays_classify_device(pt_ctx* ctx, uint32_t n, const float* d_rays, void* stream, pt_ray_classes* out /* host */);
+
 /* Output step on the GPU (kernel.cu:763-778, color.h:59-71): codes = pt_tonemap_u8(rgb) per
  * channel, identical to the host function (threshold table bisected with the host's libm at
  * pt_create).  _device: device pointers on `stream`, blocking; negative inputs (which the
