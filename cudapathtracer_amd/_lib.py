@@ -227,6 +227,11 @@ SIGNATURES = {
     "pt_accum_create_view": (C.c_void_p, [C.c_void_p, C.POINTER(Params), C.POINTER(Camera), C.POINTER(View),
                                           C.POINTER(C.c_int)]),
     "pt_accum_view": (C.c_int, [C.c_void_p, C.POINTER(View), C.POINTER(C.c_int)]),
+    "pt_accum_create_rays_device": (C.c_void_p, [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "pt_accum_create_rays": (C.c_void_p, [C.c_void_p, C.POINTER(Params), C.c_void_p, C.POINTER(C.c_int)]),
+    "pt_accum_has_rays": (C.c_int, [C.c_void_p]),
+    "pt_render_features_rays_device": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_render_features_rays": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p]),
     "pt_accum_add": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     "pt_accum_samples": (C.c_int64, [C.c_void_p]),
     "pt_accum_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -634,6 +634,63 @@ class Renderer:
                                               None if stream_ptr is None else C.c_void_p(int(stream_ptr)), C.byref(st)))
         return st.as_dict()
 
+    def accumulator_rays(self, origins, directions, width, height, bounces=3, integrator=0, seed=1234, flags=0,
+                         shard_index=0, shard_count=1, pixel_order=0, tile=0):
+        """A resumable render of this shard along the caller's rays (pt_accum_create_rays): accumulator() with the
+        camera replaced by W*H rays indexed as for render_rays().  The accumulator copies the rays and keeps them for
+        life.  add() in any split of passes equals render_rays() of the same total in every bit; noise estimates,
+        add_until, add_adaptive and freeze work as on a camera accumulator, and freeze() at 0 samples masks pixels (a
+        masked pixel still needs a valid ray).  Every ray must be regular: a far or unnormalised ray is refused here
+        (PtError PT_E_INVALID; render_rays takes such a buffer).  flags: 0, PT_FLAG_NO_DEAD_PATH_SKIP,
+        PT_FLAG_NO_PRIMARY_CACHE.  save() and save_session() are refused."""
+        rays, n = self._rays(origins, directions)
+        if n != int(width) * int(height):
+            raise ValueError("accumulator_rays: %d rays for a %dx%d image" % (n, width, height))
+        tw, th = (tile, tile) if np.isscalar(tile) else tile
+        p = self.params(width, height, 0, bounces, integrator, seed, flags, shard_index, shard_count, pixel_order, tw, th)
+        err = C.c_int(0)
+        h = L.lib().pt_accum_create_rays(self._h, C.byref(p), rays.ctypes.data, C.byref(err))
+        if not h:
+            L.check(err.value if err.value != 0 else L.PT_E_HIP)
+        return Accumulator(self, h, p)
+
+    def accumulator_rays_device(self, d_rays_ptr, width, height, bounces=3, integrator=0, seed=1234, flags=0,
+                                shard_index=0, shard_count=1, pixel_order=0, tile=0, stream_ptr=None):
+        """accumulator_rays() over W*H rays on the device (float32[6*W*H], 8-byte aligned; pt_accum_create_rays_device).
+        The buffer is copied: it may be freed or overwritten once this returns."""
+        tw, th = (tile, tile) if np.isscalar(tile) else tile
+        p = self.params(width, height, 0, bounces, integrator, seed, flags, shard_index, shard_count, pixel_order, tw, th)
+        err = C.c_int(0)
+        h = L.lib().pt_accum_create_rays_device(self._h, C.byref(p), C.c_void_p(int(d_rays_ptr)),
+                                                None if stream_ptr is None else C.c_void_p(int(stream_ptr)), C.byref(err))
+        if not h:
+            L.check(err.value if err.value != 0 else L.PT_E_HIP)
+        return Accumulator(self, h, p)
+
+    def features_rays(self, origins, directions, width, height, pixel_order=0, shard_index=0, shard_count=1, tile=0):
+        """Feature buffers of the caller's rays (pt_render_features_rays): features() with each pixel's ray taken from
+        the buffer as it stands.  depth is the hit distance along the given direction, in units of its length;
+        position = o + d * depth.  Far and unnormalised rays are legal; an invalid ray refuses the call."""
+        rays, n = self._rays(origins, directions)
+        if n != int(width) * int(height):
+            raise ValueError("features_rays: %d rays for a %dx%d image" % (n, width, height))
+        tw, th = (tile, tile) if np.isscalar(tile) else tile
+        p = self.params(width, height, 0, 1, 0, 0, 0, shard_index, shard_count, pixel_order, tw, th)
+        shape = (height * width,) if pixel_order == L.PT_ORDER_MORTON else (height, width)
+        out = np.zeros(shape, dtype=FEATURE)
+        L.check(L.lib().pt_render_features_rays(self._h, C.byref(p), rays.ctypes.data, out.ctypes.data))
+        return out
+
+    def features_rays_device(self, d_rays_ptr, d_feat_ptr, width, height, pixel_order=0, shard_index=0, shard_count=1,
+                             tile=0, stream_ptr=None):
+        """This shard's ray features into a caller-owned device buffer of W*H 48-byte records (16-byte aligned), from
+        W*H rays on the device (8-byte aligned); records of other pixels are left untouched."""
+        tw, th = (tile, tile) if np.isscalar(tile) else tile
+        p = self.params(width, height, 0, 1, 0, 0, 0, shard_index, shard_count, pixel_order, tw, th)
+        L.check(L.lib().pt_render_features_rays_device(self._h, C.byref(p), C.c_void_p(int(d_rays_ptr)),
+                                                       C.c_void_p(int(d_feat_ptr)),
+                                                       None if stream_ptr is None else C.c_void_p(int(stream_ptr))))
+
     def classify_rays_device(self, d_rays_ptr, n, stream_ptr=None):
         """The classes of n rays on the device (pt_rays_classify_device), as render_rays* sorts them: a dict of
         regular, irregular, invalid (counts) and first_invalid (lowest invalid index, 0xffffffff for none)."""
@@ -718,6 +775,11 @@ class Accumulator:
         v, has = L.View(), C.c_int(0)
         L.check(L.lib().pt_accum_view(self._h, C.byref(v), C.byref(has)))
         return v if has.value else None
+
+    @property
+    def has_rays(self):
+        """Whether the accumulator was built over a ray buffer (Renderer.accumulator_rays*; pt_accum_has_rays)."""
+        return bool(L.lib().pt_accum_has_rays(self._h))
 
     def _shape(self):
         p = self.params

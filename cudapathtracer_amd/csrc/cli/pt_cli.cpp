@@ -78,10 +78,11 @@
 // --rays FILE                             render along the caller's rays instead of a camera's (pt_render_rays): FILE is raw
 //                                         little-endian float32, 6 * W * H values {o.xyz, d.xyz} in scanline order, with
 //                                         --width / --height / --spp and the usual output options (--morton permutes the
-//                                         rays into the Morton-indexed buffer's order).  Not with the camera, view, jitter,
-//                                         checkpoint, session, temporal, adaptive, denoising or --aov options, --tri-counts
-//                                         or --gpus above 1: an error.  A ray far outside the scene or with an unnormalised
-//                                         direction sends the whole render to the slow exact walk (pt.h)
+//                                         rays into the Morton-indexed buffer's order).  --denoise and --aov take their
+//                                         features from the ray file (pt_render_features_rays).  Not with the camera, view,
+//                                         jitter, checkpoint, session, temporal, pass, adaptive or --denoise-guided options,
+//                                         --tri-counts or --gpus above 1: an error.  A ray far outside the scene or with an
+//                                         unnormalised direction sends the whole render to the slow exact walk (pt.h)
 // --aov PREFIX                            write the primary-hit feature buffers as PREFIX_albedo.pfm,
 //                                         PREFIX_normal.pfm, PREFIX_position.pfm and PREFIX_depth.pfm (depth
 //                                         replicated to 3 channels)
@@ -140,7 +141,8 @@ struct Obj {
             "                     length, default 32); the files hold the last frame's temporal image; --denoise-guided and\n"
             "                     --variance-map use the temporal variance\n"
             "  --rays FILE        render along the rays of FILE (raw float32, 6*W*H values {o.xyz, d.xyz}, scanline order) instead\n"
-            "                     of a camera's; not with the camera, view, jitter, accumulating, temporal or denoising options\n"
+            "                     of a camera's; --denoise and --aov take their features from FILE; not with the camera, view,\n"
+            "                     jitter, accumulating, temporal or --denoise-guided options\n"
             "  --aov PREFIX       write PREFIX_albedo.pfm, PREFIX_normal.pfm, PREFIX_position.pfm, PREFIX_depth.pfm\n");
     exit(2);
 }
@@ -338,13 +340,14 @@ int main(int argc, char** argv)
     if (gpus < 1) usage("--gpus must be >= 1");
     std::vector<float> rays;   // --rays: the buffer in the render's pixel order
     if (!rays_path.empty()) {
-        // a render along rays takes no camera and has neither accumulator nor features (pt.h): every option of those is an error
+        // a render along rays takes no camera, and its passes are not driven from here: every option of those is an error.
+        // (--denoise and --aov work: the features then come from the ray file, pt_render_features_rays)
         for (const std::string& g : given)
             for (const char* o : {"--cam", "--dist", "--focal", "--radius", "--look-at", "--up", "--vfov", "--film", "--jitter",
                                   "--checkpoint", "--resume", "--session", "--resume-session", "--pass-spp", "--camera-path",
                                   "--temporal", "--temporal-max", "--until-error", "--error-quantile", "--min-batches", "--error-map",
-                                  "--adaptive", "--count-map", "--denoise", "--denoise-guided", "--sigma-luma", "--variance-map",
-                                  "--aov", "--tri-counts"})
+                                  "--adaptive", "--count-map", "--denoise-guided", "--sigma-luma", "--variance-map",
+                                  "--tri-counts"})
                 if (g == o) usage(("--rays cannot be combined with " + g).c_str());
         if (gpus != 1) usage("--rays needs --gpus 1");
         if (p.width <= 0 || p.height <= 0 || p.width > 65535 || p.height > 65535) usage("--rays: bad --width / --height");
@@ -504,6 +507,7 @@ int main(int argc, char** argv)
         feat.resize((size_t)p.width * p.height);
         pt_params fp = p;
         fp.shard_index = 0; fp.shard_count = 1;
+        if (!rays.empty()) return pt_render_features_rays(ctx[0], &fp, rays.data(), feat.data()) == PT_OK;
         return pt_render_features_view(ctx[0], &fp, &cam, cam_view, feat.data()) == PT_OK;
     };
     // the image files of the current `img` (after the render; with --pass-spp after every pass)

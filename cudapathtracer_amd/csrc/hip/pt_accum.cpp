@@ -106,6 +106,7 @@ struct pt_accum {
     bool list_valid = false;
     uint32_t nactive = 0;             // entries of d_list (list_valid)
     uint32_t* d_slot_pix = nullptr;   // slot_pix on the device, uploaded when a session file first needs it (pt_session.hip)
+    float* d_rays = nullptr;          // a ray accumulator's own copy of its rays (width * height * 6 floats), kept for life
     size_t slots() const { return slot_pix.size(); }
 };
 
@@ -296,6 +297,64 @@ pt_accum* pt_accum_create(pt_ctx* ctx, const pt_params* params, const pt_camera*
     return pt_accum_create_view(ctx, params, cam, nullptr, err);
 }
 
+// The accumulator of (c, p) over a copy of the width * height rays at `rays` (host memory, or device memory read on
+// `stream`), or null with the error recorded: the checks in pt.h's order, the copy, then the copy's classes.
+static pt_accum* make_accum_rays(pt_ctx* c, const pt_params* p, const float* rays, bool host, void* stream, int* code)
+{
+    if (pt::ctx_in_flight(c) > 0) {
+        *code = pt::fail(PT_E_INVALID, "pt_accum_create_rays: %d asynchronous renders in flight (pt_render_wait first)",
+                         pt::ctx_in_flight(c));
+        return nullptr;
+    }
+    pt_camera cam;
+    *code = pt::accum_check_rays(c, p, &cam);
+    if (*code != PT_OK) return nullptr;
+    if (!host && reinterpret_cast<uintptr_t>(rays) % 8 != 0) {
+        *code = pt::fail(PT_E_INVALID, "pt_accum_create_rays: the ray buffer must be 8-byte aligned");
+        return nullptr;
+    }
+    pt_accum* a = make_accum(c, p, &cam, nullptr, code);
+    if (!a) return nullptr;
+    auto copy = [&]() -> int {
+        const size_t bytes = (size_t)p->width * (size_t)p->height * 6 * sizeof(float);
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&a->d_rays), bytes));
+        if (host) {
+            HIP_TRY(hipMemcpy(a->d_rays, rays, bytes, hipMemcpyHostToDevice));
+        } else {
+            HIP_TRY(hipMemcpyAsync(a->d_rays, rays, bytes, hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream)));
+        }
+        // (its own copy is what gets classified: what the passes read is what was checked)
+        return pt::accum_classify_rays(c, p, a->d_rays, host ? nullptr : stream);
+    };
+    *code = copy();
+    if (*code != PT_OK) { pt_accum_destroy(a); return nullptr; }
+    return a;
+}
+
+pt_accum* pt_accum_create_rays_device(pt_ctx* ctx, const pt_params* params, const float* d_rays, void* stream, int* err)
+{
+    pt::clear_error();
+    int code;
+    pt_accum* a = nullptr;
+    if (!ctx || !params || !d_rays) code = pt::fail(PT_E_INVALID, "pt_accum_create_rays: null argument");
+    else a = make_accum_rays(ctx, params, d_rays, false, stream, &code);
+    if (err) *err = code;
+    return a;
+}
+
+pt_accum* pt_accum_create_rays(pt_ctx* ctx, const pt_params* params, const float* rays, int* err)
+{
+    pt::clear_error();
+    int code;
+    pt_accum* a = nullptr;
+    if (!ctx || !params || !rays) code = pt::fail(PT_E_INVALID, "pt_accum_create_rays: null argument");
+    else a = make_accum_rays(ctx, params, rays, true, nullptr, &code);
+    if (err) *err = code;
+    return a;
+}
+
+int pt_accum_has_rays(const pt_accum* acc) { return (acc && acc->d_rays) ? 1 : 0; }
+
 int pt_accum_view(const pt_accum* acc, pt_view* out, int* has_view)
 {
     pt::clear_error();
@@ -324,6 +383,7 @@ int pt_accum_add(pt_accum* acc, int32_t spp, float* d_out, void* stream, pt_stat
     pt_params p = acc->params;
     p.spp = spp;
     pt::AccumPass pass{(uint32_t)acc->samples, acc->d_rng, acc->d_mean};
+    pass.rays = acc->d_rays;
     if (acc->any_frozen) {   // an adaptive pass: the active pixels only
         if (int rc = active_list(acc, stream)) return rc;
         if (acc->nactive == 0) {   // every pixel frozen: nothing to sample, the count stays
@@ -493,6 +553,9 @@ int pt_accum_save(pt_accum* acc, const char* path)
     pt::clear_error();
     if (!acc || !path) return pt::fail(PT_E_INVALID, "pt_accum_save: null argument");
     if (!little_endian()) return pt::fail(PT_E_INVALID, "pt_accum_save: checkpoint files are little-endian; this host is not");
+    if (acc->d_rays)
+        return pt::fail(PT_E_INVALID, "pt_accum_save: the accumulator was built over a ray buffer (pt_accum_create_rays); a "
+                        "checkpoint file holds a camera, not rays");
     if (acc->has_view)
         return pt::fail(PT_E_INVALID, "pt_accum_save: the accumulator has a view (an oriented camera); checkpoint format version 1 "
                         "holds the 32-byte camera alone (pt_session_save writes a session file that holds the view)");
@@ -594,6 +657,7 @@ void pt_accum_destroy(pt_accum* acc)
     if (acc->d_list) (void)hipFree(acc->d_list);
     if (acc->d_scan) (void)hipFree(acc->d_scan);
     if (acc->d_slot_pix) (void)hipFree(acc->d_slot_pix);
+    if (acc->d_rays) (void)hipFree(acc->d_rays);
     delete acc;
 }
 

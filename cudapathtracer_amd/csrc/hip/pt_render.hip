@@ -1080,7 +1080,9 @@ __global__ __launch_bounds__(256) void init_pixel_states(Args a, uint32_t* __res
 // list, unit u = the whole pixel of slot q = list[u] -- the words init_pixel_states writes for a whole-pixel
 // accumulating unit, whose UW_TQ names the slot: the row (stride npix, the shard's slot count) the integration
 // kernels load the unit's mean from and store its mean and stream to.  nunits = nwhole = the list's length.
-template <bool kJit>
+// (kRays: the active list of a ray accumulator, init_active_states_rays -- a pinhole unit whose direction is the
+// pixel's in RayArgs::rays, Morton index 0 too, as in init_pixel_states_body)
+template <bool kJit, bool kRays = false>
 __device__ __forceinline__ void init_active_states_body(const Args& a, uint32_t* __restrict__ st, const uint32_t* __restrict__ list)
 {
     const uint32_t u = blockIdx.x * 256u + threadIdx.x;
@@ -1096,8 +1098,8 @@ __device__ __forceinline__ void init_active_states_body(const Args& a, uint32_t*
     const uint32_t idx = morton2(px, py);
     Rng r;
     slot_stream(a, q, idx, a.acc_n0, r);
-    const bool lens = kJit || (idx == 0) || (a.cam.radius != 0.0f);   // (kJit: every unit's rays are formed per sample)
-    const V3 d = pinhole_dir(a, px, py, lens);
+    const bool lens = !kRays && (kJit || (idx == 0) || (a.cam.radius != 0.0f));   // (kJit: every unit's rays are formed per sample)
+    const V3 d = kRays ? ray_direction(a, px, py) : pinhole_dir(a, px, py, lens);
     st[u] = r.v0;
     st[N + u] = r.v1;
     st[2 * N + u] = r.v2;
@@ -2680,7 +2682,9 @@ __global__ __launch_bounds__(256) void trace_rays(Args a, const float* __restric
 // (kView: the oriented pinhole ray; primary_features_view is the kernel of a render with a view)
 // (kJit: the guide buffers of a jittered render, primary_features_jitter: the ray through the footprint's centre,
 // jx = jy = 0.5, box and tent alike, so that they sit under the image they guide)
-template <bool kView, bool kJit = false>
+// (kRays: the guide buffers of a ray render, primary_features_rays: the pixel's ray as it stands in RayArgs::rays -- no
+// normalisation, no 0 + o -- so depth is closestT along the given d and an irregular ray takes the reference's walk)
+template <bool kView, bool kJit = false, bool kRays = false>
 __device__ __forceinline__ void primary_features_body(const Args& a, float4* __restrict__ out)
 {
     extern __shared__ uint32_t lds_tr[];
@@ -2698,7 +2702,8 @@ __device__ __forceinline__ void primary_features_body(const Args& a, float4* __r
         uint32_t px, py;
         if (!unit_pixel(a, q, &px, &py)) continue;
         V3 o, d;
-        if (kJit) camera_ray_jitter<false>(a, px, py, 0.5f, 0.5f, false, 0.0f, 0.0f, &o, &d);
+        if (kRays) { o = ray_origin(a, px, py); d = ray_direction(a, px, py); }
+        else if (kJit) camera_ray_jitter<false>(a, px, py, 0.5f, 0.5f, false, 0.0f, 0.0f, &o, &d);
         else if (kView) camera_ray_view<false>(a, px, py, false, 0.0f, 0.0f, &o, &d);
         else camera_ray<false>(a.cam, px, py, false, 0.0f, 0.0f, &o, &d);
         int32_t htri = -1;
@@ -2946,6 +2951,30 @@ template <int kIntegrator, bool kRefWalk, bool kCount>
 __global__ __launch_bounds__(64) void render_tiles_rays(RayArgs a)
 {
     render_tiles_body<kIntegrator, kRefWalk, kCount, false, false, true>(a);
+}
+
+// ------------------------------------------------------------------ accumulators and features over caller-supplied rays
+// pt_accum_create_rays* / pt_render_features_rays*: the accumulating twins of the two ray-source wavefront kernels, the
+// set-up of an adaptive pass over a ray accumulator and the features kernel with a ray source -- again defined and
+// first used after every other kernel, which therefore compile as they did.  The unfrozen
+// accumulating pass is set up by init_pixel_states_rays, whose body honours Args::accum.
+template <bool kLdsWalk>
+__global__ __launch_bounds__(256, 5) void render_unidir_accum_rays_wf(RayArgs a)
+{
+    wf_main<false, false, kLdsWalk, true, false, false, true>(a);
+}
+__global__ __launch_bounds__(256, 5) void render_head_accum_rays_wf(RayArgs a)
+{
+    wf_main<false, true, true, true, false, false, true>(a);
+}
+
+__global__ __launch_bounds__(256) void init_active_states_rays(RayArgs a, uint32_t* __restrict__ st, const uint32_t* __restrict__ list)
+{
+    init_active_states_body<false, true>(a, st, list);
+}
+__global__ __launch_bounds__(256) void primary_features_rays(RayArgs a, float4* __restrict__ out)
+{
+    primary_features_body<false, false, true>(a, out);
 }
 
 }  // namespace

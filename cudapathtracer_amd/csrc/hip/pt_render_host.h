@@ -527,6 +527,9 @@ static int launch_wavefront(const pt::WavefrontVariant& v, const WavefrontLaunch
         case code(true, false, 5, false, false): rkernel = render_head_rays_wf; break;
         case code(false, false, 5, true, false): rkernel = render_unidir_rays_wf<true>; break;
         case code(false, false, 5, false, false): rkernel = render_unidir_rays_wf<false>; break;
+        case code(true, false, 5, false, true): rkernel = render_head_accum_rays_wf; break;   // (a ray accumulator's passes)
+        case code(false, false, 5, true, true): rkernel = render_unidir_accum_rays_wf<true>; break;
+        case code(false, false, 5, false, true): rkernel = render_unidir_accum_rays_wf<false>; break;
         default:
             return pt::fail(PT_E_INVALID, "pt_render_rays: no ray-source wavefront kernel instance for head %d count %d waves %d lds %d "
                             "accum %d (only the default PT_WF_MIN_WAVES / PT_HEAD_MIN_WAVES have one)",
@@ -626,10 +629,15 @@ static int enqueue_wavefront(pt_ctx* c, const pt_params* p, const pt::AccumPass*
         b.seed_states = B.seed_states;
     }
     const bool jitter = (b.flags & PT_FLAG_JITTER) != 0;   // (its set-up kernels mark every unit "ray formed per sample")
-    if (acc && acc->active)
+    if (acc && acc->active && !rays)
         hipLaunchKernelGGL(jitter ? init_active_states_jitter : init_active_states, dim3((b.nunits + 255) / 256), dim3(256), 0,
                            stream, b, B.pix_states, acc->active);
-    else if (!rays)
+    else if (acc && acc->active) {   // (an adaptive pass of a ray accumulator: the active set-up's ray twin)
+        RayArgs rb;
+        static_cast<Args&>(rb) = b;
+        rb.rays = rays;
+        hipLaunchKernelGGL(init_active_states_rays, dim3((b.nunits + 255) / 256), dim3(256), 0, stream, rb, B.pix_states, acc->active);
+    } else if (!rays)
         hipLaunchKernelGGL(jitter ? init_pixel_states_jitter : init_pixel_states, dim3((b.npix + 255) / 256), dim3(256), 0, stream,
                            b, B.pix_states);
     else {   // (a render along rays: the set-up that reads each unit's direction from the buffer)
@@ -659,8 +667,9 @@ static int enqueue_wavefront(pt_ctx* c, const pt_params* p, const pt::AccumPass*
 // acc: the render is a pass of an accumulator (pt::accum_pass) -- p->spp more samples of every pixel on top
 // of its acc->n0, from and to the accumulator's state; d_out may then be null.  Everything else -- the
 // unit split, the buffers' growth, the jump and seed tables, the flight slots -- is the plain render's.
-// d_rays: a render along the caller's rays (pt_render_rays_device, which has classified them; cam is then a
-// stand-in that only carries the image size); rays_irregular: the buffer holds an irregular ray, so the whole render
+// d_rays: a render along the caller's rays (pt_render_rays_device, which has classified them, or a pass of a ray
+// accumulator, whose rays were classified when it was created; cam is then a stand-in that only carries the image
+// size); rays_irregular: the buffer holds an irregular ray, so the whole render
 // takes the tile kernel with the reference's own walk.
 static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view, float* d_out, void* stream_v,
                           const pt::AccumPass* acc, const float* d_rays = nullptr, bool rays_irregular = false)
@@ -871,7 +880,7 @@ int pt::accum_pass(pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt
 {
     if (c->fl_n > 0)
         return pt::fail(PT_E_INVALID, "pt_accum_add: %d asynchronous renders in flight (pt_render_wait first)", c->fl_n);
-    if (int rc = render_enqueue(c, p, cam, view, d_out, stream, &acc)) return rc;
+    if (int rc = render_enqueue(c, p, cam, view, d_out, stream, &acc, acc.rays)) return rc;   // (rays: all regular)
     return pt_render_wait(c, stats);
 }
 
@@ -1164,6 +1173,33 @@ static int classify_ctx_rays(pt_ctx* c, const char* who, uint32_t n, const float
     return pt::classify_ray_buffer(d_rays, n, 64.0f * c->scene_extent, c->num_cus, c->ray_classes, stream, out);
 }
 
+// The stand-in camera of a call that takes rays: it carries the image size for the checks and sits at the origin,
+// within any scene's reach.
+static pt_camera rays_stand_in(const pt_params* p)
+{
+    pt_camera cam;
+    memset(&cam, 0, sizeof(cam));
+    cam.dist_from_film = 1.0f; cam.focal_length = 1.0f;
+    cam.pxl_width = p->width; cam.pxl_height = p->height;
+    return cam;
+}
+
+// The classes of an image's rays (p validated: width, height <= 65535), and the refusal of a buffer with an invalid
+// ray, its lowest pixel named.
+static int classify_image_rays(pt_ctx* c, const char* who, const pt_params* p, const float* d_rays, hipStream_t stream,
+                               pt_ray_classes* cls)
+{
+    const uint32_t n = (uint32_t)p->width * (uint32_t)p->height;
+    if (int rc = classify_ctx_rays(c, who, n, d_rays, stream, cls)) return rc;
+    if (cls->invalid != 0) {
+        uint32_t x = cls->first_invalid % (uint32_t)p->width, y = cls->first_invalid / (uint32_t)p->width;
+        if (p->pixel_order == PT_ORDER_MORTON) pt_morton_i_to_pxl(cls->first_invalid, &x, &y);
+        return pt::fail(PT_E_INVALID, "%s: %llu invalid rays (a non-finite component or a zero direction), the first at "
+                        "index %u, pixel (%u, %u)", who, (unsigned long long)cls->invalid, cls->first_invalid, x, y);
+    }
+    return PT_OK;
+}
+
 extern "C" int pt_rays_classify_device(pt_ctx* c, uint32_t n, const float* d_rays, void* stream, pt_ray_classes* out)
 {
     pt::clear_error();
@@ -1185,23 +1221,43 @@ extern "C" int pt_render_rays_device(pt_ctx* c, const pt_params* p, const float*
         return pt::fail(PT_E_INVALID, "pt_render_rays: flags 0x%x: a render along rays takes only PT_FLAG_NO_DEAD_PATH_SKIP, "
                         "PT_FLAG_NO_PRIMARY_CACHE, PT_FLAG_REFERENCE_TRAVERSAL and PT_FLAG_REFERENCE_BVH (no counting variants, and "
                         "no film to jitter on)", p->flags & ~allowed);
-    // a stand-in camera: it carries the image size for the checks and sits at the origin, within any scene's reach
-    pt_camera cam;
-    memset(&cam, 0, sizeof(cam));
-    cam.dist_from_film = 1.0f; cam.focal_length = 1.0f;
-    cam.pxl_width = p->width; cam.pxl_height = p->height;
+    const pt_camera cam = rays_stand_in(p);
     if (int rc = pt::validate_render(p, &cam)) return rc;
     pt_ray_classes cls;
-    const uint32_t n = (uint32_t)p->width * (uint32_t)p->height;   // (both <= 65535)
-    if (int rc = classify_ctx_rays(c, "pt_render_rays", n, d_rays, reinterpret_cast<hipStream_t>(stream), &cls)) return rc;
-    if (cls.invalid != 0) {
-        uint32_t x = cls.first_invalid % (uint32_t)p->width, y = cls.first_invalid / (uint32_t)p->width;
-        if (p->pixel_order == PT_ORDER_MORTON) pt_morton_i_to_pxl(cls.first_invalid, &x, &y);
-        return pt::fail(PT_E_INVALID, "pt_render_rays: %llu invalid rays (a non-finite component or a zero direction), the first at "
-                        "index %u, pixel (%u, %u)", (unsigned long long)cls.invalid, cls.first_invalid, x, y);
-    }
+    if (int rc = classify_image_rays(c, "pt_render_rays", p, d_rays, reinterpret_cast<hipStream_t>(stream), &cls)) return rc;
     if (int rc = render_enqueue(c, p, &cam, nullptr, d_out, stream, nullptr, d_rays, cls.irregular != 0)) return rc;
     return pt_render_wait(c, st);
+}
+
+// ---- accumulators over a ray buffer (pt_accum_create_rays*, pt_accum.cpp): the context's side
+int pt::accum_check_rays(const pt_ctx* c, const pt_params* p, pt_camera* stand_in)
+{
+    constexpr uint32_t allowed = PT_FLAG_NO_DEAD_PATH_SKIP | PT_FLAG_NO_PRIMARY_CACHE;
+    if (p->flags & ~allowed)
+        return pt::fail(PT_E_INVALID, "pt_accum_create_rays: flags 0x%x: an accumulator over rays takes only PT_FLAG_NO_DEAD_PATH_SKIP "
+                        "and PT_FLAG_NO_PRIMARY_CACHE (the reference walks and the counting variants have no accumulating kernel, "
+                        "and there is no film to jitter on)", p->flags & ~allowed);
+    *stand_in = rays_stand_in(p);
+    if (int rc = validate_render(p, stand_in)) return rc;
+    const RenderKnobs& K = c->knobs;
+    if (!takes_wavefront(p, stand_in, c->scene_extent, K.head_wf))
+        return pt::fail(PT_E_INVALID, "pt_accum_create_rays: this render would take the tile kernel (integrator 1 with PT_HEAD_WF=0), "
+                        "which does not accumulate");
+    if (K.wf_min_waves != 5 || K.head_min_waves != 5)
+        return pt::fail(PT_E_INVALID, "pt_accum_create_rays: only the default-occupancy kernels accumulate (PT_WF_MIN_WAVES / "
+                        "PT_HEAD_MIN_WAVES are set)");
+    return PT_OK;
+}
+
+int pt::accum_classify_rays(pt_ctx* c, const pt_params* p, const float* d_rays, void* stream)
+{
+    pt_ray_classes cls;
+    if (int rc = classify_image_rays(c, "pt_accum_create_rays", p, d_rays, reinterpret_cast<hipStream_t>(stream), &cls)) return rc;
+    if (cls.irregular != 0)   // (never a silent fall-back: the accumulating kernels are the wavefront kernels)
+        return pt::fail(PT_E_INVALID, "pt_accum_create_rays: %llu irregular rays (an origin beyond 64 scene extents, or a direction "
+                        "longer than a normalised one); accumulation runs on the wavefront kernels only -- pt_render_rays takes "
+                        "such a buffer", (unsigned long long)cls.irregular);
+    return PT_OK;
 }
 
 extern "C" int pt_render_rays(pt_ctx* c, const pt_params* p, const float* rays, float* out_rgb, pt_stats* st)
@@ -1302,6 +1358,79 @@ extern "C" int pt_render_features_view(pt_ctx* c, const pt_params* p, const pt_c
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_feat), n * sizeof(pt_feature)));
     HIP_TRY(hipMemcpy(d_feat, feat, n * sizeof(pt_feature), hipMemcpyHostToDevice));
     if (int rc = pt_render_features_view_device(c, p, cam, view, d_feat, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(feat, d_feat, n * sizeof(pt_feature), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+// ---- feature buffers over a ray buffer (pt_render_features_rays_device, pt_render_features_rays)
+
+// What both calls check before touching the device, in pt.h's order; *vp = params with the ignored fields neutral.
+static int features_rays_check(const pt_ctx* c, const pt_params* p, const float* rays, const void* feat, pt_params* vp)
+{
+    if (!c || !p || !rays || !feat) return pt::fail(PT_E_INVALID, "pt_render_features_rays: null argument");
+    if (c->fl_n > 0)
+        return pt::fail(PT_E_INVALID, "pt_render_features_rays: %d asynchronous renders in flight (pt_render_wait first)", c->fl_n);
+    *vp = *p;
+    vp->spp = 0; vp->bounces = 1; vp->integrator = PT_INTEGRATOR_UNIDIR; vp->seed = 0;
+    vp->flags = 0;   // (nothing jitters: there is no film)
+    const pt_camera cam = rays_stand_in(p);
+    if (int rc = pt::validate_render(vp, &cam)) return rc;
+    if ((uint64_t)c->num_tris + (uint64_t)c->num_spheres >= (uint64_t)PT_FEATURE_EMISSIVE)
+        return pt::fail(PT_E_INVALID, "pt_render_features_rays: %u triangles + %u spheres do not fit the 30 id bits of pt_feature.prim",
+                        c->num_tris, c->num_spheres);
+    return PT_OK;
+}
+
+extern "C" int pt_render_features_rays_device(pt_ctx* c, const pt_params* p_in, const float* d_rays, pt_feature* d_feat, void* stream_v)
+{
+    pt::clear_error();
+    pt_params pv;
+    if (int rc = features_rays_check(c, p_in, d_rays, d_feat, &pv)) return rc;
+    if (reinterpret_cast<uintptr_t>(d_feat) % 16 != 0)
+        return pt::fail(PT_E_INVALID, "pt_render_features_rays_device: d_feat must be 16-byte aligned");
+    const pt_params* p = &pv;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+    pt_ray_classes cls;   // (an irregular ray is legal here: the kernel chooses the walk per ray)
+    if (int rc = classify_image_rays(c, "pt_render_features_rays", p, d_rays, stream, &cls)) return rc;
+    RayArgs a;
+    memset(&a, 0, sizeof(a));
+    fill_scene_args(a, c);
+    fill_view_args(a, *p, rays_stand_in(p), nullptr);
+    a.rays = d_rays;
+    a.node_mask = c->node4_mask;
+    a.stack_words = kWaveLdsWords;
+    const size_t lds = (size_t)a.stack_words * 4 * 4;
+    if (a.npix == 0) return PT_OK;
+    uint32_t blocks = (uint32_t)(((uint64_t)a.npix + 255) / 256);
+    const uint32_t cap = (uint32_t)c->num_cus * 8u;
+    if (blocks > cap) blocks = cap;
+    if (int rc = pt::grow(&c->rb[0].spill, &c->rb[0].spill_words, stack_words_per_lane(c) * (size_t)blocks * 256)) return rc;
+    a.spill = c->rb[0].spill;
+    a.spill_stride = blocks * 256;
+    hipLaunchKernelGGL(primary_features_rays, dim3(blocks), dim3(256), lds, stream, a, reinterpret_cast<float4*>(d_feat));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
+    return PT_OK;
+}
+
+extern "C" int pt_render_features_rays(pt_ctx* c, const pt_params* p, const float* rays, pt_feature* feat)
+{
+    pt::clear_error();
+    pt_params pv;
+    if (int rc = features_rays_check(c, p, rays, feat, &pv)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = (size_t)p->width * (size_t)p->height;
+    if (int rc = pt::grow(&c->rays_stage, &c->rays_stage_floats, n * 6)) return rc;
+    HIP_TRY(hipMemcpy(c->rays_stage, rays, n * 24, hipMemcpyHostToDevice));
+    std::vector<pt_feature> host(n);   // (the caller's buffer is written only once the call has succeeded)
+    pt_feature none;
+    memset(&none, 0, sizeof(none));
+    none.prim = -1;
+    for (size_t i = 0; i < n; ++i) host[i] = none;   // pixels outside the shard stay like this
+    pt::ScopedDevice<pt_feature> d_feat;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_feat), n * sizeof(pt_feature)));
+    HIP_TRY(hipMemcpy(d_feat, host.data(), n * sizeof(pt_feature), hipMemcpyHostToDevice));
+    if (int rc = pt_render_features_rays_device(c, p, c->rays_stage, d_feat, nullptr)) return rc;
     HIP_TRY(hipMemcpy(feat, d_feat, n * sizeof(pt_feature), hipMemcpyDeviceToHost));
     return PT_OK;
 }

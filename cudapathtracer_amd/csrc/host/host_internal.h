@@ -56,11 +56,21 @@ struct AccumPass {
     // ascending) are sampled, one whole-pixel unit each; null: every pixel of the shard, as planned by plan_units
     const uint32_t* active = nullptr;
     uint32_t nactive = 0;
+    // a pass of a ray accumulator (pt_accum_create_rays*): its own copy of the rays (device, width * height * 6 floats,
+    // every one regular), indexed in the accumulator's pixel order; cam is then the stand-in of accum_check_rays
+    const float* rays = nullptr;
 };
 // Validates (params, cam) as pt_render_device_async does and refuses every mode without an accumulating
 // kernel (render_tiles, the counting variants, non-default occupancy).
 // (view: the accumulator's pt_view, or null for the reference camera)
 int accum_check(const pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view);
+// The same for an accumulator over a ray buffer (pt_accum_create_rays*): the flags a ray render and an accumulator
+// both take, the parameters, the kernels.  *stand_in: the camera the passes are enqueued with -- at the origin, it
+// carries the image size alone.
+int accum_check_rays(const pt_ctx* c, const pt_params* p, pt_camera* stand_in);
+// Classifies the accumulator's own ray copy (device, width * height rays) and refuses it unless every ray is regular:
+// an invalid ray with its lowest pixel named, irregular rays with their count.  Blocking.
+int accum_classify_rays(pt_ctx* c, const pt_params* p, const float* d_rays, void* stream);
 // p->spp more samples of every pixel (of every active pixel), blocking; d_out (device, W*H*3) may be null.
 int accum_pass(pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view, const AccumPass& acc, float* d_out,
                void* stream, pt_stats* stats);

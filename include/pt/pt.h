@@ -847,10 +847,12 @@ int pt_occluded(pt_ctx* ctx, uint32_t n, const float* rays, const float* tmax /*
  * the host before the launch.  Only the default PT_WF_MIN_WAVES / PT_HEAD_MIN_WAVES have kernels: a context created
  * with other values is refused (PT_E_INVALID) where the render would take the wavefront kernels.
  *
- * Out of scope: accumulators and everything on top of them (noise estimates, adaptive sampling, sessions) over a
- * ray buffer; pt_render_group / pt_render_multi; features, denoising and temporal reprojection for ray renders; a
- * per-sample ray source (anti-aliasing or depth of field for custom projections); masked or empty pixels -- a
- * caller compacts its rays or pads them with any valid ray. */
+ * Accumulators (with noise estimates, the convergence stop and adaptive sampling), masked pixels and feature buffers
+ * over a ray buffer: pt_accum_create_rays* and pt_render_features_rays*, below the denoisers.
+ *
+ * Out of scope: sessions and checkpoints over a ray buffer; pt_render_group / pt_render_multi; temporal reprojection
+ * for ray renders; a per-sample ray source (anti-aliasing or depth of field for custom projections); passes from the
+ * command line (pt_cli --rays renders one shot). */
 typedef struct { uint64_t regular, irregular, invalid; uint32_t first_invalid; uint32_t pad; } pt_ray_classes;
 int pt_render_rays_device(pt_ctx* ctx, const pt_params* params, const float* d_rays, float* d_out, void* stream,
                           pt_stats* stats);
@@ -987,6 +989,64 @@ int pt_denoise_guided_device(pt_ctx* ctx, const pt_denoise_guided_params* gp, in
                              const float* d_in, const pt_feature* d_feat, const float* d_var, float* d_out, void* stream);
 int pt_denoise_guided(pt_ctx* ctx, const pt_denoise_guided_params* gp, int width, int height, int pixel_order,
                       const float* in, const pt_feature* feat, const float* var, float* out /* host */);
+
+/* ----------------------------------------------- accumulators and feature buffers over caller-supplied rays
+ * The progressive and the denoising layers over a ray buffer (see "renders along caller-supplied rays" above for the
+ * buffer, its indexing and the ray classes): long bakes and probes in passes with a convergence stop and adaptive
+ * sampling, and guide records for a panorama or fisheye preview.
+ *
+ * RAY ACCUMULATORS.  rays holds width * height * 6 floats indexed in params->pixel_order, as for pt_render_rays*; a
+ * device buffer must be 8-byte aligned.  Ownership: the accumulator keeps its rays for life, as a camera accumulator
+ * keeps its camera -- create copies the whole buffer into device memory it owns (24 B per pixel, freed by
+ * pt_accum_destroy), so the caller's buffer may be freed or overwritten once create has returned.
+ *
+ * Arithmetic (a definition): pixel (x, y) after n samples holds the f64 mean of
+ *     rng = curand_init(seed, morton(x, y), 0)
+ *     for k = 1..n:  L = integrator(o, d, rng);  m = m*(k-1)/k + L/k
+ * with no lens draws anywhere (Morton index 0 is no lens pixel), so pt_accum_add in any split of passes equals
+ * pt_render_rays of the same total in every bit.
+ *
+ * Order of the checks at create: a null argument; asynchronous renders in flight; the flags; the parameters (as
+ * pt_render_rays_device validates them); the kernels (below); the device buffer's alignment; then all width *
+ * height rays (not only the shard's) are classified, once, on the accumulator's own copy.  Every refusal is
+ * PT_E_INVALID with *err set and NULL returned:
+ *     flags      only 0, PT_FLAG_NO_DEAD_PATH_SKIP and PT_FLAG_NO_PRIMARY_CACHE -- the flags pt_render_rays and
+ *                pt_accum_create both take; the jitter, counting and reference flags and unknown bits are refused
+ *     kernels    a context with a non-default PT_WF_MIN_WAVES / PT_HEAD_MIN_WAVES, or integrator 1 with PT_HEAD_WF=0,
+ *                as pt_accum_create refuses them
+ *     invalid    a buffer with an invalid ray, the message naming the lowest such pixel as pt_render_rays does
+ *     irregular  a buffer with an irregular ray: accumulation runs on the wavefront kernels only and there is never a
+ *                silent fall-back; the message gives the count and says that pt_render_rays takes such a buffer
+ * Everything else works unchanged on a ray accumulator: pt_accum_add, _samples, _read, _freeze, _counts, _active,
+ * _add_until, _add_adaptive, pt_noise_* (pt_noise_variance*, pt_noise_freeze included) and pt_accum_destroy.  Shards,
+ * tile sizes, Morton order, empty shards and split units behave as documented for camera accumulators.  Once a pixel
+ * is frozen, passes run over the active list with a set-up kernel that reads each unit's direction from the buffer.
+ * pt_accum_view reports has_view = 0; pt_accum_has_rays is 1 for a ray accumulator, 0 for any other and for NULL.
+ *
+ * MASKED PIXELS (a lightmap texel that belongs to no chart, a fisheye's corners): pt_accum_freeze at 0 samples is the
+ * mask.  Such a pixel stays at mean 0 and count 0 and is never sampled.  Its ray must still be valid and regular: the
+ * caller pads it with any such ray.
+ *
+ * pt_accum_save and pt_session_save refuse a ray accumulator with PT_E_INVALID: both formats hold a camera, not a ray
+ * buffer.
+ *
+ * RAY FEATURES.  One pt_feature per pixel for the buffer's ray as given: no normalisation, no 0 + o.  Of params the
+ * fields pt_render_features* uses are used; flags is ignored, and nothing jitters.  Each ray takes the walk
+ * pt_trace(flags = 0) gives it -- regular or irregular, inside or outside the Markstein ranges -- so an irregular
+ * ray is legal here.  depth is trace()'s closestT along the given d: for a direction that is not of unit length it is
+ * in units of |d|.  position = o + d * depth, per component in f32.  The other fields are pt_render_features'.
+ * Order of the checks: a null argument; asynchronous renders in flight; the parameters; the scene's size (30 id
+ * bits); _device: d_feat's 16-byte alignment; d_rays' 8-byte alignment; then an invalid ray anywhere in the buffer
+ * (not only in the shard) refuses the call (PT_E_INVALID, the lowest pixel named) with nothing written.  _device
+ * writes only this shard's pixels; the host variant writes the rest as zero bytes with prim = -1.  Both block.
+ * pt_denoise* and pt_denoise_guided* take these records as they stand.
+ *
+ * Out of scope: see the list under pt_render_rays. */
+pt_accum* pt_accum_create_rays_device(pt_ctx* ctx, const pt_params* params, const float* d_rays, void* stream, int* err);
+pt_accum* pt_accum_create_rays(pt_ctx* ctx, const pt_params* params, const float* rays /* host */, int* err);
+int pt_accum_has_rays(const pt_accum* acc);   /* 1 / 0; 0 for NULL */
+int pt_render_features_rays_device(pt_ctx* ctx, const pt_params* params, const float* d_rays, pt_feature* d_feat, void* stream);
+int pt_render_features_rays(pt_ctx* ctx, const pt_params* params, const float* rays /* host */, pt_feature* feat /* host */);
 
 /* ------------------------------------------------- temporal reprojection: keep the samples when the camera moves
  * An accumulator keeps its camera and view for life, so a moving camera starts from 1-spp noise every frame.  Every

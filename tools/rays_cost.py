@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Cost of rendering along caller-supplied rays: the stand-in at 1920x1080, 16 spp.
 
-    python tools/rays_cost.py [--spp 16] [--rounds 5] [--integrator 0] [--out FILE.json]
+    python tools/rays_cost.py [--spp 16] [--rounds 5] [--integrator 0] [--accum [--pass-spp 4]] [--out FILE.json]
 
 Alternated in one run, medians over the rounds:
   * render_rays_device on the camera's own rays against render_device of the same camera (the two trace the same rays,
@@ -11,6 +11,13 @@ Alternated in one run, medians over the rounds:
     floor (timed with events around each, same stream);
   * at --small-width x --small-height and --small-spp: a buffer with one far ray and one unnormalised direction -- the
     whole render on the tile kernel with the reference's walk -- against the regular buffer it was made from.
+With --accum, after those (accumulators and feature buffers over rays, the camera's own rays against the camera):
+  * a --pass-spp accumulating pass of a ray accumulator against the camera accumulator's;
+  * the same pass over the active list, with about 50% and about 10% of the pixels active (the others masked at 0 samples
+    by the same random mask on both sides);
+  * features_rays_device against features_device (events around the blocking calls);
+  * the create call -- the copy of the buffer and its classification on top of a camera accumulator's allocations --
+    against creating the camera accumulator (host wall time of the blocking calls).
 Prints one JSON line per block and one of ratios, each ratio with the smallest and largest per-round ratio beside the
 ratio of the medians.  --out also keeps the lines in a file.
 """
@@ -20,6 +27,7 @@ import os
 import statistics
 import sys
 import tempfile
+import time
 
 import numpy as np
 import torch
@@ -42,6 +50,82 @@ def _ratio(num, den):
     return dict(of_medians=statistics.median(num) / statistics.median(den), min=min(per_round), max=max(per_round))
 
 
+def accum_blocks(r, a, cam, d_rays, w, h):
+    """The --accum blocks: lines of passes, active-list passes, features and the create call, and their ratios."""
+    n = w * h
+    make = {"rays": lambda: r.accumulator_rays_device(d_rays.data_ptr(), w, h, 3, a.integrator, 1234),
+            "camera": lambda: r.accumulator(cam, w, h, 3, a.integrator, 1234)}
+    kinds = ["camera", "rays"]
+    lines, ratios = [], {}
+    rs = np.random.RandomState(5)
+    for label, active in (("all", 1.0), ("half", 0.5), ("tenth", 0.1)):
+        mask = rs.uniform(size=(h, w)) >= active                 # the masked pixels
+        accs = {k: make[k]() for k in kinds}
+        try:
+            for k in kinds:
+                if mask.any():
+                    accs[k].freeze(mask)
+                accs[k].add(1)                                   # warm-up: buffers, the active list
+            t = {k: dict(seconds=[], kernel_ms=[]) for k in kinds}
+            units = {}
+            for _ in range(a.rounds):
+                for k in kinds:                                  # alternated
+                    st = accs[k].add(a.pass_spp)
+                    t[k]["seconds"].append(st["seconds"])
+                    t[k]["kernel_ms"].append(st["kernel_ms"])
+                    units[k] = st["work_units"]
+        finally:
+            for acc in accs.values():
+                acc.close()
+        line = dict(block="accum_pass_" + label, integrator=a.integrator, width=w, height=h, pass_spp=a.pass_spp, rounds=a.rounds,
+                    active_pixels=int(n - mask.sum()))
+        for k in kinds:
+            sec, kms = statistics.median(t[k]["seconds"]), statistics.median(t[k]["kernel_ms"])
+            line[k] = dict(seconds=sec, kernel_ms=kms, setup_ms=sec * 1e3 - kms, seconds_min=min(t[k]["seconds"]),
+                           seconds_max=max(t[k]["seconds"]), work_units=units[k])
+        lines.append(line)
+        ratios["accum_pass_%s_rays_over_camera" % label] = _ratio(t["rays"]["seconds"], t["camera"]["seconds"])
+    # ---- the features kernels
+    feat = torch.zeros((n * 48,), dtype=torch.uint8, device="cuda")
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    t_cam, t_rays = [], []
+    r.features_device(cam, feat.data_ptr(), w, h)
+    r.features_rays_device(d_rays.data_ptr(), feat.data_ptr(), w, h)
+    for _ in range(max(a.rounds, 5) * 2):
+        ev[0].record()
+        r.features_device(cam, feat.data_ptr(), w, h)
+        ev[1].record()
+        ev[2].record()
+        r.features_rays_device(d_rays.data_ptr(), feat.data_ptr(), w, h)   # (classifies the buffer first)
+        ev[3].record()
+        torch.cuda.synchronize()
+        t_cam.append(ev[0].elapsed_time(ev[1]))
+        t_rays.append(ev[2].elapsed_time(ev[3]))
+    lines.append(dict(block="features", width=w, height=h, features_ms=statistics.median(t_cam), features_ms_min=min(t_cam),
+                      features_rays_ms=statistics.median(t_rays), features_rays_ms_min=min(t_rays),
+                      note="events around the blocking calls; features_rays includes the classification of the buffer"))
+    ratios["features_rays_over_features"] = _ratio(t_rays, t_cam)
+    # ---- the create call
+    t_create = {k: [] for k in kinds}
+    for k in kinds:
+        make[k]().close()
+    for _ in range(max(a.rounds, 5)):
+        for k in kinds:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            acc = make[k]()
+            t_create[k].append((time.perf_counter() - t0) * 1e3)
+            acc.close()
+    lines.append(dict(block="create", width=w, height=h, rays_bytes=n * 24,
+                      create_rays_ms=statistics.median(t_create["rays"]), create_rays_ms_min=min(t_create["rays"]),
+                      create_camera_ms=statistics.median(t_create["camera"]), create_camera_ms_min=min(t_create["camera"]),
+                      copy_and_classify_ms=statistics.median(t_create["rays"]) - statistics.median(t_create["camera"]),
+                      note="host wall time of the blocking create calls; the difference is the ray copy's allocation, the "
+                           "device-to-device copy and the classification"))
+    lines.append(dict(ratios=ratios))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--spp", type=int, default=16)
@@ -53,6 +137,8 @@ def main():
     ap.add_argument("--small-height", type=int, default=144)
     ap.add_argument("--small-spp", type=int, default=4)
     ap.add_argument("--cache-dir", default=os.path.join(tempfile.gettempdir(), "pt_bench_scene"))
+    ap.add_argument("--accum", action="store_true")
+    ap.add_argument("--pass-spp", type=int, default=4)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     p = os.path.join(a.cache_dir, "models", "sponza_standin.obj")
@@ -144,6 +230,8 @@ def main():
             panorama_rays_over_plain=_ratio(t["panorama_rays"]["seconds"], t["plain"]["seconds"]),
             classify_over_copy=_ratio(t_cls, t_copy),
             irregular_over_regular=_ratio(ti["irregular"], ti["regular"]))))
+        if a.accum:
+            lines.extend(accum_blocks(r, a, cam, bufs["camera_rays"], w, h))
     for line in lines:
         print(json.dumps(line))
     if a.out:
