@@ -97,6 +97,15 @@ def lib(variant=None):
         h.or_render.argtypes = [C.POINTER(OScene), C.POINTER(OCamera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.POINTER(OCounters)]
         h.or_render.restype = C.c_int
+        h.or_radiance_unidir.argtypes = [C.POINTER(OScene), OVec3, OVec3, C.c_int, C.POINTER(OXorwow),
+                                         C.POINTER(C.c_double * 3), C.POINTER(OCounters)]
+        h.or_radiance_unidir.restype = None
+        h.or_radiance_head.argtypes = [C.POINTER(OScene), OVec3, OVec3, C.POINTER(OXorwow), C.POINTER(C.c_double * 3),
+                                       C.POINTER(OCounters)]
+        h.or_radiance_head.restype = None
+        h.or_radiance_batch.argtypes = [C.POINTER(OScene), C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]
+        h.or_radiance_batch.restype = C.c_int
         h.or_write_ppm_imgbuf.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int]
         h.or_write_ppm_imgbuf.restype = C.c_int
         _libs[variant] = h
@@ -217,8 +226,129 @@ def helpers(normals, albedos, variant=None):
     return tan, brdf
 
 
-def refgen_available():
-    return os.path.exists(REFGEN)
+REF_TREE = os.environ.get("REF", "/root/reference")   # oracle/Makefile's REF: where refgen is compiled from
+
+
+def refgen_available(command=None):
+    """Whether oracle/_ref/refgen exists and, with `command`, knows that command (a binary built by an older
+    oracle/Makefile answers "unknown command" to the newer ones).  Looks only; builds nothing."""
+    if not os.path.exists(REFGEN):
+        return False
+    if command is None:
+        return True
+    p = subprocess.run([REFGEN, command], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)
+    return b"unknown command" not in p.stderr
+
+
+def ensure_refgen(command):
+    """A refgen that knows `command`, rebuilt from the reference tree if the one here is missing or older than
+    oracle/Makefile.  False only where there is no reference tree to build it from; a build that fails raises, and so
+    does a fresh build that still lacks the command."""
+    if refgen_available(command):
+        return True
+    if not os.path.isdir(REF_TREE):
+        return False
+    subprocess.check_call(["make", "-s", "-C", HERE, "refgen"])
+    if not refgen_available(command):
+        raise RuntimeError("oracle/_ref/refgen was rebuilt and still has no `%s` command" % command)
+    return True
+
+
+def xorwow_states(seed, subsequences):
+    """or_xorwow_init(seed, s) for every s: uint32 (n, 6) rows {d, v[5]}, the layout of curandStateXORWOW's words."""
+    out = np.empty((len(subsequences), 6), dtype=np.uint32)
+    st = OXorwow()
+    for i, s in enumerate(subsequences):
+        lib().or_xorwow_init(int(seed), int(s), C.byref(st))
+        out[i] = (st.d, *st.v)
+    return out
+
+
+def camera_rays(cam: OCamera, width, height):
+    """or_camera_ray of every pixel without lens draws (radius 0, as or_render calls it for Morton index > 0):
+    float32 (H*W, 6) rows {o, d} in scanline order y*W + x."""
+    out = np.empty((height * width, 6), dtype=np.float32)
+    o, d = OVec3(), OVec3()
+    nan = float("nan")
+    for y in range(height):
+        for x in range(width):
+            lib().or_camera_ray(C.byref(cam), lib().or_morton_pxl_to_i(x, y), nan, nan, C.byref(o), C.byref(d))
+            out[y * width + x] = (o.x, o.y, o.z, d.x, d.y, d.z)
+    return out
+
+
+def _state(words):
+    st = OXorwow()
+    st.d = int(words[0])
+    for k in range(5):
+        st.v[k] = int(words[1 + k])
+    return st
+
+
+def radiance_unidir(scene: OracleScene, o, d, bounces, state, variant=None):
+    """or_radiance_unidir (integrator 0) for one sample from the stream state `state` (6 words {d, v[5]}):
+    returns (colour f64[3], end state uint32[6])."""
+    st = _state(state)
+    out = (C.c_double * 3)()
+    lib(variant).or_radiance_unidir(C.byref(scene.c), OVec3(*[float(v) for v in o]), OVec3(*[float(v) for v in d]),
+                                    int(bounces), C.byref(st), C.byref(out), None)
+    return np.array(out[:], dtype=np.float64), np.array([st.d, *st.v], dtype=np.uint32)
+
+
+def radiance_head(scene: OracleScene, o, d, state, variant=None):
+    """or_radiance_head (integrator 1) for one sample; as radiance_unidir."""
+    st = _state(state)
+    out = (C.c_double * 3)()
+    lib(variant).or_radiance_head(C.byref(scene.c), OVec3(*[float(v) for v in o]), OVec3(*[float(v) for v in d]),
+                                  C.byref(st), C.byref(out), None)
+    return np.array(out[:], dtype=np.float64), np.array([st.d, *st.v], dtype=np.uint32)
+
+
+def radiance_batch(scene: OracleScene, integrator, bounces, rays, states, variant=None):
+    """One sample per record (or_radiance_batch, OpenMP): rays float32 (n, 6) = {o, d}, states uint32 (n, 6).
+    Returns (colours f64 (n, 3), end states uint32 (n, 6)); the inputs are left unchanged."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    st = np.array(states, dtype=np.uint32).reshape(-1, 6)
+    assert len(st) == len(rays)
+    out = np.zeros((len(rays), 3), dtype=np.float64)
+    if lib(variant).or_radiance_batch(C.byref(scene.c), int(integrator), int(bounces), len(rays), rays.ctypes.data,
+                                      st.ctypes.data, out.ctypes.data) != 0:
+        raise ValueError("or_radiance_batch: bad integrator or depth")
+    return out, st
+
+
+REF_SAMPLE = np.dtype([("o", "<f4", (3,)), ("d", "<f4", (3,)), ("state", "<u4", (6,))])
+REF_RESULT = np.dtype([("colour", "<f8", (3,)), ("state", "<u4", (6,)), ("flag", "<u4"), ("misses", "<u4")])
+
+
+def ref_radiance(flavour, integrator, bounces, rays, states, loads, cwd, workdir):
+    """The reference's OWN integrators (refgen radiance: kernel.cu:217-515 and :56-99 compiled verbatim over the
+    XORWOW stand-in), one sample per record.  flavour: "libm" (glibc cosf/sinf) or "det" (or_sincos).  loads: the
+    (obj, origin, scale, flip) list, paths relative to cwd.  Returns a REF_RESULT array: colour, end state, flag
+    (1 = integrator 1's camera bounce missed: the reference reads tris[-1] there, decision d2) and the mask of
+    trace-call ordinals that missed.  Build container only (needs oracle/_ref/refgen)."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    rec = np.zeros(len(rays), dtype=REF_SAMPLE)
+    rec["o"], rec["d"] = rays[:, :3], rays[:, 3:]
+    rec["state"] = np.asarray(states, dtype=np.uint32).reshape(-1, 6)
+    inp, outp = os.path.join(workdir, "radiance.in"), os.path.join(workdir, "radiance.out")
+    rec.tofile(inp)
+    args = [REFGEN, "radiance", flavour, str(int(integrator)), str(int(bounces)), inp, outp]
+    for obj, origin, scale, flip in loads:
+        args += [obj, *[repr(float(v)) for v in origin], repr(float(scale)), str(int(flip))]
+    subprocess.check_call(args, cwd=cwd, stdout=subprocess.DEVNULL)
+    return np.fromfile(outp, dtype=REF_RESULT)
+
+
+def ref_mean(colours, workdir):
+    """The reference's OWN running mean (refgen mean: kernel.cu:551-552 compiled verbatim) over colours
+    f64 (n, spp, 3): returns f64 (n, 3).  Build container only."""
+    c = np.ascontiguousarray(colours, dtype=np.float64)
+    n, spp = c.shape[0], c.shape[1]
+    inp, outp = os.path.join(workdir, "mean.in"), os.path.join(workdir, "mean.out")
+    c.tofile(inp)
+    subprocess.check_call([REFGEN, "mean", inp, outp, str(spp)], stdout=subprocess.DEVNULL)
+    return np.fromfile(outp, dtype="<f8").reshape(n, 3)
 
 
 def write_ppm_imgbuf(path, imgbuf, width, height):

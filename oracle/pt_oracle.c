@@ -725,6 +725,28 @@ void or_radiance_head(const or_scene* sc, or_vec3 cam_o, or_vec3 cam_d,
     out[0] = accum.r; out[1] = accum.g; out[2] = accum.b;
 }
 
+/* One sample per record of either integrator, from a stream state the caller supplies (no or_xorwow_init, no
+ * lens draws): rays[6r] = {o.xyz, d.xyz}, states[6r] = {d, v[5]} advanced in place, out[3r] the colour. */
+int or_radiance_batch(const or_scene* sc, int integrator, int bounces, uint32_t n, const float* rays,
+                      uint32_t* states, double* out)
+{
+    if ((integrator != 0 && integrator != 1) || bounces < 1) return -1;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 64)
+#endif
+    for (long r = 0; r < (long)n; ++r) {
+        const float* q = rays + 6 * r;
+        or_vec3 o = {q[0], q[1], q[2]}, d = {q[3], q[4], q[5]};
+        or_xorwow st;
+        or_counters c = {0, 0, 0, NULL};
+        memcpy(&st, states + 6 * r, sizeof(st));
+        if (integrator == 1) or_radiance_head(sc, o, d, &st, out + 3 * r, &c);
+        else or_radiance_unidir(sc, o, d, bounces, &st, out + 3 * r, &c);
+        memcpy(states + 6 * r, &st, sizeof(st));
+    }
+    return 0;
+}
+
 /* ------------------------------------------------------------------ render */
 /* Camera draws (kernel.cu:547 reads &randState[0] from every thread: a race).  Decision d1:
  * a pixel consumes the two lens draws from its own stream iff it is Morton index 0 (the

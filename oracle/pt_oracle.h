@@ -20,12 +20,23 @@
  *     original CUDA binary's RNG is unpinned; the recurrence and the 2^67
  *     subsequence jump ARE pinned against rocRAND's precomputed matrices).
  *
- * Pinning: kernel.cu cannot be built here (CUDA/cuRAND/NVML/windows.h
- * absent, triple.h broken), so the integrator itself is a restatement.  Its
- * building blocks (triIntersect, rayAABBIntersect, cameraRay, Morton maps, OBJ
- * ingest, BVH build) are pinned against golden vectors emitted by the
- * reference's own sources compiled with g++ (oracle/refgen, outputs in
- * tests/golden).
+ * Pinning: kernel.cu cannot be built here as a whole (CUDA/cuRAND/NVML/
+ * windows.h absent, triple.h broken), so this file is a restatement.  It is pinned
+ * against golden vectors emitted by the reference's own sources compiled with g++
+ * (oracle/refgen, outputs in tests/golden):
+ *   - the building blocks: triIntersect, rayAABBIntersect, trace, cameraRay, Morton
+ *     maps, getTangent/BRDF, the PPM loop, OBJ ingest, BVH build;
+ *   - the integrators' composition, given a stream: radianceAlongSingleStep{,2}
+ *     (kernel.cu:217-515), the samplers randRay/cosineWeightedRay (:56-99) and the
+ *     running mean (:551-552), compiled verbatim over a stand-in that supplies only
+ *     the XORWOW recurrence and the uniform conversion, from start states given as
+ *     input.  Colour (3 x f64) and end state of every sample, bit for bit
+ *     (tests/test_integrator_host.py; refgen.cpp's header lists the bindings:
+ *     NUM_BOUNCES, a recording wrapper of trace, CUDA's max, and cos/sin bound to
+ *     or_sincos for the `det` flavour only).
+ * Still unpinned: cuRAND's seeding salts (above), the argument order of the two lens
+ * draws (kernel.cu:547, decision d1) and the camera-bounce miss of integrator 1,
+ * where the reference reads tris[-1] (decision d2: the reference cannot arbitrate).
  */
 #ifndef PT_ORACLE_H
 #define PT_ORACLE_H
@@ -102,6 +113,11 @@ void     or_radiance_unidir(const or_scene* sc, or_vec3 o, or_vec3 dir, int boun
 /* kernel.cu:217-415 radianceAlongSingleStep (integrator 1, HEAD default) */
 void     or_radiance_head(const or_scene* sc, or_vec3 o, or_vec3 dir,
                           or_xorwow* rng, double out[3], or_counters* cnt);
+
+/* One sample per record of integrator 0 / 1 from caller-supplied stream states (OpenMP): rays[6n] = {o.xyz, d.xyz},
+ * states[6n] = {d, v[5]} advanced in place, out[3n].  Returns 0, or -1 for a bad integrator or depth. */
+int      or_radiance_batch(const or_scene* sc, int integrator, int bounces, uint32_t n, const float* rays,
+                           uint32_t* states, double* out);
 
 /* Render the pixels listed in `pixels` (scanline ids y*W+x) with `spp` samples each,
  * writing the f64 running mean (kernel.cu:551-552) into out[(y*W+x)*3 + c].

@@ -35,8 +35,34 @@
 //                PPM is written by the reference's own output loop (kernel.cu:763-778, "save the file"),
 //                extracted verbatim into oracle/_ref/ref_ppm.inc by oracle/Makefile, with IMAGE_WIDTH /
 //                IMAGE_HEIGHT (kernel.cu:28-29 #defines) bound to W and H
+//   refgen radiance <libm|det> <integrator> <bounces> <in.bin> <out.bin> <obj> <ox> <oy> <oz> <scale> <flip> [<obj> ...]
+//                in: n x {o[3], d[3] f32, state 6 x u32 (d, v[5])}; out: n x {colour 3 x f64, end state 6 x u32,
+//                flag u32, miss mask u32}.  One sample per record of the reference's own integrators, compiled
+//                verbatim: integrator 0 = radianceAlongSingleStep2 (kernel.cu:417-515), 1 = radianceAlongSingleStep
+//                (:217-415), with the samplers nrand/randRay/cosineWeightedRay (:56-99).  oracle/Makefile extracts
+//                the spans into oracle/_ref/ref_samplers.inc and ref_integ.inc.  What is NOT the reference's text:
+//                  - curandState / curand_uniform: a stand-in below (the XORWOW recurrence and the uniform
+//                    conversion only).  There is no curand_init: every record brings its start state.
+//                  - NUM_BOUNCES (kernel.cu:33 #define, outside the spans) is bound to a variable, as ppm binds
+//                    IMAGE_WIDTH; integrator 1 does not read it.
+//                  - `trace` is bound, while the spans are included, to a wrapper around the verbatim trace()
+//                    above that records which call ordinals of the sample missed (bit k of the miss mask = call k).
+//                  - max(): CUDA's device max on float/double is fmaxf/fmax (a NaN operand is ignored), std::max is
+//                    not; the spans are included inside a namespace that declares max with CUDA's meaning.
+//                  - the spans are included twice, in two namespaces: `libm` as they stand (cos/sin are glibc's
+//                    cosf/sinf through <math.h>'s float overloads), `det` with cos/sin bound to the oracle's
+//                    or_sincos (pt_oracle.c is linked) while the SAMPLERS' span is included, #undef'ed after it.
+//                  - scene.tris is preceded by one sentinel record, a copy of triangle 0: integrator 1 reads
+//                    scene.tris[-1] when its camera bounce misses (kernel.cu:333-346), which is undefined in the
+//                    reference; the sentinel makes the run defined, and flag = 1 marks the sample "reference
+//                    undefined (d2)": integrator 1 and its third trace call (the camera bounce, :333) missed.
+//   refgen mean  <in.bin> <out.bin> <spp>
+//                in: n x spp x 3 f64 sample colours; out: n x 3 f64, the reference's running mean: imgBuff starts
+//                at color(0,0,0) (kernel.cu:525) and the two statements of kernel.cu:551-552, extracted verbatim into
+//                oracle/_ref/ref_mean.inc, fold samples curSampleNum = 1..spp
 #include <cstdint>
 #include <cmath>
+#include <math.h>          // kernel.cu:8 includes it: cos/sin/sqrt of a float are the float overloads
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -52,12 +78,72 @@ using std::abs;
 #include "/root/reference/modelLoader.h"
 #include "/root/reference/BVH.h"
 #include "/root/reference/camera.h"
+#include "/root/reference/SIUnits.h"
 #ifdef REFGEN_HELPERS
 #include REFGEN_HELPERS    // kernel.cu:44-54 getTangent and :101-104 BRDF, extracted verbatim by oracle/Makefile
 #endif
 #ifdef REFGEN_TRACE
 #define MAX_BVH_DEPTH 64   // kernel.cu:35
 #include REFGEN_TRACE      // kernel.cu:107-161, extracted verbatim by oracle/Makefile
+#endif
+
+#if defined(REFGEN_INTEG) && defined(REFGEN_SAMPLERS) && defined(REFGEN_TRACE) && defined(REFGEN_HELPERS)
+#define REFGEN_RADIANCE 1
+#include "../pt_oracle.h"   // or_sincos, for the det flavour only
+
+static_assert(sizeof(decltype(cos(1.0f))) == sizeof(float) && sizeof(decltype(sqrt(1.0f))) == sizeof(float),
+              "cos/sqrt of a float must be the float overloads, as in the reference's CUDA build");
+
+// ---- the cuRAND stand-in (this project's text): curandStateXORWOW's d, v[5], curand()'s recurrence and
+// curand_uniform's conversion x * 2^-32 + 2^-33, fused.  Nothing of curand_init.
+struct curandState { uint32_t d, v[5]; };
+static inline uint32_t curand(curandState* s)
+{
+    const uint32_t t = s->v[0] ^ (s->v[0] >> 2);
+    s->v[0] = s->v[1]; s->v[1] = s->v[2]; s->v[2] = s->v[3]; s->v[3] = s->v[4];
+    s->v[4] = (s->v[4] ^ (s->v[4] << 4)) ^ (t ^ (t << 1));
+    s->d += 362437u;
+    return s->v[4] + s->d;
+}
+static inline float curand_uniform(curandState* s)
+{
+    return fmaf((float)curand(s), 2.3283064e-10f, 2.3283064e-10f / 2.0f);
+}
+
+static int refgen_num_bounces = 3;
+static uint32_t refgen_trace_calls = 0, refgen_trace_misses = 0;
+static triIntersection refgen_trace(ray r, sceneDesc scene, BVH_array bvh, uint32_t* test)
+{
+    const triIntersection h = trace(r, scene, bvh, test);                                // kernel.cu:112, verbatim
+    if (h.triIndex < 0 && refgen_trace_calls < 32) refgen_trace_misses |= 1u << refgen_trace_calls;
+    ++refgen_trace_calls;
+    return h;
+}
+static inline float refgen_det_cos(float x) { float s, c; or_sincos(x, &s, &c); return c; }
+static inline float refgen_det_sin(float x) { float s, c; or_sincos(x, &s, &c); return s; }
+
+#define REFGEN_CUDA_MAX \
+    static inline float max(float a, float b) { return fmaxf(a, b); } \
+    static inline double max(double a, double b) { return fmax(a, b); } \
+    static inline int max(int a, int b) { return a < b ? b : a; }
+#define NUM_BOUNCES refgen_num_bounces
+#define trace refgen_trace
+namespace ref_libm {
+REFGEN_CUDA_MAX
+#include REFGEN_SAMPLERS   // kernel.cu:56-99, verbatim
+#include REFGEN_INTEG      // kernel.cu:217-515, verbatim
+}
+namespace ref_det {
+REFGEN_CUDA_MAX
+#define cos(x) refgen_det_cos(x)
+#define sin(x) refgen_det_sin(x)
+#include REFGEN_SAMPLERS   // kernel.cu:56-99, verbatim, cos/sin bound to or_sincos
+#undef cos
+#undef sin
+#include REFGEN_INTEG      // kernel.cu:217-515, verbatim
+}
+#undef trace
+#undef NUM_BOUNCES
 #endif
 
 static std::vector<char> slurp(const char* path)
@@ -242,6 +328,87 @@ int main(int argc, char** argv)
             memcpy(&out[40 * i + 16], bv, 24);
         }
         spit(argv[3], out.data(), out.size());
+        return 0;
+    }
+#endif
+#ifdef REFGEN_RADIANCE
+    if (cmd == "radiance") {
+        if (argc < 13) { fprintf(stderr, "refgen radiance: too few arguments\n"); return 2; }
+        const std::string flavour = argv[2];
+        const int integrator = atoi(argv[3]);
+        refgen_num_bounces = atoi(argv[4]);
+        if ((flavour != "libm" && flavour != "det") || (integrator != 0 && integrator != 1) ||
+            refgen_num_bounces < 1 || refgen_num_bounces > 32) {
+            fprintf(stderr, "refgen radiance: bad flavour, integrator or bounces\n");
+            return 2;
+        }
+        std::vector<char> in = slurp(argv[5]);
+        const size_t n = in.size() / 48;
+        for (int a = 7; a + 5 < argc; a += 6) {
+            vec3 origin((float)atof(argv[a + 1]), (float)atof(argv[a + 2]), (float)atof(argv[a + 3]));
+            loadOBJ(argv[a], origin, (float)atof(argv[a + 4]), atoi(argv[a + 5]) != 0);   // modelLoader.h:125
+        }
+        if (tris.size() < 2) { fprintf(stderr, "refgen radiance: need >= 2 triangles\n"); return 2; }
+        BVH_array bvh = buildBVH();                                                      // BVH.h:443
+        if (bvh.depth >= MAX_BVH_DEPTH) { fprintf(stderr, "refgen radiance: BVH depth too big\n"); return 2; }   // kernel.cu:627
+        std::vector<triangle> tris_s(tris.size() + 1);   // [0]: the sentinel scene.tris[-1] reads, a copy of triangle 0
+        tris_s[0] = tris[0];
+        std::copy(tris.begin(), tris.end(), tris_s.begin() + 1);
+        sceneDesc scene;                                                                 // kernel.cu:664-689
+        scene.numVerts = (uint32_t)verts.size(); scene.verts = verts.data();
+        scene.numTris = (uint32_t)tris.size(); scene.tris = tris_s.data() + 1;
+        scene.numMats = (uint32_t)mats.size(); scene.mats = mats.data();
+        scene.numLights = (uint32_t)lights.size(); scene.lights = (uint32_t*)lights.data();
+        scene.totalLightArea = totalLightArea;
+        std::vector<uint32_t> test(tris.size(), 0u);
+        std::vector<char> out(n * 56);
+        const bool det = flavour == "det";
+        for (size_t i = 0; i < n; ++i) {
+            float p[6];
+            curandState st;
+            memcpy(p, &in[48 * i], 24);
+            memcpy(&st, &in[48 * i + 24], 24);
+            ray r;
+            r.o = vec3(p[0], p[1], p[2]);
+            r.dir = vec3(p[3], p[4], p[5]);
+            refgen_trace_calls = 0;
+            refgen_trace_misses = 0;
+            color c;
+            if (integrator == 1)
+                c = det ? ref_det::radianceAlongSingleStep(r, scene, bvh, &st, test.data())
+                        : ref_libm::radianceAlongSingleStep(r, scene, bvh, &st, test.data());      // kernel.cu:549
+            else
+                c = det ? ref_det::radianceAlongSingleStep2(r, scene, bvh, &st, test.data())
+                        : ref_libm::radianceAlongSingleStep2(r, scene, bvh, &st, test.data());
+            const double cv[3] = {c.r, c.g, c.b};
+            const uint32_t flag = (integrator == 1 && (refgen_trace_misses & 4u)) ? 1u : 0u;   // call 2: the camera bounce
+            memcpy(&out[56 * i], cv, 24);
+            memcpy(&out[56 * i + 24], &st, 24);
+            memcpy(&out[56 * i + 48], &flag, 4);
+            memcpy(&out[56 * i + 52], &refgen_trace_misses, 4);
+        }
+        spit(argv[6], out.data(), out.size());
+        return 0;
+    }
+#endif
+#ifdef REFGEN_MEAN
+    if (cmd == "mean") {
+        if (argc < 5) { fprintf(stderr, "refgen mean: too few arguments\n"); return 2; }
+        std::vector<char> in = slurp(argv[2]);
+        const int spp = atoi(argv[4]);
+        if (spp < 1 || in.size() % ((size_t)spp * 24) != 0) { fprintf(stderr, "refgen mean: size mismatch\n"); return 2; }
+        const size_t n = in.size() / ((size_t)spp * 24);
+        const double* p = (const double*)in.data();
+        std::vector<color> imgBuff(n, color(0, 0, 0));                                   // kernel.cu:525
+        for (size_t idx = 0; idx < n; ++idx)
+            for (int curSampleNum = 1; curSampleNum <= spp; ++curSampleNum) {
+                const double* q = p + (idx * (size_t)spp + (size_t)(curSampleNum - 1)) * 3;
+                color result(q[0], q[1], q[2]);
+#include REFGEN_MEAN   // kernel.cu:551-552, verbatim
+            }
+        std::vector<double> out(n * 3);
+        for (size_t idx = 0; idx < n; ++idx) { out[3 * idx] = imgBuff[idx].r; out[3 * idx + 1] = imgBuff[idx].g; out[3 * idx + 2] = imgBuff[idx].b; }
+        spit(argv[3], out.data(), out.size() * 8);
         return 0;
     }
 #endif

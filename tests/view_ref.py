@@ -201,22 +201,9 @@ def morton_xy(idx):
     return x, y
 
 
-_signed = False
-
-
 def _integrators():
-    """The oracle's two integrators with their ctypes signatures (oracle.py sets none for them)."""
-    global _signed
-    h = oracle.lib()
-    if not _signed:
-        h.or_radiance_unidir.argtypes = [C.POINTER(oracle.OScene), oracle.OVec3, oracle.OVec3, C.c_int,
-                                         C.POINTER(oracle.OXorwow), C.POINTER(C.c_double * 3), C.POINTER(oracle.OCounters)]
-        h.or_radiance_unidir.restype = None
-        h.or_radiance_head.argtypes = [C.POINTER(oracle.OScene), oracle.OVec3, oracle.OVec3, C.POINTER(oracle.OXorwow),
-                                       C.POINTER(C.c_double * 3), C.POINTER(oracle.OCounters)]
-        h.or_radiance_head.restype = None
-        _signed = True
-    return h
+    """The oracle library; oracle.py sets the ctypes signatures of its two integrators."""
+    return oracle.lib()
 
 
 def render(osc, cam, view, spp, bounces=3, integrator=0, seed=1234, pixels=None, counts=None, tri_counts=None,

@@ -23,7 +23,14 @@ Outputs (all small, committed):
                                      refgen ppm) over a Morton-indexed imgBuffer_host (64x64 f32 values
                                      incl. 0, huge, inf, NaN): the input buffer and the PPM bytes
 
-`python tools/make_golden.py --only trace|ppm` regenerates only the kat_trace_* / kat_ppm_* files.
+  scenes/models/closed.obj|.mtl      a closed box with a ceiling light (the blob is loaded into it): the scene in
+                                     which no ray of integrator 1 leaves, so none of its samples is undefined
+  integ_*.npz                        the reference's own integrators (kernel.cu:217-515 over the samplers :56-99,
+                                     compiled verbatim: refgen radiance) and running mean (:551-552: refgen mean)
+                                     from given XORWOW states, per sample, in both sin/cos flavours; sets and file
+                                     layout in tests/integrator_ref.py
+
+`python tools/make_golden.py --only trace|ppm|integ` regenerates only the kat_trace_* / kat_ppm_* / integ_* files.
 """
 from __future__ import annotations
 
@@ -320,9 +327,210 @@ def kat_ppm_morton(tmp):
     print("kat_ppm_morton", len(ppm), "bytes")
 
 
+CLOSED_MTL = "newmtl wall\nKd 0.725 0.71 0.68\nnewmtl lamp\nKd 0.78 0.78 0.78\nKe 17 12 4\n"
+
+
+def write_closed():
+    """models/closed.obj|.mtl: a closed box x, z in [-1, 1] x [-1, 3.5], y in [0, 2] (inward normals, the floor first),
+    and a ceiling light quad facing -y.  With the blob loaded into it (integrator_ref.LOADS) and the camera of
+    integrator_ref.CAMERA inside, no ray of integrator 1 can leave the scene."""
+    q = scenes._oriented_quad
+    x0, x1, y0, y1, z0, z1 = -1.0, 1.0, 0.0, 2.0, -1.0, 3.5
+    quads = [("wall", q([(x0, y0, z0), (x0, y0, z1), (x1, y0, z1), (x1, y0, z0)], (0, 1, 0))),      # floor
+             ("wall", q([(x0, y1, z0), (x1, y1, z0), (x1, y1, z1), (x0, y1, z1)], (0, -1, 0))),     # ceiling
+             ("wall", q([(x0, y0, z0), (x1, y0, z0), (x1, y1, z0), (x0, y1, z0)], (0, 0, 1))),      # back
+             ("wall", q([(x0, y0, z1), (x1, y0, z1), (x1, y1, z1), (x0, y1, z1)], (0, 0, -1))),     # front
+             ("wall", q([(x0, y0, z0), (x0, y1, z0), (x0, y1, z1), (x0, y0, z1)], (1, 0, 0))),      # left
+             ("wall", q([(x1, y0, z0), (x1, y0, z1), (x1, y1, z1), (x1, y1, z0)], (-1, 0, 0))),     # right
+             ("lamp", q([(-0.5, 1.98, 0.0), (0.5, 1.98, 0.0), (0.5, 1.98, 1.0), (-0.5, 1.98, 1.0)], (0, -1, 0)))]
+    w = scenes._ObjWriter()
+    w.raw("mtllib closed.mtl")
+    cur = None
+    for mat, quad in quads:
+        if mat != cur:
+            w.raw("usemtl %s" % mat)
+            cur = mat
+        w.faces(np.array([[0, 1, 2, 3]]), w.verts(quad))
+    scenes._write(SCENES, "closed", w.text(), CLOSED_MTL)
+
+
+def integ_fixtures(tmp):
+    """tests/golden/integ_*.npz (layout: tests/integrator_ref.py): the reference's own integrators and running mean
+    on every set of integrator_ref.sets(), both flavours.  Asserts the conditions that keep the d2 flag from hiding a
+    failure, and prints the counts (DESIGN.md 5 quotes them)."""
+    import integrator_ref as ir
+    write_closed()
+    caller, total, total_flagged, wrong_spp = {}, 0, 0, []
+    ref_loads = {k: [("models/" + o, org, sc, fl) for o, org, sc, fl in v] for k, v in ir.LOADS.items()}
+    for name in ir.LOADS:
+        verts = ref_scene(tmp, "integ_" + name, ref_loads[name])["verts"]
+        v = np.stack([verts["x"], verts["y"], verts["z"]], axis=1)
+        caller[name] = ir.caller_rays(v, ir.RAYS_W * ir.RAYS_H, np.random.default_rng(sum(name.encode()) + 417),
+                                      pad=-0.02 if name == "closed" else 0.1, region=ir.RAY_REGION.get(name))
+    for s in ir.sets():
+        w, h, spp = s["w"], s["h"], s["spp"]
+        if s["kind"] == "camera":
+            cam = oracle.camera(ir.CAMERA_POS[s["scene"]], ir.CAMERA["dist_from_film"], ir.CAMERA["focal_length"],
+                                ir.CAMERA["radius"], w, h)
+            rays = oracle.camera_rays(cam, w, h)
+        else:
+            rays = caller[s["scene"]]
+        state0 = oracle.xorwow_states(s["seed"], ir.morton_grid(w, h))
+        out = dict(rays=rays, state0=state0,
+                   meta=np.array([w, h, spp, s["seed"], s["integrator"], s["bounces"], s["kind"] == "rays"], np.int64))
+        flags = {}
+        if s["integrator"] == 1:
+            # 4 spp unless that leaves fewer than a third of the pixels without a flagged sample: then 2 (SPP2)
+            st, bad4 = state0, np.zeros(w * h, bool)
+            for _ in range(4):
+                r = oracle.ref_radiance("det", 1, s["bounces"], rays, st, ref_loads[s["scene"]], SCENES, tmp)
+                st, bad4 = r["state"], bad4 | (r["flag"] != 0)
+            need = 4 if 3 * int((~bad4).sum()) >= w * h else 2
+            if need != spp:
+                wrong_spp.append((s["scene"], s["kind"], w, h, s["seed"], need))
+        for fl in ir.FLAVOURS:
+            st = state0
+            res = []
+            for _ in range(spp):
+                r = oracle.ref_radiance(fl, s["integrator"], s["bounces"], rays, st, ref_loads[s["scene"]], SCENES, tmp)
+                st = r["state"]
+                res.append(r)
+            out["colour_" + fl] = np.stack([r["colour"] for r in res], axis=1)
+            out["end_" + fl] = np.stack([r["state"] for r in res], axis=1)
+            out["mean_" + fl] = oracle.ref_mean(out["colour_" + fl], tmp)
+            flags[fl] = (np.stack([r["flag"] for r in res], axis=1).astype(np.uint8),
+                         np.stack([r["misses"] for r in res], axis=1))
+        # which calls miss depends on the geometry and the directions' hemispheres; the two flavours' directions
+        # differ by an ulp at most, but a flag that differed would make "unflagged" ambiguous: flag the union
+        out["flag"] = flags["libm"][0] | flags["det"][0]
+        out["misses"] = flags["det"][1]
+        n, nf = out["flag"].size, int(out["flag"].sum())
+        clean = int((out["flag"].sum(axis=1) == 0).sum())
+        print("%-46s samples %5d  flagged %5d (%.1f%%)  pixels without a flagged sample %4d of %4d"
+              % (s["name"], n, nf, 100.0 * nf / n, clean, w * h))
+        if s["integrator"] == 0:
+            assert nf == 0, "integrator 0 is never flagged"
+        elif s["scene"] == "closed":
+            assert nf <= 0.01 * n, "closed scene: at most 1% flagged"
+        else:
+            assert n - nf >= 0.4 * n, "open scene: at least 40% unflagged (change the rays, not the cap)"
+            assert need != spp or 3 * clean >= w * h, "open scene: at least a third of the pixels comparable"
+        total += n
+        total_flagged += nf
+        np.savez_compressed(os.path.join(GOLD, s["name"] + ".npz"), **out)
+    assert not wrong_spp, "integrator_ref.SPP2 must name exactly the sets that need 2 spp; (set, spp needed): %r" % wrong_spp
+    print("integ fixtures: %d samples per flavour, %d flagged" % (total, total_flagged))
+
+
+def integ_crafted(tmp):
+    """tests/golden/integ_crafted.npz: samples of integrator 1 in the closed scene, built to reach the guards that no
+    drawn sample reaches (coverage).  The start STATE is an input of refgen radiance, so a draw can be
+    forced: XORWOW's output is v[4] + d, and d is free.
+      A  kernel.cu:340 (G == 0) and :379 (G != G, camera side): the camera ray goes straight down onto the floor
+         next to the left wall; the bounce's first draw is forced to u1 = 1, so the cosine ray is horizontal
+         (castRay.y = sqrt(max(0, 1 - u1)) = 0): dot(norm, dir) = 0 gives G = 0 at :338, and the ray's start is placed
+         0.001 / |dir.x| from the wall, where closestT - 0.001 is too small to move the vertex: x[2] == x[3], seg = 0.
+      B  kernel.cu:391 (G != G, middle link): the camera ray goes straight up into the light at the very point the
+         light path's first vertex was drawn at, from the height at which o.y + (t - 0.001) equals v0.y - 0.001f in
+         float: x[3] == x[0], seg = 0, 0 / 0.
+    Every candidate is checked in float32 here with the oracle's trace (pinned by kat_trace_*) before it is kept; that
+    the reference's text really takes the lines is read off the coverage run, not assumed."""
+    import ctypes as C
+    import integrator_ref as ir
+    F = np.float32
+    loads = [("models/" + o, org, sc, fl) for o, org, sc, fl in ir.LOADS["closed"]]
+    osc = oracle.OracleScene(ref_scene(tmp, "crafted_closed", loads))
+    L = oracle.lib()
+    rng = np.random.default_rng(340379391)
+
+    def draws(words, n):
+        st = oracle._state(words)
+        return [F(L.or_uniform(C.byref(st))) for _ in range(n)]
+
+    def forced(v, k, want):
+        """State {d, v} whose k-th output (1-based) is `want`."""
+        st = oracle._state([0, *v])
+        for _ in range(k):
+            out = L.or_xorwow_next(C.byref(st))
+        return np.array([(want - out) & 0xFFFFFFFF, *v], dtype=np.uint32)
+
+    def pulled(o, d, t):
+        ta = F(np.float64(t) - 0.001)
+        return (o + d * ta).astype(F), ta
+
+    recs = []
+    # ---- A
+    while len(recs) < 2:
+        state = forced(rng.integers(1, 2**32, 5, dtype=np.uint64), 6, 0xFFFFFFFF)
+        u = draws(state, 7)
+        assert u[5] == F(1.0)
+        theta = F(2 * 3.14159 * np.float64(u[6]))
+        s, c = C.c_float(), C.c_float()
+        L.or_sincos(theta, C.byref(s), C.byref(c))
+        x, z = F(F(1.0) * F(c.value)), F(F(1.0) * F(s.value))
+        ln = np.sqrt(F(F(x * x) + F(0.0)) + F(z * z), dtype=F)
+        d2 = np.array([x / ln, 0.0, -z / ln], dtype=F)            # norm (0,1,0): tangent (1,0,0), bitangent (0,0,-1)
+        if d2[0] > -0.5:
+            continue
+        for z0 in (2.5, 2.25, 2.75, 3.0):
+            ox0 = F(-1.0 + 0.001 * abs(float(d2[0])))
+            for k in range(-6, 7):
+                ox = ox0
+                for _ in range(abs(k)):
+                    ox = np.nextafter(ox, F(1.0 if k > 0 else -2.0))
+                o, d = np.array([ox, 0.5, z0], dtype=F), np.array([0.0, -1.0, 0.0], dtype=F)
+                x3, _ = pulled(o, d, oracle.trace(osc, o, d)[1])
+                tri, t2 = oracle.trace(osc, x3, d2)
+                x2, _ = pulled(x3, d2, t2)
+                if tri >= 0 and np.array_equal(x2, x3):
+                    recs.append((np.concatenate([o, d]), state))
+                    break
+            else:
+                continue
+            break
+    # ---- B
+    a = osc.verts.view(F).reshape(-1, 3)
+    tris = osc.tris
+    while len(recs) < 4:
+        state = np.array([rng.integers(0, 2**32), *rng.integers(1, 2**32, 5, dtype=np.uint64)], dtype=np.uint32)
+        u0, u, v = draws(state, 3)
+        ra = F(F(osc.c.total_light_area) * u0)
+        sel = 12 if 0 < ra < 0.5 else 13
+        assert ra != 0.5 and list(osc.lights) == [12, 13]
+        if np.float64(F(u + v)) > 1.0:
+            u, v = F(np.float64(u) + 2 * (0.5 - np.float64(u))), F(np.float64(v) + 2 * (0.5 - np.float64(v)))
+        v0 = a[tris["v0"][sel]]
+        a1, a2 = a[tris["v1"][sel]] - v0, a[tris["v2"][sel]] - v0
+        x0 = (((v0 + a1 * u).astype(F) + (a2 * v).astype(F)).astype(F) + np.array([0.0, -1.0, 0.0], F) * F(0.001)).astype(F)
+        oy = F(1.9)
+        for _ in range(4000):
+            o, d = np.array([x0[0], oy, x0[2]], dtype=F), np.array([0.0, 1.0, 0.0], dtype=F)
+            tri, t = oracle.trace(osc, o, d)
+            if tri == sel and np.array_equal(pulled(o, d, t)[0], x0):
+                recs.append((np.concatenate([o, d]), state))
+                break
+            oy = np.nextafter(oy, F(2.0))
+    rays = np.stack([r for r, _ in recs]).astype(F)
+    states = np.stack([s for _, s in recs]).astype(np.uint32)
+    out = dict(rays=rays, state0=states)
+    for fl in ir.FLAVOURS:
+        r = oracle.ref_radiance(fl, 1, 3, rays, states, loads, SCENES, tmp)
+        assert not r["flag"].any(), "crafted samples must be ones the reference defines"
+        out["colour_" + fl], out["end_" + fl] = r["colour"], r["state"]
+    np.savez_compressed(os.path.join(GOLD, "integ_crafted.npz"), **out)
+    print("integ_crafted", len(rays), "samples: 2 for kernel.cu:340 and :379, 2 for :391")
+
+
 def main():
     if not os.path.exists(REFGEN):
         sys.exit("oracle/_ref/refgen missing: run `make -C oracle` with /root/reference present")
+    if not (oracle.ensure_refgen("radiance") and oracle.ensure_refgen("mean")):
+        sys.exit("oracle/_ref/refgen lacks the radiance / mean commands and there is no reference tree to rebuild it")
+    if sys.argv[1:] == ["--only", "integ"]:
+        with tempfile.TemporaryDirectory() as tmp:
+            integ_fixtures(tmp)
+            integ_crafted(tmp)
+        return
     if sys.argv[1:] == ["--only", "trace"]:
         with tempfile.TemporaryDirectory() as tmp:
             kat_trace(tmp)
@@ -378,6 +586,8 @@ def main():
         kat_helpers(tmp, rng)
         kat_trace(tmp)
         kat_ppm_morton(tmp)
+        integ_fixtures(tmp)
+        integ_crafted(tmp)
     xorwow_fixture()
     render_fixtures()
     print("golden fixtures written to", GOLD)
