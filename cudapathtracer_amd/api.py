@@ -700,6 +700,54 @@ class Renderer:
         return dict(regular=int(rc.regular), irregular=int(rc.irregular), invalid=int(rc.invalid),
                     first_invalid=int(rc.first_invalid))
 
+    def render_irradiance(self, points, normals, width, height, spp, bounces=3, integrator=0, seed=1234, flags=0,
+                          shard_index=0, shard_count=1, pixel_order=0, tile_w=0, tile_h=0, out=None):
+        """An irradiance render (pt_render_irradiance): every sample of pixel (x, y) leaves its point along a fresh
+        cosine-weighted direction about its normal (the bounces' own cosineWeightedRay, its pair drawn first), so the
+        pixel is the cosine-weighted mean of the incoming radiance, E / pi; a Lambertian texel's outgoing radiance is
+        its albedo times that.  points, normals: W*H float32 triples indexed as render_rays' rays
+        (cudapathtracer_amd.rays has grid_points, triangle_points, feature_points).  A point is used as given: lift it
+        off its surface, or the integrator's self-hit rule (a first hit nearer than 0.002 zeroes the path) blackens
+        it.  A non-finite component or a normal whose squared length is outside 1 +- 2^-10 is refused (PtError
+        PT_E_INVALID naming the pixel); one point beyond 64 scene extents sends THE WHOLE RENDER to the slow exact tile
+        kernel (stats["work_units"] == 0).  flags as render_rays; PT_FLAG_NO_PRIMARY_CACHE changes nothing.  Returns
+        (image, stats)."""
+        pts, n = self._rays(points, normals)
+        if n != int(width) * int(height):
+            raise ValueError("render_irradiance: %d points for a %dx%d image" % (n, width, height))
+        p = self.params(width, height, spp, bounces, integrator, seed, flags, shard_index, shard_count,
+                        pixel_order, tile_w, tile_h)
+        shape = (height * width, 3) if pixel_order == L.PT_ORDER_MORTON else (height, width, 3)
+        if out is None:
+            out = np.zeros(shape, dtype=np.float32)
+        elif out.dtype != np.float32 or out.size != width * height * 3 or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous float32 array of W*H*3 values")
+        st = L.Stats()
+        L.check(L.lib().pt_render_irradiance(self._h, C.byref(p), pts.ctypes.data, out.ctypes.data, C.byref(st)))
+        return out, st.as_dict()
+
+    def render_irradiance_device(self, d_points_ptr, d_out_ptr, width, height, spp, bounces=3, integrator=0, seed=1234,
+                                 flags=0, shard_index=0, shard_count=1, pixel_order=0, tile_w=0, tile_h=0, stream_ptr=None):
+        """pt_render_irradiance_device on raw device pointers: W*H points {p.xyz, n.xyz} (float32[6*W*H], 8-byte
+        aligned) into this shard's pixels of a caller-owned float32[W*H*3] buffer; blocking; returns the stats.
+        Everything else as render_irradiance()."""
+        p = self.params(width, height, spp, bounces, integrator, seed, flags, shard_index, shard_count,
+                        pixel_order, tile_w, tile_h)
+        st = L.Stats()
+        L.check(L.lib().pt_render_irradiance_device(self._h, C.byref(p), C.c_void_p(int(d_points_ptr)),
+                                                    C.c_void_p(int(d_out_ptr)),
+                                                    None if stream_ptr is None else C.c_void_p(int(stream_ptr)), C.byref(st)))
+        return st.as_dict()
+
+    def classify_points_device(self, d_points_ptr, n, stream_ptr=None):
+        """The classes of n points on the device (pt_points_classify_device), as render_irradiance* sorts them: the
+        dict of classify_rays_device."""
+        rc = L.RayClasses()
+        L.check(L.lib().pt_points_classify_device(self._h, int(n), None if not d_points_ptr else C.c_void_p(int(d_points_ptr)),
+                                                  None if stream_ptr is None else C.c_void_p(int(stream_ptr)), C.byref(rc)))
+        return dict(regular=int(rc.regular), irregular=int(rc.irregular), invalid=int(rc.invalid),
+                    first_invalid=int(rc.first_invalid))
+
 
 def accum_file_info(path):
     """Header of a checkpoint file (pt_accum_file_info, host-only): dict of params (spp = 0), camera,

@@ -83,6 +83,10 @@
 //                                         jitter, checkpoint, session, temporal, pass, adaptive or --denoise-guided options,
 //                                         --tri-counts or --gpus above 1: an error.  A ray far outside the scene or with an
 //                                         unnormalised direction sends the whole render to the slow exact walk (pt.h)
+// --irradiance FILE                       an irradiance render at the caller's points (pt_render_irradiance): FILE has
+//                                         --rays' format with the second triple a unit normal, {p.xyz, n.xyz}; every sample
+//                                         leaves p along a fresh cosine-weighted direction about n.  --rays' exclusions, and
+//                                         not with --rays, --denoise or --aov (there are no features over points): an error
 // --aov PREFIX                            write the primary-hit feature buffers as PREFIX_albedo.pfm,
 //                                         PREFIX_normal.pfm, PREFIX_position.pfm and PREFIX_depth.pfm (depth
 //                                         replicated to 3 channels)
@@ -118,7 +122,7 @@ struct Obj {
             "              [--checkpoint FILE] [--resume FILE] [--pass-spp K]\n"
             "              [--session FILE] [--resume-session FILE]\n"
             "              [--denoise [ITERS]] [--aov PREFIX]\n"
-            "              [--camera-path FILE --temporal [--temporal-max N]] [--rays FILE]\n"
+            "              [--camera-path FILE --temporal [--temporal-max N]] [--rays FILE | --irradiance FILE]\n"
             "              [--until-error TOL [--error-quantile Q] [--min-batches B] [--adaptive]] [--error-map FILE.pfm]\n"
             "              [--count-map FILE.pfm] [--denoise-guided [ITERS] [--sigma-luma S]] [--variance-map FILE.pfm]\n"
             "  --until-error TOL  with --pass-spp: stop once the fraction Q (default 0.95) of the pixels has a relative\n"
@@ -143,6 +147,9 @@ struct Obj {
             "  --rays FILE        render along the rays of FILE (raw float32, 6*W*H values {o.xyz, d.xyz}, scanline order) instead\n"
             "                     of a camera's; --denoise and --aov take their features from FILE; not with the camera, view,\n"
             "                     jitter, accumulating, temporal or --denoise-guided options\n"
+            "  --irradiance FILE  an irradiance render at the points of FILE (--rays' format, {p.xyz, n.xyz} with n a unit normal):\n"
+            "                     every sample leaves p along a cosine-weighted direction about n; --rays' exclusions, and not with\n"
+            "                     --rays, --denoise or --aov\n"
             "  --aov PREFIX       write PREFIX_albedo.pfm, PREFIX_normal.pfm, PREFIX_position.pfm, PREFIX_depth.pfm\n");
     exit(2);
 }
@@ -237,6 +244,7 @@ int main(int argc, char** argv)
     std::string variance_map;
     std::string aov;
     std::string rays_path;     // --rays FILE
+    std::string irr_path;      // --irradiance FILE
     std::string camera_path;   // --camera-path FILE --temporal [--temporal-max N]
     bool temporal = false;
     pt_temporal_params tparams;
@@ -304,6 +312,7 @@ int main(int argc, char** argv)
         else if (a == "--variance-map") variance_map = next();
         else if (a == "--aov") aov = next();
         else if (a == "--rays") rays_path = next();
+        else if (a == "--irradiance") irr_path = next();
         else if (a == "--camera-path") camera_path = next();
         else if (a == "--temporal") temporal = true;
         else if (a == "--temporal-max") { tparams.max_history = atoi(next().c_str()); if (tparams.max_history < 1) usage("--temporal-max must be >= 1"); }
@@ -338,7 +347,16 @@ int main(int argc, char** argv)
     }
     if (objs.empty()) usage("at least one --obj is required");
     if (gpus < 1) usage("--gpus must be >= 1");
-    std::vector<float> rays;   // --rays: the buffer in the render's pixel order
+    std::vector<float> rays;   // --rays / --irradiance: the buffer in the render's pixel order
+    const bool irradiance = !irr_path.empty();
+    if (irradiance && !rays_path.empty()) usage("--irradiance cannot be combined with --rays");
+    if (irradiance) {   // (no features over a point buffer, pt.h)
+        for (const std::string& g : given)
+            for (const char* o : {"--denoise", "--aov"})
+                if (g == o) usage(("--irradiance cannot be combined with " + g).c_str());
+        rays_path = irr_path;
+    }
+    const std::string rays_opt = irradiance ? "--irradiance" : "--rays";
     if (!rays_path.empty()) {
         // a render along rays takes no camera, and its passes are not driven from here: every option of those is an error.
         // (--denoise and --aov work: the features then come from the ray file, pt_render_features_rays)
@@ -348,19 +366,19 @@ int main(int argc, char** argv)
                                   "--temporal", "--temporal-max", "--until-error", "--error-quantile", "--min-batches", "--error-map",
                                   "--adaptive", "--count-map", "--denoise-guided", "--sigma-luma", "--variance-map",
                                   "--tri-counts"})
-                if (g == o) usage(("--rays cannot be combined with " + g).c_str());
-        if (gpus != 1) usage("--rays needs --gpus 1");
-        if (p.width <= 0 || p.height <= 0 || p.width > 65535 || p.height > 65535) usage("--rays: bad --width / --height");
+                if (g == o) usage((rays_opt + " cannot be combined with " + g).c_str());
+        if (gpus != 1) usage((rays_opt + " needs --gpus 1").c_str());
+        if (p.width <= 0 || p.height <= 0 || p.width > 65535 || p.height > 65535) usage((rays_opt + ": bad --width / --height").c_str());
         const size_t npx = (size_t)p.width * p.height;
         FILE* f = fopen(rays_path.c_str(), "rb");
-        if (!f) { fprintf(stderr, "pt_cli: --rays: cannot read %s\n", rays_path.c_str()); return 2; }
+        if (!f) { fprintf(stderr, "pt_cli: %s: cannot read %s\n", rays_opt.c_str(), rays_path.c_str()); return 2; }
         std::vector<float> scan(npx * 6);
         const size_t got = fread(scan.data(), sizeof(float), scan.size(), f);
         const bool more = got == scan.size() && fgetc(f) != EOF;
         fclose(f);
         if (got != scan.size() || more) {
-            fprintf(stderr, "pt_cli: --rays: %s does not hold %zu float32 values (6 per pixel of %dx%d)\n", rays_path.c_str(), scan.size(),
-                    p.width, p.height);
+            fprintf(stderr, "pt_cli: %s: %s does not hold %zu float32 values (6 per pixel of %dx%d)\n", rays_opt.c_str(),
+                    rays_path.c_str(), scan.size(), p.width, p.height);
             return 2;
         }
         if (p.pixel_order == PT_ORDER_MORTON) {
@@ -680,6 +698,8 @@ int main(int argc, char** argv)
                 }
             if (pt_write_pfm(variance_map.c_str(), grey.data(), p.width, p.height) != PT_OK) return die("--variance-map");
         }
+    } else if (!rays.empty() && irradiance) {
+        if (pt_render_irradiance(ctx[0], &p, rays.data(), img.data(), &st) != PT_OK) return die("pt_render_irradiance");
     } else if (!rays.empty()) {
         if (pt_render_rays(ctx[0], &p, rays.data(), img.data(), &st) != PT_OK) return die("pt_render_rays");
     } else {

@@ -733,8 +733,10 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
 // kJit: a jittered render, render_tiles_jitter -- every sample draws its film point first and forms its own ray,
 // through the view or not (a.oriented), and the primary memo is off;
 // kRays: a render along the caller's rays, render_tiles_rays -- the pixel's ray is read from RayArgs::rays, no sample
-// draws a lens pair, Morton index 0 included, and the ray is the same for every sample, so the memo works)
-template <int kIntegrator, bool kRefWalk, bool kCount, bool kView, bool kJit = false, bool kRays = false>
+// draws a lens pair, Morton index 0 included, and the ray is the same for every sample, so the memo works;
+// kPts: an irradiance render, render_tiles_points -- RayArgs::rays holds the pixel's point {p, n}; every sample draws a
+// pair and leaves p along cosine_ray(n), the bounces' own function, so there is no memo)
+template <int kIntegrator, bool kRefWalk, bool kCount, bool kView, bool kJit = false, bool kRays = false, bool kPts = false>
 __device__ __forceinline__ void render_tiles_body(Args& a)
 {
     extern __shared__ uint32_t lds_stack[];
@@ -748,7 +750,7 @@ __device__ __forceinline__ void render_tiles_body(Args& a)
     tr.reference = 0;
     unsigned long long samples = 0;
     const bool skip_dead = !(a.flags & PT_FLAG_NO_DEAD_PATH_SKIP);
-    const bool memo = !kJit && !(a.flags & PT_FLAG_NO_PRIMARY_CACHE);
+    const bool memo = !kJit && !kPts && !(a.flags & PT_FLAG_NO_PRIMARY_CACHE);
     for (;;) {
         uint32_t k = 0;   // the next 8x8 block of this shard's tiles (64 work slots)
         if (lane == 0) k = atomicAdd(a.tile_counter, 1u);
@@ -759,7 +761,7 @@ __device__ __forceinline__ void render_tiles_body(Args& a)
         const uint32_t idx = morton2(px, py);
         Rng rng;
         rng_init(rng, a.seed, idx, a.jump);
-        const bool lens = !kRays && ((idx == 0) || (a.cam.radius != 0.0f));
+        const bool lens = !kRays && !kPts && ((idx == 0) || (a.cam.radius != 0.0f));
         tr.have = false;
         double m0 = 0.0, m1 = 0.0, m2 = 0.0;
         for (int n = 1; n <= a.spp; ++n) {
@@ -770,7 +772,8 @@ __device__ __forceinline__ void render_tiles_body(Args& a)
             }
             if (lens) { u1 = rng_uniform(rng); u2 = rng_uniform(rng); }
             V3 o, d;
-            if (kRays) { o = ray_origin(a, px, py); d = ray_direction(a, px, py); }
+            if (kPts) { o = ray_origin(a, px, py); d = cosine_ray(ray_direction(a, px, py), rng); }   // (the sample's pair is drawn here)
+            else if (kRays) { o = ray_origin(a, px, py); d = ray_direction(a, px, py); }
             else if (kJit) camera_ray_jitter<false>(a, px, py, jx, jy, lens, u1, u2, &o, &d);
             else if (kView) camera_ray_view<false>(a, px, py, lens, u1, u2, &o, &d);
             else camera_ray<false>(a.cam, px, py, lens, u1, u2, &o, &d);
@@ -1005,8 +1008,10 @@ __device__ __forceinline__ void reset_render_counters(const Args& a)
 // every unit is marked as a lens unit is -- the ray is formed per sample: no UW_CD direction, no CF_CAMC, no memo --
 // and the replay skips two more draws per sample.
 // kRays: the set-up of a render along the caller's rays, init_pixel_states_rays.  Every unit is a pinhole unit whose
-// direction is the pixel's in RayArgs::rays -- Morton index 0 too: no sample draws a lens pair -- so the memos work.)
-template <bool kJit, bool kRays = false>
+// direction is the pixel's in RayArgs::rays -- Morton index 0 too: no sample draws a lens pair -- so the memos work.
+// kPts: the set-up of an irradiance render, init_pixel_states_points.  Every sample draws a pair and forms its own
+// ray, so every unit is marked and replayed as a lens unit is: no UW_CD direction, no CF_CAMC, no memo.)
+template <bool kJit, bool kRays = false, bool kPts = false>
 __device__ __forceinline__ void init_pixel_states_body(const Args& a, uint32_t* __restrict__ st)
 {
     // one lane per pixel slot: curand_init, then one pass over the samples that writes the state
@@ -1042,7 +1047,7 @@ __device__ __forceinline__ void init_pixel_states_body(const Args& a, uint32_t* 
     Rng r;
     const uint32_t n_done = a.accum ? a.acc_n0 : 0u;   // samples the pixel has before this render
     slot_stream(a, q, idx, n_done, r);
-    const bool lens = !kRays && ((idx == 0) || (a.cam.radius != 0.0f));
+    const bool lens = kPts || (!kRays && ((idx == 0) || (a.cam.radius != 0.0f)));
     const bool per_sample = kJit || lens;   // the unit's mark: its rays are formed per sample
     const V3 d = kRays ? ray_direction(a, px, py) : pinhole_dir(a, px, py, per_sample);
     uint32_t done = 0;
@@ -1406,7 +1411,10 @@ __device__ __forceinline__ void finish_pixel(const Args& a, uint32_t slot, uint3
 // first, then the lens pair if its pixel is a lens pixel (lens_pixel), and takes the view under a.oriented.
 // kRays: a render along the caller's rays (RayArgs::rays; instances of their own again).  Every unit arrives as a
 // pinhole unit with its direction present (CF_CAMC); a sample's origin is read from the buffer by the pixel's index.
-template <bool kCount, bool kAccum, bool kView = false, bool kJit = false, bool kRays = false>
+// kPts: an irradiance render (RayArgs::rays holds points {p, n}; instances of their own once more).  Every unit arrives
+// as a lens unit; a sample reads its pixel's 24 bytes and leaves p along cosine_ray(n), whose two draws are the
+// sample's first.  The memo paths are compiled out.
+template <bool kCount, bool kAccum, bool kView = false, bool kJit = false, bool kRays = false, bool kPts = false>
 __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, int lane, uint32_t& state, V3& ro, V3& rd,
                                            int32_t& htri, float& ht, W4& w, const Stack4& S,
                                            unsigned long long* lcnt, const uint32_t* lprobe, uint32_t* done_rel,
@@ -1463,9 +1471,9 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
         fl |= CF_ACC0;   // acc = 0 (stored on the sample's first emission)
         wgt = c3(1, 1, 1);
         float u1 = 0.0f, u2 = 0.0f;
-        const bool lens = !kRays && (fl & CF_LENS) != 0u;
+        const bool lens = kPts || (!kRays && (fl & CF_LENS) != 0u);
         float jx = 0.0f, jy = 0.0f;
-        bool pair = lens;   // the sample draws a lens pair
+        bool pair = !kPts && lens;   // the sample draws a lens pair (kPts: cosine_ray draws the sample's pair itself)
         if (kJit) {
             const float ua = rng_uniform(rng), ub = rng_uniform(rng);
             jitter_offset(fresh(a.flags), ua, ub, &jx, &jy);
@@ -1475,7 +1483,8 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
         SEC(SEC_START);
         if (!kRays && (lens || !(fl & CF_CAMC))) {
             SEC(SEC_CAMERA);
-            if (kJit) camera_ray_jitter(a, px, py, jx, jy, pair, u1, u2, &ro, &rd);
+            if (kPts) { ro = ray_origin(a, px, py); rd = cosine_ray(ray_direction(a, px, py), rng); }
+            else if (kJit) camera_ray_jitter(a, px, py, jx, jy, pair, u1, u2, &ro, &rd);
             else if (kView) camera_ray_view(a, px, py, lens, u1, u2, &ro, &rd);
             else camera_ray(a.cam, px, py, lens, u1, u2, &ro, &rd);
             if (!lens) {   // a pinhole ray is the same for every sample of the pixel
@@ -1489,14 +1498,14 @@ __device__ __forceinline__ void shade_lane(const Args& a_in, const ColdRec& R, i
             rd = v3(__uint_as_float(cd.x), __uint_as_float(cd.y), __uint_as_float(cd.z));
         }
         wave_count(lcnt + 1, lane);
-        if (fl & CF_HAVE) {
+        if (!kPts && (fl & CF_HAVE)) {
             SEC(SEC_MEMO);
             const uint2 mm = have_cells ? make_uint2(c7.z, c7.w) : R.ld2(CW_MTRI);
             htri = (int32_t)mm.x; ht = __uint_as_float(mm.y);
             fl = (fl & ~CF_PRIMARY) | CF_MEMO; state = ST_SHADE;
             return true;
         }
-        if (fl & CF_SHARE) {
+        if (!kPts && (fl & CF_SHARE)) {
             // the pixel's chunk 0 may have published the (sample-invariant) primary hit
             const uint32_t q = have_cells ? c8.w : R.ld(CW_Q);
             // hit and flag in one word: a relaxed agent-scope load (coherent across the XCDs' L2s
@@ -1950,7 +1959,10 @@ __device__ __forceinline__ float head_vis_occluded(float len)
 // (kRays: a render along the caller's rays, instances of their own too.  A unit is a pinhole unit whose camera vertex
 // is the ray's origin: written to HW_CO once, when the unit is taken, beside the direction in HW_CD, and read from
 // there by every sample's camera stage -- so the memo path is the pinhole unit's.)
-template <bool kCount, bool kAccum, bool kJit = false, bool kRays = false>
+// (kPts: an irradiance render, instances of their own as well.  A unit is a lens unit; a sample's first two draws are
+// cosine_ray's over the pixel's normal, and the ray goes to HW_CO / HW_CD at once, where the camera stage reads a
+// lens sample's ray.  The memo paths are compiled out.)
+template <bool kCount, bool kAccum, bool kJit = false, bool kRays = false, bool kPts = false>
 __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint32_t& state, V3& ro, V3& rd,
                                                 int32_t& htri, float& ht, W4& w, const Stack4& S,
                                                 unsigned long long* lcnt, const uint32_t* lprobe, uint32_t* done_rel,
@@ -1997,10 +2009,16 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
             rng.v0 = k1.x; rng.v1 = k1.y; rng.v2 = k1.z; rng.v3 = k1.w;
             rng.v4 = R.ld(HW_RNG_V4);
         }
-        const bool lens = !kRays && (fl & CF_LENS) != 0u;
+        const bool lens = kPts || (!kRays && (fl & CF_LENS) != 0u);
         float lu1 = 0.0f, lu2 = 0.0f;
         float jx = 0.0f, jy = 0.0f;
-        bool pair = lens;   // the sample draws a lens pair
+        bool pair = !kPts && lens;   // the sample draws a lens pair
+        if (kPts) {   // this sample's ray: the pair (cosine_ray draws it) comes before every other draw
+            const V3 co = ray_origin(a, px, py);
+            const V3 cd = cosine_ray(ray_direction(a, px, py), rng);
+            R.st4(HW_CD, __float_as_uint(cd.x), __float_as_uint(cd.y), __float_as_uint(cd.z), 0u);
+            R.st4(HW_CO, __float_as_uint(co.x), __float_as_uint(co.y), __float_as_uint(co.z), 0u);
+        }
         if (kJit) {   // the sample's film point: its first two draws (every unit of a jittered render has CF_LENS)
             const float ua = rng_uniform(rng), ub = rng_uniform(rng);
             jitter_offset(fresh(a.flags), ua, ub, &jx, &jy);
@@ -2044,7 +2062,7 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
         R.st4(HW_RNG_V0, rng.v0, rng.v1, rng.v2, rng.v3);
         R.st4(HW_X0, __float_as_uint(ro.x), __float_as_uint(ro.y), __float_as_uint(ro.z), (uint32_t)m0);
         R.st4(HW_N0, __float_as_uint(n0.x), __float_as_uint(n0.y), __float_as_uint(n0.z), 0u);
-        if (lens) {   // this sample's camera ray (its draws came first)
+        if (!kPts && lens) {   // this sample's camera ray (its draws came first)
             V3 co, cd;
             if (kJit) camera_ray_jitter(a, px, py, jx, jy, pair, lu1, lu2, &co, &cd);
             else if (a.oriented) camera_ray_view(a, px, py, true, lu1, lu2, &co, &cd);
@@ -2062,21 +2080,21 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
         wave_count(lcnt + 1, lane);
         const uint4 cd = R.ld4(HW_CD);
         rd = v3(__uint_as_float(cd.x), __uint_as_float(cd.y), __uint_as_float(cd.z));
-        const bool lens = !kRays && (fl & CF_LENS) != 0u;
+        const bool lens = kPts || (!kRays && (fl & CF_LENS) != 0u);
         if (kRays || lens) {
             const uint4 co = R.ld4(HW_CO);
             ro = v3(__uint_as_float(co.x), __uint_as_float(co.y), __uint_as_float(co.z));
         } else {
             ro = v3(0.0f, 0.0f, 0.0f) + v3(fresh(a.cam.pos[0]), fresh(a.cam.pos[1]), fresh(a.cam.pos[2]));
         }
-        if (fl & CF_HAVE) {
+        if (!kPts && (fl & CF_HAVE)) {
             SEC(SEC_MEMO);
             const uint2 mm = R.ld2(HW_MTRI);
             htri = (int32_t)mm.x; ht = __uint_as_float(mm.y);
             fl = (fl & ~CF_PRIMARY) | CF_MEMO; state = ST_SHADE;
             return true;
         }
-        if (fl & CF_SHARE) {
+        if (!kPts && (fl & CF_SHARE)) {
             const uint32_t q = R.ld(HW_Q);
             const uint64_t mv = __hip_atomic_load(reinterpret_cast<uint64_t*>(a.pmemo) + q, __ATOMIC_RELAXED,
                                                   __HIP_MEMORY_SCOPE_AGENT);
@@ -2341,7 +2359,7 @@ __device__ __forceinline__ void shade_lane_head(const ColdRec& R, int lane, uint
 // kLdsWalk: walk steps read the staged top from LDS (integrator 1 always; integrator 0 when the LDS
 // top holds the whole tree) instead of issuing every node's loads to memory.
 template <bool kCount, bool kHead, bool kLdsWalk = kHead, bool kAccum = false, bool kView = false, bool kJit = false,
-          bool kRays = false>
+          bool kRays = false, bool kPts = false>
 __device__ __forceinline__ void wf_main(const Args& a)
 {
     extern __shared__ uint32_t lds_wf[];
@@ -2482,8 +2500,8 @@ __device__ __forceinline__ void wf_main(const Args& a)
         if (kCount) ++shade_slots;
         // (the lane id is recomputed for the shading pass: one VGPR less live across the walk loop)
         if (state != ST_TRACE && state != ST_DONE) {
-            if (kHead) shade_lane_head<kCount, kAccum, kJit, kRays>(R, (int)__lane_id(), state, ro, rd, htri, ht, w, S, lcnt, lprobe, done_rel, cnt);
-            else shade_lane<kCount, kAccum, kView, kJit, kRays>(a, R, (int)__lane_id(), state, ro, rd, htri, ht, w, S, lcnt, lprobe, done_rel, cnt);
+            if (kHead) shade_lane_head<kCount, kAccum, kJit, kRays, kPts>(R, (int)__lane_id(), state, ro, rd, htri, ht, w, S, lcnt, lprobe, done_rel, cnt);
+            else shade_lane<kCount, kAccum, kView, kJit, kRays, kPts>(a, R, (int)__lane_id(), state, ro, rd, htri, ht, w, S, lcnt, lprobe, done_rel, cnt);
         }
         if (kCount) shade_clk += clock64() - clk0;
         if (__ballot(state != ST_DONE) == 0ull) break;
@@ -2975,6 +2993,30 @@ __global__ __launch_bounds__(256) void init_active_states_rays(RayArgs a, uint32
 __global__ __launch_bounds__(256) void primary_features_rays(RayArgs a, float4* __restrict__ out)
 {
     primary_features_body<false, false, true>(a, out);
+}
+
+// ------------------------------------------------------------------ irradiance renders at caller-supplied points
+// pt_render_irradiance*: the kernels of a render whose every sample leaves its pixel's point along a cosine-weighted
+// direction about the point's normal (kPts; RayArgs::rays names the point buffer) -- the set-up kernel, the two
+// integrators' wavefront kernels at the default occupancy and the tile kernel -- defined and first used after every
+// other kernel once more, which therefore compile as they did.
+__global__ __launch_bounds__(256) void init_pixel_states_points(RayArgs a, uint32_t* __restrict__ st)
+{
+    init_pixel_states_body<false, false, true>(a, st);
+}
+template <bool kLdsWalk>
+__global__ __launch_bounds__(256, 5) void render_unidir_points_wf(RayArgs a)
+{
+    wf_main<false, false, kLdsWalk, false, false, false, false, true>(a);
+}
+__global__ __launch_bounds__(256, 5) void render_head_points_wf(RayArgs a)
+{
+    wf_main<false, true, true, false, false, false, false, true>(a);
+}
+template <int kIntegrator, bool kRefWalk, bool kCount>
+__global__ __launch_bounds__(64) void render_tiles_points(RayArgs a)
+{
+    render_tiles_body<kIntegrator, kRefWalk, kCount, false, false, false, true>(a);
 }
 
 }  // namespace

@@ -459,9 +459,10 @@ struct LaneTiming {
 // (b.oriented) of integrator 0 takes that instance's view twin; integrator 1's instances serve both.  A jittered
 // render (PT_FLAG_JITTER) takes the instance's jitter twin, which serves both cameras.
 // A render along a caller's rays (rays != null) takes the ray-source instance, whose argument block is b with the
-// buffer appended (RayArgs).
+// buffer appended (RayArgs); points: the buffer holds points {p, n} and the render is an irradiance render, which
+// takes the point-source instance.
 static int launch_wavefront(const pt::WavefrontVariant& v, const WavefrontLaunch& L, hipStream_t stream, const Args& b,
-                            const float* rays = nullptr)
+                            const float* rays = nullptr, bool points = false)
 {
     constexpr auto code = [](bool head, bool count, int min_waves, bool lds_walk, bool accum) {
         return pt::WavefrontVariant{head, count, min_waves, lds_walk, accum}.code();
@@ -521,7 +522,7 @@ static int launch_wavefront(const pt::WavefrontVariant& v, const WavefrontLaunch
                             v.head, v.count, v.min_waves, v.lds_walk, v.accum);
         }
     }
-    if (rays) {   // (the ray-source instances, default occupancy only: below every other instance again)
+    if (rays && !points) {   // (the ray-source instances, default occupancy only: below every other instance again)
         void (*rkernel)(RayArgs) = nullptr;
         switch (v.code()) {
         case code(true, false, 5, false, false): rkernel = render_head_rays_wf; break;
@@ -542,6 +543,24 @@ static int launch_wavefront(const pt::WavefrontVariant& v, const WavefrontLaunch
         HIP_TRY(hipGetLastError());
         return PT_OK;
     }
+    if (rays) {   // (the point-source instances of an irradiance render: default occupancy only, no accumulating twins)
+        void (*pkernel)(RayArgs) = nullptr;
+        switch (v.code()) {
+        case code(true, false, 5, false, false): pkernel = render_head_points_wf; break;
+        case code(false, false, 5, true, false): pkernel = render_unidir_points_wf<true>; break;
+        case code(false, false, 5, false, false): pkernel = render_unidir_points_wf<false>; break;
+        default:
+            return pt::fail(PT_E_INVALID, "pt_render_irradiance: no point-source wavefront kernel instance for head %d count %d waves "
+                            "%d lds %d accum %d (only the default PT_WF_MIN_WAVES / PT_HEAD_MIN_WAVES have one)",
+                            v.head, v.count, v.min_waves, v.lds_walk, v.accum);
+        }
+        RayArgs rb;
+        static_cast<Args&>(rb) = b;
+        rb.rays = rays;
+        hipLaunchKernelGGL(pkernel, dim3(L.blocks), dim3(256), L.lds, stream, rb);
+        HIP_TRY(hipGetLastError());
+        return PT_OK;
+    }
     hipLaunchKernelGGL(kernel, dim3(L.blocks), dim3(256), L.lds, stream, b);
     HIP_TRY(hipGetLastError());
     return PT_OK;
@@ -549,9 +568,9 @@ static int launch_wavefront(const pt::WavefrontVariant& v, const WavefrontLaunch
 
 // The tile kernel of a render the wavefront kernels do not take: one wave per 8x8 block of the shard's tiles.
 // (rays: a render along a caller's rays; rays_refwalk: it takes the reference's own walk -- an irregular buffer or
-// one of the two reference flags)
+// one of the two reference flags; points: the buffer holds the points of an irradiance render)
 static int launch_tiles(const pt_ctx* c, const pt_params* p, pt_ctx::Bufs& B, size_t lds, hipStream_t stream, Args& a,
-                        const float* rays, bool rays_refwalk)
+                        const float* rays, bool rays_refwalk, bool points)
 {
     uint32_t grid = (uint32_t)c->num_cus * 16;   // waves per CU
     if (grid > a.ntiles_shard * a.tile_blocks) grid = a.ntiles_shard > 0 ? a.ntiles_shard * a.tile_blocks : 1;
@@ -566,6 +585,7 @@ static int launch_tiles(const pt_ctx* c, const pt_params* p, pt_ctx::Bufs& B, si
 #define PT_LAUNCH_VIEW(I, R, C) hipLaunchKernelGGL((render_tiles_view<I, R, C>), dim3(grid), dim3(64), lds, stream, a)
 #define PT_LAUNCH_JITTER(I, R, C) hipLaunchKernelGGL((render_tiles_jitter<I, R, C>), dim3(grid), dim3(64), lds, stream, a)
 #define PT_LAUNCH_RAYS(I, R) hipLaunchKernelGGL((render_tiles_rays<I, R, false>), dim3(grid), dim3(64), lds, stream, ra)
+#define PT_LAUNCH_POINTS(I, R) hipLaunchKernelGGL((render_tiles_points<I, R, false>), dim3(grid), dim3(64), lds, stream, ra)
     const bool jitter = (p->flags & PT_FLAG_JITTER) != 0;
     if (rays) {
         // (the ray-source instances: run only here, and first used below every other instance)
@@ -590,13 +610,20 @@ static int launch_tiles(const pt_ctx* c, const pt_params* p, pt_ctx::Bufs& B, si
         if (refwalk) { if (count) PT_LAUNCH_JITTER(0, true, true); else PT_LAUNCH_JITTER(0, true, false); }
         else { if (count) PT_LAUNCH_JITTER(0, false, true); else PT_LAUNCH_JITTER(0, false, false); }
     }
-    if (rays) {
+    if (rays && !points) {
         RayArgs ra;
         static_cast<Args&>(ra) = a;
         ra.rays = rays;
         if (p->integrator == PT_INTEGRATOR_HEAD) { if (rays_refwalk) PT_LAUNCH_RAYS(1, true); else PT_LAUNCH_RAYS(1, false); }
         else { if (rays_refwalk) PT_LAUNCH_RAYS(0, true); else PT_LAUNCH_RAYS(0, false); }
+    } else if (rays) {   // (the point-source instances: below the ray-source ones)
+        RayArgs ra;
+        static_cast<Args&>(ra) = a;
+        ra.rays = rays;
+        if (p->integrator == PT_INTEGRATOR_HEAD) { if (rays_refwalk) PT_LAUNCH_POINTS(1, true); else PT_LAUNCH_POINTS(1, false); }
+        else { if (rays_refwalk) PT_LAUNCH_POINTS(0, true); else PT_LAUNCH_POINTS(0, false); }
     }
+#undef PT_LAUNCH_POINTS
 #undef PT_LAUNCH_RAYS
 #undef PT_LAUNCH_JITTER
 #undef PT_LAUNCH_VIEW
@@ -612,9 +639,9 @@ struct WavefrontDone {
 };
 
 // The wavefront path of one render, from its plan to finalize_pixels.  a: the render's Args; F: its flight slot.
-// (rays: a render along a caller's rays, or null)
+// (rays: a render along a caller's rays, or null; points: the buffer holds the points of an irradiance render)
 static int enqueue_wavefront(pt_ctx* c, const pt_params* p, const pt::AccumPass* acc, const Args& a, pt_ctx::Flight& F,
-                             pt_ctx::Bufs& B, hipStream_t stream, WavefrontDone* done, const float* rays)
+                             pt_ctx::Bufs& B, hipStream_t stream, WavefrontDone* done, const float* rays, bool points)
 {
     const pt::RenderKnobs& K = c->knobs;
     Args b = a;
@@ -644,7 +671,8 @@ static int enqueue_wavefront(pt_ctx* c, const pt_params* p, const pt::AccumPass*
         RayArgs rb;
         static_cast<Args&>(rb) = b;
         rb.rays = rays;
-        hipLaunchKernelGGL(init_pixel_states_rays, dim3((b.npix + 255) / 256), dim3(256), 0, stream, rb, B.pix_states);
+        if (points) hipLaunchKernelGGL(init_pixel_states_points, dim3((b.npix + 255) / 256), dim3(256), 0, stream, rb, B.pix_states);
+        else hipLaunchKernelGGL(init_pixel_states_rays, dim3((b.npix + 255) / 256), dim3(256), 0, stream, rb, B.pix_states);
     }
     // A render queued on another stream while one is in flight: its seeding pre-pass runs beside the
     // earlier render's last waves (its own buffers), but the integration kernel waits until the earlier
@@ -656,7 +684,7 @@ static int enqueue_wavefront(pt_ctx* c, const pt_params* p, const pt::AccumPass*
     done->split = b.ntail;
     const pt::WavefrontVariant v = pt::wavefront_variant(b.head != 0, (p->flags & PT_FLAG_COUNT) != 0, acc != nullptr, L.lds_tree,
                                                          K.wf_min_waves, K.head_min_waves);
-    if (int rc = launch_wavefront(v, L, stream, b, rays)) return rc;
+    if (int rc = launch_wavefront(v, L, stream, b, rays, points)) return rc;
     HIP_TRY(hipEventRecord(F.ek1, stream));
     if (b.ntail > 0) hipLaunchKernelGGL(finalize_pixels, dim3((b.ntail + 255) / 256), dim3(256), 0, stream, b);
     HIP_TRY(hipGetLastError());
@@ -670,9 +698,10 @@ static int enqueue_wavefront(pt_ctx* c, const pt_params* p, const pt::AccumPass*
 // d_rays: a render along the caller's rays (pt_render_rays_device, which has classified them, or a pass of a ray
 // accumulator, whose rays were classified when it was created; cam is then a stand-in that only carries the image
 // size); rays_irregular: the buffer holds an irregular ray, so the whole render
-// takes the tile kernel with the reference's own walk.
+// takes the tile kernel with the reference's own walk.  points: d_rays holds the points {p, n} of an irradiance render
+// (pt_render_irradiance_device), classified likewise; never with acc.
 static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view, float* d_out, void* stream_v,
-                          const pt::AccumPass* acc, const float* d_rays = nullptr, bool rays_irregular = false)
+                          const pt::AccumPass* acc, const float* d_rays = nullptr, bool rays_irregular = false, bool points = false)
 {
     if (!c || !p || !cam || (!d_out && !acc)) return pt::fail(PT_E_INVALID, "pt_render: null argument");
     if (c->fl_n >= pt_ctx::kFlights)
@@ -723,8 +752,10 @@ static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, c
     const bool wavefront = pt::takes_wavefront(p, cam, c->scene_extent, K.head_wf) && !rays_irregular;
     const bool rays_refwalk = d_rays && (rays_irregular || (p->flags & (PT_FLAG_REFERENCE_TRAVERSAL | PT_FLAG_REFERENCE_BVH)) != 0);
     if (d_rays && wavefront && (K.wf_min_waves != 5 || K.head_min_waves != 5))   // (never another kernel in silence)
-        return pt::fail(PT_E_INVALID, "pt_render_rays: only the default-occupancy wavefront kernels take a ray buffer "
-                        "(PT_WF_MIN_WAVES / PT_HEAD_MIN_WAVES are set)");
+        return pt::fail(PT_E_INVALID, "%s: only the default-occupancy wavefront kernels take a %s buffer "
+                        "(PT_WF_MIN_WAVES / PT_HEAD_MIN_WAVES are set)", points ? "pt_render_irradiance" : "pt_render_rays",
+                        points ? "point" : "ray");
+    if (points && acc) return pt::fail(PT_E_INVALID, "pt_render_irradiance: no accumulating kernel takes a point buffer");
     if (acc) {   // (pt_accum_create refused these already: never a silent fall-back to another kernel)
         if (!wavefront || count || K.wf_min_waves != 5 || K.head_min_waves != 5)
             return pt::fail(PT_E_INVALID, "pt_accum_add: this mode has no accumulating kernel");
@@ -745,9 +776,9 @@ static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, c
     HIP_TRY(hipEventRecord(F.ev0, stream));
     WavefrontDone wf;
     if (has_work && wavefront) {
-        if (int rc = enqueue_wavefront(c, p, acc, a, F, B, stream, &wf, d_rays)) return rc;
+        if (int rc = enqueue_wavefront(c, p, acc, a, F, B, stream, &wf, d_rays, points)) return rc;
     } else if (has_work) {
-        if (int rc = launch_tiles(c, p, B, lds, stream, a, d_rays, rays_refwalk)) return rc;
+        if (int rc = launch_tiles(c, p, B, lds, stream, a, d_rays, rays_refwalk, points)) return rc;
     }
     HIP_TRY(hipEventRecord(F.ev1, stream));
     HIP_TRY(hipMemcpyAsync(F.hcnt, B.counters, kCounterWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
@@ -1165,12 +1196,15 @@ extern "C" int pt_occluded(pt_ctx* c, uint32_t n, const float* rays, const float
 // ---- renders along caller-supplied rays (pt_render_rays_device, pt_render_rays, pt_rays_classify_device)
 
 // The classes of n rays at d_rays, through the context's four words: what both entry points below run first.
-static int classify_ctx_rays(pt_ctx* c, const char* who, uint32_t n, const float* d_rays, hipStream_t stream, pt_ray_classes* out)
+// (points: the records are the points {p, n} of an irradiance render)
+static int classify_ctx_rays(pt_ctx* c, const char* who, uint32_t n, const float* d_rays, hipStream_t stream, pt_ray_classes* out,
+                             bool points = false)
 {
-    if (reinterpret_cast<uintptr_t>(d_rays) % 8 != 0) return pt::fail(PT_E_INVALID, "%s: the ray buffer must be 8-byte aligned", who);
+    if (reinterpret_cast<uintptr_t>(d_rays) % 8 != 0)
+        return pt::fail(PT_E_INVALID, "%s: the %s buffer must be 8-byte aligned", who, points ? "point" : "ray");
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = pt::grow(&c->ray_classes, &c->ray_classes_words, 4)) return rc;
-    return pt::classify_ray_buffer(d_rays, n, 64.0f * c->scene_extent, c->num_cus, c->ray_classes, stream, out);
+    return pt::classify_ray_buffer(d_rays, n, 64.0f * c->scene_extent, c->num_cus, c->ray_classes, stream, out, points);
 }
 
 // The stand-in camera of a call that takes rays: it carries the image size for the checks and sits at the origin,
@@ -1187,13 +1221,16 @@ static pt_camera rays_stand_in(const pt_params* p)
 // The classes of an image's rays (p validated: width, height <= 65535), and the refusal of a buffer with an invalid
 // ray, its lowest pixel named.
 static int classify_image_rays(pt_ctx* c, const char* who, const pt_params* p, const float* d_rays, hipStream_t stream,
-                               pt_ray_classes* cls)
+                               pt_ray_classes* cls, bool points = false)
 {
     const uint32_t n = (uint32_t)p->width * (uint32_t)p->height;
-    if (int rc = classify_ctx_rays(c, who, n, d_rays, stream, cls)) return rc;
+    if (int rc = classify_ctx_rays(c, who, n, d_rays, stream, cls, points)) return rc;
     if (cls->invalid != 0) {
         uint32_t x = cls->first_invalid % (uint32_t)p->width, y = cls->first_invalid / (uint32_t)p->width;
         if (p->pixel_order == PT_ORDER_MORTON) pt_morton_i_to_pxl(cls->first_invalid, &x, &y);
+        if (points)
+            return pt::fail(PT_E_INVALID, "%s: %llu invalid points (a non-finite component or a normal that is not of unit length), "
+                            "the first at index %u, pixel (%u, %u)", who, (unsigned long long)cls->invalid, cls->first_invalid, x, y);
         return pt::fail(PT_E_INVALID, "%s: %llu invalid rays (a non-finite component or a zero direction), the first at "
                         "index %u, pixel (%u, %u)", who, (unsigned long long)cls->invalid, cls->first_invalid, x, y);
     }
@@ -1275,6 +1312,57 @@ extern "C" int pt_render_rays(pt_ctx* c, const pt_params* p, const float* rays, 
     HIP_TRY(hipMemcpy(c->rays_stage, rays, npx * 24, hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(c->scratch_out, 0, bytes, nullptr));
     if (int rc = pt_render_rays_device(c, p, c->rays_stage, c->scratch_out, nullptr, st)) return rc;
+    return pt::copy_to_host(out_rgb, c->scratch_out, bytes, nullptr, &c->pinned, &c->pinned_bytes);
+}
+
+// ---- irradiance renders at caller-supplied points (pt_render_irradiance_device, pt_render_irradiance,
+// pt_points_classify_device): pt_render_rays*'s entry points over a point buffer, word for word
+
+extern "C" int pt_points_classify_device(pt_ctx* c, uint32_t n, const float* d_points, void* stream, pt_ray_classes* out)
+{
+    pt::clear_error();
+    if (!c || !out) return pt::fail(PT_E_INVALID, "pt_points_classify_device: null argument");
+    if (n > 0 && !d_points) return pt::fail(PT_E_INVALID, "pt_points_classify_device: null buffer");
+    if (c->fl_n > 0)
+        return pt::fail(PT_E_INVALID, "pt_points_classify_device: %d asynchronous renders in flight (pt_render_wait first)", c->fl_n);
+    return classify_ctx_rays(c, "pt_points_classify_device", n, d_points, reinterpret_cast<hipStream_t>(stream), out, true);
+}
+
+extern "C" int pt_render_irradiance_device(pt_ctx* c, const pt_params* p, const float* d_points, float* d_out, void* stream,
+                                           pt_stats* st)
+{
+    pt::clear_error();
+    if (!c || !p || !d_points || !d_out) return pt::fail(PT_E_INVALID, "pt_render_irradiance: null argument");
+    if (c->fl_n > 0)
+        return pt::fail(PT_E_INVALID, "pt_render_irradiance: %d asynchronous renders in flight (pt_render_wait first)", c->fl_n);
+    constexpr uint32_t allowed = PT_FLAG_NO_DEAD_PATH_SKIP | PT_FLAG_NO_PRIMARY_CACHE | PT_FLAG_REFERENCE_TRAVERSAL | PT_FLAG_REFERENCE_BVH;
+    if (p->flags & ~allowed)
+        return pt::fail(PT_E_INVALID, "pt_render_irradiance: flags 0x%x: an irradiance render takes only PT_FLAG_NO_DEAD_PATH_SKIP, "
+                        "PT_FLAG_NO_PRIMARY_CACHE, PT_FLAG_REFERENCE_TRAVERSAL and PT_FLAG_REFERENCE_BVH (no counting variants, and "
+                        "no film to jitter on)", p->flags & ~allowed);
+    const pt_camera cam = rays_stand_in(p);
+    if (int rc = pt::validate_render(p, &cam)) return rc;
+    pt_ray_classes cls;
+    if (int rc = classify_image_rays(c, "pt_render_irradiance", p, d_points, reinterpret_cast<hipStream_t>(stream), &cls, true)) return rc;
+    if (int rc = render_enqueue(c, p, &cam, nullptr, d_out, stream, nullptr, d_points, cls.irregular != 0, true)) return rc;
+    return pt_render_wait(c, st);
+}
+
+extern "C" int pt_render_irradiance(pt_ctx* c, const pt_params* p, const float* points, float* out_rgb, pt_stats* st)
+{
+    pt::clear_error();
+    if (!c || !p || !points || !out_rgb) return pt::fail(PT_E_INVALID, "pt_render_irradiance: null argument");
+    if (p->width <= 0 || p->height <= 0 || p->width > 65535 || p->height > 65535)
+        return pt::fail(PT_E_INVALID, "pt_render_irradiance: image size %dx%d out of range (1..65535)", p->width, p->height);
+    if (c->fl_n > 0)
+        return pt::fail(PT_E_INVALID, "pt_render_irradiance: %d asynchronous renders in flight (pt_render_wait first)", c->fl_n);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t npx = (size_t)p->width * (size_t)p->height, bytes = npx * 3 * sizeof(float);
+    if (int rc = pt::grow(&c->rays_stage, &c->rays_stage_floats, npx * 6)) return rc;   // (the ray renders' staging buffer)
+    if (int rc = pt::grow(&c->scratch_out, &c->scratch_floats, npx * 3)) return rc;
+    HIP_TRY(hipMemcpy(c->rays_stage, points, npx * 24, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(c->scratch_out, 0, bytes, nullptr));
+    if (int rc = pt_render_irradiance_device(c, p, c->rays_stage, c->scratch_out, nullptr, st)) return rc;
     return pt::copy_to_host(out_rgb, c->scratch_out, bytes, nullptr, &c->pinned, &c->pinned_bytes);
 }
 

@@ -119,8 +119,9 @@ int ctx_num_cus(const pt_ctx* c);
 
 // ---- the classes of a ray buffer (pt_rays.hip): d_rays[0..n) on the current device, 8-byte aligned, against
 // origin_max = 64 scene extents; d_words: four device words the context keeps.  Blocking: *out is final on return.
+// points: the records are the points {p, n} of an irradiance render, classified by pt.h's point classes.
 int classify_ray_buffer(const float* d_rays, uint32_t n, float origin_max, int num_cus, uint32_t* d_words, void* stream,
-                  pt_ray_classes* out);
+                  pt_ray_classes* out, bool points = false);
 
 // PT_TIMING=1: the host wall time of each stage of a checkpoint / session save or load on stderr, "who: stage ms"
 // (every stage ends in a blocking call; the measurements of DESIGN.md 8).

@@ -1,4 +1,5 @@
-"""Ray sets for Renderer.render_rays (pt_render_rays): host only, numpy.
+"""Ray sets for Renderer.render_rays (pt_render_rays) and point sets for Renderer.render_irradiance
+(pt_render_irradiance): host only, numpy.
 
 Every helper returns (origins, directions), two float32 arrays of shape (W*H, 3) in scanline order (the ray of pixel
 (x, y) at y*W + x), the directions normalised in float32 -- so every ray is "regular" for a scene the origins lie
@@ -7,6 +8,10 @@ Morton order first.
 
 The image orientation is the pinhole camera's: a set built at the camera's pose shows the scene the way
 Renderer.render does (film x and y grow against the view's right and up, as camera.h's film does).
+
+The point helpers (grid_points, triangle_points, feature_points) return (points, normals) the same way, the normals
+normalised in float32 and the points lifted `lift` along them: an irradiance render uses a point as given, and one
+lying in its own surface is black.
 """
 from __future__ import annotations
 
@@ -112,3 +117,49 @@ def fisheye_rays(pos, target, up, fov_deg, W, H):
     d = np.cos(ang)[:, None] * (0.0 - back) + np.sin(ang)[:, None] * lat
     o = np.broadcast_to(np.asarray(pos, dtype=np.float64), d.shape)
     return np.ascontiguousarray(o, dtype=F), _normalised(d)
+
+
+def _lifted(p, n, lift):
+    """(p + lift * n, n) as float32 (W*H, 3) arrays, n normalised in float32 first."""
+    n = _normalised(n)
+    p = np.asarray(p, dtype=np.float64) + float(lift) * n.astype(np.float64)
+    return np.ascontiguousarray(p, dtype=F), n
+
+
+def grid_points(corner, edge_u, edge_v, W, H, lift=1e-3):
+    """Texel centres on the parallelogram corner + u * edge_u + v * edge_v, u = (x + 0.5) / W, v = (y + 0.5) / H, in
+    scanline order; every normal is cross(edge_u, edge_v), normalised."""
+    sx, sy = _film(W, H)
+    c, eu, ev = (np.asarray(v, dtype=np.float64) for v in (corner, edge_u, edge_v))
+    nrm = np.cross(eu, ev)
+    if not np.linalg.norm(nrm) > 0:
+        raise ValueError("rays: edge_u and edge_v are parallel")
+    p = c[None, :] + (sx + 0.5)[:, None] * eu + (sy + 0.5)[:, None] * ev
+    return _lifted(p, np.broadcast_to(nrm, p.shape), lift)
+
+
+def triangle_points(arrays, tri, b1, b2, lift=1e-3):
+    """Points v0 + b1 * (v1 - v0) + b2 * (v2 - v0) on triangles `tri` of Scene.arrays(), with the triangles' stored
+    normals (normalised).  tri, b1, b2: one entry per point (scalars broadcast)."""
+    tri = np.atleast_1d(np.asarray(tri, dtype=np.int64))
+    b1 = np.broadcast_to(np.asarray(b1, dtype=np.float64), tri.shape)
+    b2 = np.broadcast_to(np.asarray(b2, dtype=np.float64), tri.shape)
+    t = arrays["tris"][tri]
+    vx = np.stack([arrays["verts"][k].astype(np.float64) for k in ("x", "y", "z")], axis=1)
+    v0, v1, v2 = vx[t["v0"]], vx[t["v1"]], vx[t["v2"]]
+    p = v0 + b1[:, None] * (v1 - v0) + b2[:, None] * (v2 - v0)
+    nrm = np.stack([t["nx"], t["ny"], t["nz"]], axis=1)
+    return _lifted(p, nrm, lift)
+
+
+def feature_points(features, lift=1e-3):
+    """The primary-hit positions and normals of a feature buffer (Renderer.features / features_rays), flattened in
+    the buffer's own order: "bake what this camera sees".  Returns (points, normals, miss): miss marks the pixels
+    without a hit (prim < 0), whose entries are a valid dummy point, the origin with normal +y."""
+    f = np.asarray(features).reshape(-1)
+    miss = f["prim"] < 0
+    nrm = np.where(miss[:, None], np.array([0.0, 1.0, 0.0], dtype=F), f["normal"]).astype(F)
+    pos = np.where(miss[:, None], F(0.0), f["position"])
+    p, n = _lifted(pos, nrm, lift)
+    p[miss] = 0.0
+    return p, n, miss

@@ -851,14 +851,64 @@ int pt_occluded(pt_ctx* ctx, uint32_t n, const float* rays, const float* tmax /*
  * over a ray buffer: pt_accum_create_rays* and pt_render_features_rays*, below the denoisers.
  *
  * Out of scope: sessions and checkpoints over a ray buffer; pt_render_group / pt_render_multi; temporal reprojection
- * for ray renders; a per-sample ray source (anti-aliasing or depth of field for custom projections); passes from the
- * command line (pt_cli --rays renders one shot). */
+ * for ray renders; anti-aliasing and depth of field for custom projections (the one per-sample ray source is the
+ * cosine hemisphere of pt_render_irradiance*, below); passes from the command line (pt_cli --rays renders one
+ * shot). */
 typedef struct { uint64_t regular, irregular, invalid; uint32_t first_invalid; uint32_t pad; } pt_ray_classes;
 int pt_render_rays_device(pt_ctx* ctx, const pt_params* params, const float* d_rays, float* d_out, void* stream,
                           pt_stats* stats);
 int pt_render_rays(pt_ctx* ctx, const pt_params* params, const float* rays /* host */, float* out_rgb /* host */,
                    pt_stats* stats);
 int pt_rays_classify_device(pt_ctx* ctx, uint32_t n, const float* d_rays, void* stream, pt_ray_classes* out /* host */);
+
+/* ------------------------------------------------------------------ irradiance renders at caller-supplied points
+ * A ray render sends every sample of a pixel down one fixed ray.  An irradiance render gives every sample a fresh
+ * direction over the hemisphere of a surface point: lightmap texels, surface probes, light baking.
+ *
+ * A point buffer holds width * height * 6 floats, {p.xyz, n.xyz} per pixel (position, unit normal), indexed exactly
+ * like a ray buffer (params->pixel_order) and 8-byte aligned on the device.  Pixel (x, y) is
+ *     rng = curand_init(seed, morton(x, y), 0)
+ *     for s = 1..spp:
+ *         u1 = uniform(rng); u2 = uniform(rng)
+ *         d  = cosineWeightedRay(n, u1, u2)      (kernel.cu:78-99: the device function the bounces already use)
+ *         L  = integrator(p, d, rng)
+ *         m  = m*(s-1)/s + L/s                   (kernel.cu:551-552)
+ * A sample's draws are those of a lens pixel: a pair first, then the integrator's own (integrator 1: 9 draws per
+ * sample).  No pixel has a sample-invariant ray, so there is no primary-hit memo of any kind:
+ * PT_FLAG_NO_PRIMARY_CACHE is legal and changes nothing, neither the image nor rays_traced.
+ *
+ * What m is: the cosine-weighted mean of the incoming radiance over n's hemisphere, E / pi for the irradiance E.  A
+ * Lambertian texel's outgoing radiance is its albedo times m.
+ *
+ * p is used as given: the caller lifts it off the surface (the helpers of cudapathtracer_amd.rays take a `lift`
+ * along the normal).  The self-hit rule is the integrator's: it zeroes a path whose first hit is nearer than 0.002
+ * (closestT -= 0.001; if (closestT < 0.001)), so a point lying in a surface it can see is black along those
+ * directions.
+ *
+ * Point classes.  Every one of the width * height points is classified before a render, by the kernel
+ * pt_points_classify_device makes public, into the same pt_ray_classes; all arithmetic is float32:
+ *     invalid    a non-finite component, or (n.x*n.x + n.y*n.y) + n.z*n.z outside [1 - 2^-10, 1 + 2^-10] (a normal
+ *                far from unit length bends the distribution, a tiny one underflows the tangent: both are refused)
+ *     regular    max |p_k| <= 64 * the scene's extent
+ *     irregular  every other valid point
+ * An invalid point refuses the render (PT_E_INVALID, the lowest such pixel is named, nothing is written).  A single
+ * irregular point sends THE WHOLE RENDER to the tile kernel with the reference's walk, as for ray buffers;
+ * stats->work_units == 0 shows it.  The direction handed to the walk is normalized(...) in float32, so it is always
+ * within pt_trace's length rule.
+ *
+ * Flags, shard fields, tile sizes, pixel order, empty shards, spp == 0, blocking behaviour, the refusal while
+ * asynchronous renders are in flight and the refusal of non-default PT_WF_MIN_WAVES / PT_HEAD_MIN_WAVES are
+ * pt_render_rays*'s.  The host call stages the points through the context's ray staging buffer.  pt_stats keeps its
+ * meanings; rays_reference counts the trace() calls of the loop above.
+ *
+ * Out of scope: accumulators, noise estimates, adaptive sampling, feature buffers, checkpoints and sessions over a
+ * point buffer; pt_render_group / pt_render_multi; other distributions (uniform sphere, cones); passes from the
+ * command line (pt_cli --irradiance renders one shot). */
+int pt_render_irradiance_device(pt_ctx* ctx, const pt_params* params, const float* d_points, float* d_out, void* stream,
+                                pt_stats* stats);
+int pt_render_irradiance(pt_ctx* ctx, const pt_params* params, const float* points /* host */, float* out_rgb /* host */,
+                         pt_stats* stats);
+int pt_points_classify_device(pt_ctx* ctx, uint32_t n, const float* d_points, void* stream, pt_ray_classes* out /* host */);
 
 /* Output step on the GPU (kernel.cu:763-778, color.h:59-71): codes = pt_tonemap_u8(rgb) per
  * channel, identical to the host function (threshold table bisected with the host's libm at
