@@ -233,6 +233,9 @@ SIGNATURES = {
     "pt_accum_create_rays_device": (C.c_void_p, [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "pt_accum_create_rays": (C.c_void_p, [C.c_void_p, C.POINTER(Params), C.c_void_p, C.POINTER(C.c_int)]),
     "pt_accum_has_rays": (C.c_int, [C.c_void_p]),
+    "pt_accum_create_points_device": (C.c_void_p, [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "pt_accum_create_points": (C.c_void_p, [C.c_void_p, C.POINTER(Params), C.c_void_p, C.POINTER(C.c_int)]),
+    "pt_accum_has_points": (C.c_int, [C.c_void_p]),
     "pt_render_features_rays_device": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p]),
     "pt_render_features_rays": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p]),
     "pt_accum_add": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),

@@ -667,6 +667,41 @@ class Renderer:
             L.check(err.value if err.value != 0 else L.PT_E_HIP)
         return Accumulator(self, h, p)
 
+    def accumulator_points(self, points, normals, width, height, bounces=3, integrator=0, seed=1234, flags=0,
+                           shard_index=0, shard_count=1, pixel_order=0, tile=0):
+        """A resumable irradiance render of this shard at the caller's points (pt_accum_create_points): a progressive
+        bake.  accumulator_rays() with the rays replaced by W*H points {p, n} indexed as for render_irradiance(); the
+        accumulator copies the points and keeps them for life.  add() in any split of passes equals
+        render_irradiance() of the same total in every bit; noise estimates, add_until, add_adaptive and freeze work
+        as on a camera accumulator, and freeze() at 0 samples masks texels (rays.chart_points names the uncovered
+        ones; a masked texel still needs a valid point).  Every point must be regular: one beyond 64 scene extents is
+        refused here (PtError PT_E_INVALID; render_irradiance takes such a buffer).  flags: 0,
+        PT_FLAG_NO_DEAD_PATH_SKIP, PT_FLAG_NO_PRIMARY_CACHE (which changes nothing).  save() and save_session() are
+        refused."""
+        pts, n = self._rays(points, normals)
+        if n != int(width) * int(height):
+            raise ValueError("accumulator_points: %d points for a %dx%d image" % (n, width, height))
+        tw, th = (tile, tile) if np.isscalar(tile) else tile
+        p = self.params(width, height, 0, bounces, integrator, seed, flags, shard_index, shard_count, pixel_order, tw, th)
+        err = C.c_int(0)
+        h = L.lib().pt_accum_create_points(self._h, C.byref(p), pts.ctypes.data, C.byref(err))
+        if not h:
+            L.check(err.value if err.value != 0 else L.PT_E_HIP)
+        return Accumulator(self, h, p)
+
+    def accumulator_points_device(self, d_points_ptr, width, height, bounces=3, integrator=0, seed=1234, flags=0,
+                                  shard_index=0, shard_count=1, pixel_order=0, tile=0, stream_ptr=None):
+        """accumulator_points() over W*H points on the device (float32[6*W*H], 8-byte aligned;
+        pt_accum_create_points_device).  The buffer is copied: it may be freed or overwritten once this returns."""
+        tw, th = (tile, tile) if np.isscalar(tile) else tile
+        p = self.params(width, height, 0, bounces, integrator, seed, flags, shard_index, shard_count, pixel_order, tw, th)
+        err = C.c_int(0)
+        h = L.lib().pt_accum_create_points_device(self._h, C.byref(p), C.c_void_p(int(d_points_ptr)),
+                                                  None if stream_ptr is None else C.c_void_p(int(stream_ptr)), C.byref(err))
+        if not h:
+            L.check(err.value if err.value != 0 else L.PT_E_HIP)
+        return Accumulator(self, h, p)
+
     def features_rays(self, origins, directions, width, height, pixel_order=0, shard_index=0, shard_count=1, tile=0):
         """Feature buffers of the caller's rays (pt_render_features_rays): features() with each pixel's ray taken from
         the buffer as it stands.  depth is the hit distance along the given direction, in units of its length;
@@ -828,6 +863,11 @@ class Accumulator:
     def has_rays(self):
         """Whether the accumulator was built over a ray buffer (Renderer.accumulator_rays*; pt_accum_has_rays)."""
         return bool(L.lib().pt_accum_has_rays(self._h))
+
+    @property
+    def has_points(self):
+        """Whether the accumulator was built over a point buffer (Renderer.accumulator_points*; pt_accum_has_points)."""
+        return bool(L.lib().pt_accum_has_points(self._h))
 
     def _shape(self):
         p = self.params

@@ -107,6 +107,7 @@ struct pt_accum {
     uint32_t nactive = 0;             // entries of d_list (list_valid)
     uint32_t* d_slot_pix = nullptr;   // slot_pix on the device, uploaded when a session file first needs it (pt_session.hip)
     float* d_rays = nullptr;          // a ray accumulator's own copy of its rays (width * height * 6 floats), kept for life
+    bool points = false;              // d_rays holds points {p, n}: a point accumulator (pt_accum_create_points*)
     size_t slots() const { return slot_pix.size(); }
 };
 
@@ -299,22 +300,25 @@ pt_accum* pt_accum_create(pt_ctx* ctx, const pt_params* params, const pt_camera*
 
 // The accumulator of (c, p) over a copy of the width * height rays at `rays` (host memory, or device memory read on
 // `stream`), or null with the error recorded: the checks in pt.h's order, the copy, then the copy's classes.
-static pt_accum* make_accum_rays(pt_ctx* c, const pt_params* p, const float* rays, bool host, void* stream, int* code)
+// (points: the records are points {p, n} and the accumulator is a point accumulator, pt_accum_create_points*)
+static pt_accum* make_accum_rays(pt_ctx* c, const pt_params* p, const float* rays, bool host, void* stream, int* code,
+                                 bool points = false)
 {
+    const char* who = points ? "pt_accum_create_points" : "pt_accum_create_rays";
     if (pt::ctx_in_flight(c) > 0) {
-        *code = pt::fail(PT_E_INVALID, "pt_accum_create_rays: %d asynchronous renders in flight (pt_render_wait first)",
-                         pt::ctx_in_flight(c));
+        *code = pt::fail(PT_E_INVALID, "%s: %d asynchronous renders in flight (pt_render_wait first)", who, pt::ctx_in_flight(c));
         return nullptr;
     }
     pt_camera cam;
-    *code = pt::accum_check_rays(c, p, &cam);
+    *code = pt::accum_check_rays(c, p, &cam, points);
     if (*code != PT_OK) return nullptr;
     if (!host && reinterpret_cast<uintptr_t>(rays) % 8 != 0) {
-        *code = pt::fail(PT_E_INVALID, "pt_accum_create_rays: the ray buffer must be 8-byte aligned");
+        *code = pt::fail(PT_E_INVALID, "%s: the %s buffer must be 8-byte aligned", who, points ? "point" : "ray");
         return nullptr;
     }
     pt_accum* a = make_accum(c, p, &cam, nullptr, code);
     if (!a) return nullptr;
+    a->points = points;
     auto copy = [&]() -> int {
         const size_t bytes = (size_t)p->width * (size_t)p->height * 6 * sizeof(float);
         HIP_TRY(hipMalloc(reinterpret_cast<void**>(&a->d_rays), bytes));
@@ -324,7 +328,7 @@ static pt_accum* make_accum_rays(pt_ctx* c, const pt_params* p, const float* ray
             HIP_TRY(hipMemcpyAsync(a->d_rays, rays, bytes, hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream)));
         }
         // (its own copy is what gets classified: what the passes read is what was checked)
-        return pt::accum_classify_rays(c, p, a->d_rays, host ? nullptr : stream);
+        return pt::accum_classify_rays(c, p, a->d_rays, host ? nullptr : stream, points);
     };
     *code = copy();
     if (*code != PT_OK) { pt_accum_destroy(a); return nullptr; }
@@ -353,7 +357,31 @@ pt_accum* pt_accum_create_rays(pt_ctx* ctx, const pt_params* params, const float
     return a;
 }
 
-int pt_accum_has_rays(const pt_accum* acc) { return (acc && acc->d_rays) ? 1 : 0; }
+int pt_accum_has_rays(const pt_accum* acc) { return (acc && acc->d_rays && !acc->points) ? 1 : 0; }
+
+pt_accum* pt_accum_create_points_device(pt_ctx* ctx, const pt_params* params, const float* d_points, void* stream, int* err)
+{
+    pt::clear_error();
+    int code;
+    pt_accum* a = nullptr;
+    if (!ctx || !params || !d_points) code = pt::fail(PT_E_INVALID, "pt_accum_create_points: null argument");
+    else a = make_accum_rays(ctx, params, d_points, false, stream, &code, true);
+    if (err) *err = code;
+    return a;
+}
+
+pt_accum* pt_accum_create_points(pt_ctx* ctx, const pt_params* params, const float* points, int* err)
+{
+    pt::clear_error();
+    int code;
+    pt_accum* a = nullptr;
+    if (!ctx || !params || !points) code = pt::fail(PT_E_INVALID, "pt_accum_create_points: null argument");
+    else a = make_accum_rays(ctx, params, points, true, nullptr, &code, true);
+    if (err) *err = code;
+    return a;
+}
+
+int pt_accum_has_points(const pt_accum* acc) { return (acc && acc->d_rays && acc->points) ? 1 : 0; }
 
 int pt_accum_view(const pt_accum* acc, pt_view* out, int* has_view)
 {
@@ -384,6 +412,7 @@ int pt_accum_add(pt_accum* acc, int32_t spp, float* d_out, void* stream, pt_stat
     p.spp = spp;
     pt::AccumPass pass{(uint32_t)acc->samples, acc->d_rng, acc->d_mean};
     pass.rays = acc->d_rays;
+    pass.points = acc->points;
     if (acc->any_frozen) {   // an adaptive pass: the active pixels only
         if (int rc = active_list(acc, stream)) return rc;
         if (acc->nactive == 0) {   // every pixel frozen: nothing to sample, the count stays
@@ -553,6 +582,9 @@ int pt_accum_save(pt_accum* acc, const char* path)
     pt::clear_error();
     if (!acc || !path) return pt::fail(PT_E_INVALID, "pt_accum_save: null argument");
     if (!little_endian()) return pt::fail(PT_E_INVALID, "pt_accum_save: checkpoint files are little-endian; this host is not");
+    if (acc->d_rays && acc->points)
+        return pt::fail(PT_E_INVALID, "pt_accum_save: the accumulator was built over a point buffer (pt_accum_create_points); a "
+                        "checkpoint file holds a camera, not points");
     if (acc->d_rays)
         return pt::fail(PT_E_INVALID, "pt_accum_save: the accumulator was built over a ray buffer (pt_accum_create_rays); a "
                         "checkpoint file holds a camera, not rays");

@@ -1086,8 +1086,10 @@ __global__ __launch_bounds__(256) void init_pixel_states(Args a, uint32_t* __res
 // accumulating unit, whose UW_TQ names the slot: the row (stride npix, the shard's slot count) the integration
 // kernels load the unit's mean from and store its mean and stream to.  nunits = nwhole = the list's length.
 // (kRays: the active list of a ray accumulator, init_active_states_rays -- a pinhole unit whose direction is the
-// pixel's in RayArgs::rays, Morton index 0 too, as in init_pixel_states_body)
-template <bool kJit, bool kRays = false>
+// pixel's in RayArgs::rays, Morton index 0 too, as in init_pixel_states_body;
+// kPts: the active list of a point accumulator, init_active_states_points -- every unit is marked as a lens unit is,
+// with no UW_CD direction: a sample draws its pair and forms its ray itself, again as in init_pixel_states_body)
+template <bool kJit, bool kRays = false, bool kPts = false>
 __device__ __forceinline__ void init_active_states_body(const Args& a, uint32_t* __restrict__ st, const uint32_t* __restrict__ list)
 {
     const uint32_t u = blockIdx.x * 256u + threadIdx.x;
@@ -1103,7 +1105,7 @@ __device__ __forceinline__ void init_active_states_body(const Args& a, uint32_t*
     const uint32_t idx = morton2(px, py);
     Rng r;
     slot_stream(a, q, idx, a.acc_n0, r);
-    const bool lens = !kRays && (kJit || (idx == 0) || (a.cam.radius != 0.0f));   // (kJit: every unit's rays are formed per sample)
+    const bool lens = kPts || (!kRays && (kJit || (idx == 0) || (a.cam.radius != 0.0f)));   // (kJit: every unit's rays are formed per sample)
     const V3 d = kRays ? ray_direction(a, px, py) : pinhole_dir(a, px, py, lens);
     st[u] = r.v0;
     st[N + u] = r.v1;
@@ -3017,6 +3019,28 @@ template <int kIntegrator, bool kRefWalk, bool kCount>
 __global__ __launch_bounds__(64) void render_tiles_points(RayArgs a)
 {
     render_tiles_body<kIntegrator, kRefWalk, kCount, false, false, false, true>(a);
+}
+
+// ------------------------------------------------------------------ accumulators over caller-supplied points
+// pt_accum_create_points*: the accumulating twins of the two point-source wavefront kernels and the set-up of an
+// adaptive pass over a point accumulator -- defined and first used after every other kernel yet again, which
+// therefore compile as they did.  The unfrozen accumulating pass is set up by
+// init_pixel_states_points, whose body honours Args::accum: the stream continues from acc_rng, the sample numbers
+// from acc_n0, a whole-pixel unit carries its slot, and a split unit's replay skips the sample's pair as a lens
+// unit's does.
+template <bool kLdsWalk>
+__global__ __launch_bounds__(256, 5) void render_unidir_accum_points_wf(RayArgs a)
+{
+    wf_main<false, false, kLdsWalk, true, false, false, false, true>(a);
+}
+__global__ __launch_bounds__(256, 5) void render_head_accum_points_wf(RayArgs a)
+{
+    wf_main<false, true, true, true, false, false, false, true>(a);
+}
+
+__global__ __launch_bounds__(256) void init_active_states_points(RayArgs a, uint32_t* __restrict__ st, const uint32_t* __restrict__ list)
+{
+    init_active_states_body<false, false, true>(a, st, list);
 }
 
 }  // namespace

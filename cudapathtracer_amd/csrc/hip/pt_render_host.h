@@ -543,16 +543,19 @@ static int launch_wavefront(const pt::WavefrontVariant& v, const WavefrontLaunch
         HIP_TRY(hipGetLastError());
         return PT_OK;
     }
-    if (rays) {   // (the point-source instances of an irradiance render: default occupancy only, no accumulating twins)
+    if (rays) {   // (the point-source instances of an irradiance render: default occupancy only)
         void (*pkernel)(RayArgs) = nullptr;
         switch (v.code()) {
         case code(true, false, 5, false, false): pkernel = render_head_points_wf; break;
         case code(false, false, 5, true, false): pkernel = render_unidir_points_wf<true>; break;
         case code(false, false, 5, false, false): pkernel = render_unidir_points_wf<false>; break;
+        case code(true, false, 5, false, true): pkernel = render_head_accum_points_wf; break;   // (a point accumulator's passes)
+        case code(false, false, 5, true, true): pkernel = render_unidir_accum_points_wf<true>; break;
+        case code(false, false, 5, false, true): pkernel = render_unidir_accum_points_wf<false>; break;
         default:
-            return pt::fail(PT_E_INVALID, "pt_render_irradiance: no point-source wavefront kernel instance for head %d count %d waves "
+            return pt::fail(PT_E_INVALID, "%s: no point-source wavefront kernel instance for head %d count %d waves "
                             "%d lds %d accum %d (only the default PT_WF_MIN_WAVES / PT_HEAD_MIN_WAVES have one)",
-                            v.head, v.count, v.min_waves, v.lds_walk, v.accum);
+                            v.accum ? "pt_accum_add" : "pt_render_irradiance", v.head, v.count, v.min_waves, v.lds_walk, v.accum);
         }
         RayArgs rb;
         static_cast<Args&>(rb) = b;
@@ -639,7 +642,8 @@ struct WavefrontDone {
 };
 
 // The wavefront path of one render, from its plan to finalize_pixels.  a: the render's Args; F: its flight slot.
-// (rays: a render along a caller's rays, or null; points: the buffer holds the points of an irradiance render)
+// (rays: a render along a caller's rays, or null; points: the buffer holds the points of an irradiance render or of a
+// point accumulator)
 static int enqueue_wavefront(pt_ctx* c, const pt_params* p, const pt::AccumPass* acc, const Args& a, pt_ctx::Flight& F,
                              pt_ctx::Bufs& B, hipStream_t stream, WavefrontDone* done, const float* rays, bool points)
 {
@@ -663,7 +667,9 @@ static int enqueue_wavefront(pt_ctx* c, const pt_params* p, const pt::AccumPass*
         RayArgs rb;
         static_cast<Args&>(rb) = b;
         rb.rays = rays;
-        hipLaunchKernelGGL(init_active_states_rays, dim3((b.nunits + 255) / 256), dim3(256), 0, stream, rb, B.pix_states, acc->active);
+        // (points: a point accumulator's, whose every unit is a lens unit)
+        hipLaunchKernelGGL(points ? init_active_states_points : init_active_states_rays, dim3((b.nunits + 255) / 256), dim3(256), 0,
+                           stream, rb, B.pix_states, acc->active);
     } else if (!rays)
         hipLaunchKernelGGL(jitter ? init_pixel_states_jitter : init_pixel_states, dim3((b.npix + 255) / 256), dim3(256), 0, stream,
                            b, B.pix_states);
@@ -699,7 +705,7 @@ static int enqueue_wavefront(pt_ctx* c, const pt_params* p, const pt::AccumPass*
 // accumulator, whose rays were classified when it was created; cam is then a stand-in that only carries the image
 // size); rays_irregular: the buffer holds an irregular ray, so the whole render
 // takes the tile kernel with the reference's own walk.  points: d_rays holds the points {p, n} of an irradiance render
-// (pt_render_irradiance_device), classified likewise; never with acc.
+// (pt_render_irradiance_device) or of a point accumulator's pass, classified likewise.
 static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view, float* d_out, void* stream_v,
                           const pt::AccumPass* acc, const float* d_rays = nullptr, bool rays_irregular = false, bool points = false)
 {
@@ -755,7 +761,6 @@ static int render_enqueue(pt_ctx* c, const pt_params* p, const pt_camera* cam, c
         return pt::fail(PT_E_INVALID, "%s: only the default-occupancy wavefront kernels take a %s buffer "
                         "(PT_WF_MIN_WAVES / PT_HEAD_MIN_WAVES are set)", points ? "pt_render_irradiance" : "pt_render_rays",
                         points ? "point" : "ray");
-    if (points && acc) return pt::fail(PT_E_INVALID, "pt_render_irradiance: no accumulating kernel takes a point buffer");
     if (acc) {   // (pt_accum_create refused these already: never a silent fall-back to another kernel)
         if (!wavefront || count || K.wf_min_waves != 5 || K.head_min_waves != 5)
             return pt::fail(PT_E_INVALID, "pt_accum_add: this mode has no accumulating kernel");
@@ -911,7 +916,7 @@ int pt::accum_pass(pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt
 {
     if (c->fl_n > 0)
         return pt::fail(PT_E_INVALID, "pt_accum_add: %d asynchronous renders in flight (pt_render_wait first)", c->fl_n);
-    if (int rc = render_enqueue(c, p, cam, view, d_out, stream, &acc, acc.rays)) return rc;   // (rays: all regular)
+    if (int rc = render_enqueue(c, p, cam, view, d_out, stream, &acc, acc.rays, false, acc.points)) return rc;   // (rays: all regular)
     return pt_render_wait(c, stats);
 }
 
@@ -1266,31 +1271,39 @@ extern "C" int pt_render_rays_device(pt_ctx* c, const pt_params* p, const float*
     return pt_render_wait(c, st);
 }
 
-// ---- accumulators over a ray buffer (pt_accum_create_rays*, pt_accum.cpp): the context's side
-int pt::accum_check_rays(const pt_ctx* c, const pt_params* p, pt_camera* stand_in)
+// ---- accumulators over a ray buffer or a point buffer (pt_accum_create_rays*, pt_accum_create_points*, pt_accum.cpp):
+// the context's side
+int pt::accum_check_rays(const pt_ctx* c, const pt_params* p, pt_camera* stand_in, bool points)
 {
+    const char* who = points ? "pt_accum_create_points" : "pt_accum_create_rays";
     constexpr uint32_t allowed = PT_FLAG_NO_DEAD_PATH_SKIP | PT_FLAG_NO_PRIMARY_CACHE;
     if (p->flags & ~allowed)
-        return pt::fail(PT_E_INVALID, "pt_accum_create_rays: flags 0x%x: an accumulator over rays takes only PT_FLAG_NO_DEAD_PATH_SKIP "
+        return pt::fail(PT_E_INVALID, "%s: flags 0x%x: an accumulator over %s takes only PT_FLAG_NO_DEAD_PATH_SKIP "
                         "and PT_FLAG_NO_PRIMARY_CACHE (the reference walks and the counting variants have no accumulating kernel, "
-                        "and there is no film to jitter on)", p->flags & ~allowed);
+                        "and there is no film to jitter on)", who, p->flags & ~allowed, points ? "points" : "rays");
     *stand_in = rays_stand_in(p);
     if (int rc = validate_render(p, stand_in)) return rc;
     const RenderKnobs& K = c->knobs;
     if (!takes_wavefront(p, stand_in, c->scene_extent, K.head_wf))
-        return pt::fail(PT_E_INVALID, "pt_accum_create_rays: this render would take the tile kernel (integrator 1 with PT_HEAD_WF=0), "
-                        "which does not accumulate");
+        return pt::fail(PT_E_INVALID, "%s: this render would take the tile kernel (integrator 1 with PT_HEAD_WF=0), "
+                        "which does not accumulate", who);
     if (K.wf_min_waves != 5 || K.head_min_waves != 5)
-        return pt::fail(PT_E_INVALID, "pt_accum_create_rays: only the default-occupancy kernels accumulate (PT_WF_MIN_WAVES / "
-                        "PT_HEAD_MIN_WAVES are set)");
+        return pt::fail(PT_E_INVALID, "%s: only the default-occupancy kernels accumulate (PT_WF_MIN_WAVES / "
+                        "PT_HEAD_MIN_WAVES are set)", who);
     return PT_OK;
 }
 
-int pt::accum_classify_rays(pt_ctx* c, const pt_params* p, const float* d_rays, void* stream)
+int pt::accum_classify_rays(pt_ctx* c, const pt_params* p, const float* d_rays, void* stream, bool points)
 {
     pt_ray_classes cls;
-    if (int rc = classify_image_rays(c, "pt_accum_create_rays", p, d_rays, reinterpret_cast<hipStream_t>(stream), &cls)) return rc;
-    if (cls.irregular != 0)   // (never a silent fall-back: the accumulating kernels are the wavefront kernels)
+    if (int rc = classify_image_rays(c, points ? "pt_accum_create_points" : "pt_accum_create_rays", p, d_rays,
+                                     reinterpret_cast<hipStream_t>(stream), &cls, points))
+        return rc;
+    if (cls.irregular != 0 && points)   // (never a silent fall-back: the accumulating kernels are the wavefront kernels)
+        return pt::fail(PT_E_INVALID, "pt_accum_create_points: %llu irregular points (a position beyond 64 scene extents); "
+                        "accumulation runs on the wavefront kernels only -- pt_render_irradiance takes such a buffer",
+                        (unsigned long long)cls.irregular);
+    if (cls.irregular != 0)
         return pt::fail(PT_E_INVALID, "pt_accum_create_rays: %llu irregular rays (an origin beyond 64 scene extents, or a direction "
                         "longer than a normalised one); accumulation runs on the wavefront kernels only -- pt_render_rays takes "
                         "such a buffer", (unsigned long long)cls.irregular);

@@ -196,6 +196,9 @@ int pt_session_save(pt_accum* acc, pt_noise* noise, const char* path)
     if (pt_accum_has_rays(acc))
         return pt::fail(PT_E_INVALID, "pt_session_save: the accumulator was built over a ray buffer (pt_accum_create_rays); a "
                         "session file holds a camera, not rays");
+    if (pt_accum_has_points(acc))
+        return pt::fail(PT_E_INVALID, "pt_session_save: the accumulator was built over a point buffer (pt_accum_create_points); a "
+                        "session file holds a camera, not points");
     pt::StageTimer timer{"pt_session_save"};
     const pt::AccumView view = pt::accum_view(acc);
     if (noise && noise != *view.noise) return pt::fail(PT_E_INVALID, "pt_session_save: the estimator is not this accumulator's live estimator");

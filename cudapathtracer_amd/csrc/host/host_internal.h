@@ -59,6 +59,9 @@ struct AccumPass {
     // a pass of a ray accumulator (pt_accum_create_rays*): its own copy of the rays (device, width * height * 6 floats,
     // every one regular), indexed in the accumulator's pixel order; cam is then the stand-in of accum_check_rays
     const float* rays = nullptr;
+    // a pass of a point accumulator (pt_accum_create_points*): rays holds its own copy of the points {p, n}, every one
+    // regular, and every sample leaves its pixel's point along a cosine-weighted direction (pt_render_irradiance's loop)
+    bool points = false;
 };
 // Validates (params, cam) as pt_render_device_async does and refuses every mode without an accumulating
 // kernel (render_tiles, the counting variants, non-default occupancy).
@@ -66,11 +69,13 @@ struct AccumPass {
 int accum_check(const pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view);
 // The same for an accumulator over a ray buffer (pt_accum_create_rays*): the flags a ray render and an accumulator
 // both take, the parameters, the kernels.  *stand_in: the camera the passes are enqueued with -- at the origin, it
-// carries the image size alone.
-int accum_check_rays(const pt_ctx* c, const pt_params* p, pt_camera* stand_in);
+// carries the image size alone.  (points: an accumulator over a point buffer, pt_accum_create_points* -- the same
+// checks under its own name)
+int accum_check_rays(const pt_ctx* c, const pt_params* p, pt_camera* stand_in, bool points = false);
 // Classifies the accumulator's own ray copy (device, width * height rays) and refuses it unless every ray is regular:
 // an invalid ray with its lowest pixel named, irregular rays with their count.  Blocking.
-int accum_classify_rays(pt_ctx* c, const pt_params* p, const float* d_rays, void* stream);
+// (points: the copy holds points {p, n}, classified as pt_render_irradiance classifies them)
+int accum_classify_rays(pt_ctx* c, const pt_params* p, const float* d_rays, void* stream, bool points = false);
 // p->spp more samples of every pixel (of every active pixel), blocking; d_out (device, W*H*3) may be null.
 int accum_pass(pt_ctx* c, const pt_params* p, const pt_camera* cam, const pt_view* view, const AccumPass& acc, float* d_out,
                void* stream, pt_stats* stats);

@@ -9,7 +9,7 @@ Morton order first.
 The image orientation is the pinhole camera's: a set built at the camera's pose shows the scene the way
 Renderer.render does (film x and y grow against the view's right and up, as camera.h's film does).
 
-The point helpers (grid_points, triangle_points, feature_points) return (points, normals) the same way, the normals
+The point helpers (grid_points, triangle_points, chart_points, feature_points) return (points, normals) the same way, the normals
 normalised in float32 and the points lifted `lift` along them: an irradiance render uses a point as given, and one
 lying in its own surface is black.
 """
@@ -150,6 +150,53 @@ def triangle_points(arrays, tri, b1, b2, lift=1e-3):
     p = v0 + b1[:, None] * (v1 - v0) + b2[:, None] * (v2 - v0)
     nrm = np.stack([t["nx"], t["ny"], t["nz"]], axis=1)
     return _lifted(p, nrm, lift)
+
+
+def chart_points(arrays, tris, uvs, W, H, lift=1e-3):
+    """Texel points of a UV chart: "bake this lightmap".  tris: T triangle indices of Scene.arrays(); uvs: (T, 3, 2),
+    the chart coordinates of v0, v1, v2 in [0, 1]^2.  Texel (x, y) has centre c = ((x + 0.5) / W, (y + 0.5) / H); for
+    triangle k in list order with chart corners a, b, cc, all in float64:
+        e = b - a;  f = cc - a;  g = c - a;  det = e.x*f.y - e.y*f.x            (det == 0: the triangle is skipped)
+        b1 = (g.x*f.y - g.y*f.x) / det;  b2 = (e.x*g.y - e.y*g.x) / det
+    and the triangle covers the texel iff b1 >= 0, b2 >= 0 and b1 + b2 <= 1; the first covering triangle wins.
+    Returns (points, normals, tri_of_texel, covered) in scanline order: a covered texel's point is
+    triangle_points(arrays, tri, b1, b2, lift)'s; an uncovered one gets feature_points' dummy (the origin, normal +y),
+    tri_of_texel = -1 and covered = False.  ~covered is the mask for Accumulator.freeze at 0 samples."""
+    tris = np.atleast_1d(np.asarray(tris, dtype=np.int64))
+    uvs = np.asarray(uvs, dtype=np.float64)
+    if uvs.shape != (tris.shape[0], 3, 2):
+        raise ValueError("rays: uvs must have shape (%d, 3, 2)" % tris.shape[0])
+    W, H = int(W), int(H)
+    if W <= 0 or H <= 0:
+        raise ValueError("rays: bad image size %dx%d" % (W, H))
+    # (the centres as defined, one division each: _film's -0.5 and back is not exact below 0.25)
+    cx = np.tile((np.arange(W, dtype=np.float64) + 0.5) / W, H)
+    cy = np.repeat((np.arange(H, dtype=np.float64) + 0.5) / H, W)
+    n = cx.shape[0]
+    which = np.full(n, -1, dtype=np.int64)   # position in `tris` of the texel's triangle
+    b1 = np.zeros(n, dtype=np.float64)
+    b2 = np.zeros(n, dtype=np.float64)
+    for k in range(tris.shape[0]):
+        a, b, cc = uvs[k]
+        ex, ey = b[0] - a[0], b[1] - a[1]
+        fx, fy = cc[0] - a[0], cc[1] - a[1]
+        det = ex * fy - ey * fx
+        if det == 0:
+            continue
+        gx, gy = cx - a[0], cy - a[1]
+        t1 = (gx * fy - gy * fx) / det
+        t2 = (ex * gy - ey * gx) / det
+        take = (which < 0) & (t1 >= 0) & (t2 >= 0) & (t1 + t2 <= 1)
+        which[take] = k
+        b1[take] = t1[take]
+        b2[take] = t2[take]
+    covered = which >= 0
+    p = np.zeros((n, 3), dtype=F)
+    nrm = np.tile(np.array([0.0, 1.0, 0.0], dtype=F), (n, 1))
+    if covered.any():
+        p[covered], nrm[covered] = triangle_points(arrays, tris[which[covered]], b1[covered], b2[covered], lift)
+    tri_of_texel = np.where(covered, tris[np.maximum(which, 0)] if tris.shape[0] else -1, -1).astype(np.int64)
+    return p, nrm, tri_of_texel, covered
 
 
 def feature_points(features, lift=1e-3):

@@ -901,9 +901,11 @@ int pt_rays_classify_device(pt_ctx* ctx, uint32_t n, const float* d_rays, void* 
  * pt_render_rays*'s.  The host call stages the points through the context's ray staging buffer.  pt_stats keeps its
  * meanings; rays_reference counts the trace() calls of the loop above.
  *
- * Out of scope: accumulators, noise estimates, adaptive sampling, feature buffers, checkpoints and sessions over a
- * point buffer; pt_render_group / pt_render_multi; other distributions (uniform sphere, cones); passes from the
- * command line (pt_cli --irradiance renders one shot). */
+ * Accumulators over a point buffer (passes, noise estimates, the convergence stop, adaptive sampling, masked texels):
+ * pt_accum_create_points*, below the ray accumulators.
+ *
+ * Out of scope: feature buffers, checkpoints and sessions over a point buffer; pt_render_group / pt_render_multi;
+ * other distributions (uniform sphere, cones); passes from the command line (pt_cli --irradiance renders one shot). */
 int pt_render_irradiance_device(pt_ctx* ctx, const pt_params* params, const float* d_points, float* d_out, void* stream,
                                 pt_stats* stats);
 int pt_render_irradiance(pt_ctx* ctx, const pt_params* params, const float* points /* host */, float* out_rgb /* host */,
@@ -1097,6 +1099,56 @@ pt_accum* pt_accum_create_rays(pt_ctx* ctx, const pt_params* params, const float
 int pt_accum_has_rays(const pt_accum* acc);   /* 1 / 0; 0 for NULL */
 int pt_render_features_rays_device(pt_ctx* ctx, const pt_params* params, const float* d_rays, pt_feature* d_feat, void* stream);
 int pt_render_features_rays(pt_ctx* ctx, const pt_params* params, const float* rays /* host */, pt_feature* feat /* host */);
+
+/* ------------------------------------------------------------- accumulators over caller-supplied points
+ * The progressive layer over a point buffer (see "irradiance renders at caller-supplied points" above for the buffer,
+ * its indexing, the arithmetic of a sample and the point classes): a lightmap or probe bake in passes, with a preview
+ * after each, noise estimates, a convergence stop, adaptive sampling and masked texels.
+ *
+ * points holds width * height * 6 floats, {p.xyz, n.xyz} per pixel, indexed in params->pixel_order as for
+ * pt_render_irradiance*; a device buffer must be 8-byte aligned.  Ownership is the ray accumulator's: create copies
+ * the whole buffer into device memory the accumulator owns (24 B per pixel, freed by pt_accum_destroy), so the
+ * caller's buffer may be freed or overwritten once create has returned.
+ *
+ * Arithmetic (a definition): pixel (x, y) after n samples holds the f64 mean of pt_render_irradiance's loop,
+ *     rng = curand_init(seed, morton(x, y), 0)
+ *     for k = 1..n:  u1 = uniform(rng); u2 = uniform(rng);  d = cosineWeightedRay(n, u1, u2)
+ *                    L = integrator(p, d, rng);  m = m*(k-1)/k + L/k
+ * so pt_accum_add in any split of passes equals pt_render_irradiance of the same total in every bit, and a pixel
+ * frozen at k samples holds the k-sample value whatever is frozen around it.  Every unit of a pass is a lens unit: its
+ * ray is formed per sample, there is no primary-hit memo, and a split unit's replay skips the pair of every earlier
+ * sample.  rays_reference of a pass counts the loop's trace() calls for that pass's samples; summed over the passes it
+ * is the one-shot render's.
+ *
+ * Order of the checks at create, pt_accum_create_rays': a null argument; asynchronous renders in flight; the flags; the
+ * parameters; the kernels; the device buffer's alignment; then all width * height points (not only the shard's) are
+ * classified, once, on the accumulator's own copy.  Every refusal is PT_E_INVALID with *err set and NULL returned:
+ *     flags      only 0, PT_FLAG_NO_DEAD_PATH_SKIP and PT_FLAG_NO_PRIMARY_CACHE (legal, and it changes nothing, as in
+ *                the one-shot render); the jitter, counting and reference flags and unknown bits are refused
+ *     kernels    a context with a non-default PT_WF_MIN_WAVES / PT_HEAD_MIN_WAVES, or integrator 1 with PT_HEAD_WF=0
+ *     invalid    a buffer with an invalid point, the message naming the lowest such pixel as pt_render_irradiance does
+ *     irregular  a buffer with an irregular point (beyond 64 scene extents): accumulation runs on the wavefront
+ *                kernels only and there is never a silent fall-back; the message gives the count and says that
+ *                pt_render_irradiance takes such a buffer
+ * Everything else works unchanged on a point accumulator: pt_accum_add, _samples, _read, _freeze, _counts, _active,
+ * _add_until, _add_adaptive, pt_noise_* (pt_noise_variance*, pt_noise_freeze included) and pt_accum_destroy.  Shards,
+ * tile sizes, Morton order, empty shards and split units behave as documented for camera accumulators.  Once a pixel
+ * is frozen, passes run over the active list with a set-up kernel that marks every unit a lens unit.
+ * pt_accum_view reports has_view = 0.  pt_accum_has_points is 1 for a point accumulator, 0 for any other and for NULL;
+ * pt_accum_has_rays is 0 for a point accumulator.
+ *
+ * MASKED TEXELS (a lightmap texel that belongs to no chart): pt_accum_freeze at 0 samples is the mask, as for ray
+ * accumulators.  Such a texel stays at mean 0 and count 0 and is never sampled.  Its point must still be valid and
+ * regular: the caller pads it (cudapathtracer_amd.rays.chart_points pads with the origin and the normal +y).
+ *
+ * pt_accum_save and pt_session_save refuse a point accumulator with PT_E_INVALID: both formats hold a camera, not a
+ * point buffer.
+ *
+ * Out of scope: sessions and checkpoints over a point buffer; feature buffers over points; pt_render_group /
+ * pt_render_multi; passes from the command line (pt_cli --irradiance renders one shot). */
+pt_accum* pt_accum_create_points_device(pt_ctx* ctx, const pt_params* params, const float* d_points, void* stream, int* err);
+pt_accum* pt_accum_create_points(pt_ctx* ctx, const pt_params* params, const float* points /* host */, int* err);
+int pt_accum_has_points(const pt_accum* acc);   /* 1 / 0; 0 for NULL */
 
 /* ------------------------------------------------- temporal reprojection: keep the samples when the camera moves
  * An accumulator keeps its camera and view for life, so a moving camera starts from 1-spp noise every frame.  Every

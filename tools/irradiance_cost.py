@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Cost of an irradiance render: the stand-in at 1920x1080, 16 spp, both integrators.
 
-    python tools/irradiance_cost.py [--spp 16] [--rounds 5] [--integrators 0,1] [--out FILE.json]
+    python tools/irradiance_cost.py [--spp 16] [--rounds 5] [--integrators 0,1] [--accum [--pass-spp 4]] [--out FILE.json]
 
 The points are feature_points of the stand-in's camera: what it sees, lifted 1e-3.  Alternated in one run, medians over
 the rounds, per integrator:
@@ -12,6 +12,17 @@ the rounds, per integrator:
 and once:
   * classify_points_device of the buffer on its own against a device-to-device copy of its 24 B per point (events around
     the blocking calls).
+With --accum, after those (accumulators over points, pt_accum_create_points*), per integrator:
+  * a --pass-spp accumulating pass of a point accumulator against render_irradiance_device at --pass-spp over the same
+    points (the existing one-shot path: the same samples, without the stored mean and stream);
+  * the same pass over the active list, with about 50% and about 10% of the pixels active (the others masked at 0
+    samples), against the same fractions of a camera accumulator with radius = 0.05 -- the other source whose every
+    unit is a lens unit;
+  * the add_adaptive loop over the points (--adaptive-tol, --adaptive-cap, passes of --pass-spp, the camera's misses
+    masked at 0 samples): samples_total over texels x cap, the saving against uniform sampling to the cap;
+and once:
+  * the create call against accumulator_rays_device over the same buffer (host wall time of the blocking calls: both
+    copy and classify 24 B per pixel).
 Prints one JSON line per block and one of ratios, each ratio with the smallest and largest per-round ratio beside the
 ratio of the medians.  --out also keeps the lines in a file.
 """
@@ -21,6 +32,7 @@ import os
 import statistics
 import sys
 import tempfile
+import time
 
 import numpy as np
 import torch
@@ -37,6 +49,82 @@ def _ratio(num, den):
     return dict(of_medians=statistics.median(num) / statistics.median(den), min=min(per_round), max=max(per_round))
 
 
+def accum_blocks(r, a, lens_cam, buf, miss, out, w, h):
+    """The --accum blocks: lines of passes, active-list passes, the adaptive loop and the create call, and their ratios."""
+    n = w * h
+    lines, ratios = [], {}
+    for integrator in [int(v) for v in a.integrators.split(",")]:
+        make = {"points": lambda: r.accumulator_points_device(buf.data_ptr(), w, h, 3, integrator, 1234),
+                "lens": lambda: r.accumulator(lens_cam, w, h, 3, integrator, 1234)}
+        rs = np.random.RandomState(5)
+        for label, active in (("all", 1.0), ("half", 0.5), ("tenth", 0.1)):
+            mask = rs.uniform(size=(h, w)) >= active             # the masked pixels
+            kinds = ["points", "one_shot"] if label == "all" else ["lens", "points"]
+            accs = {k: make[k]() for k in kinds if k != "one_shot"}
+            try:
+                for acc in accs.values():
+                    if mask.any():
+                        acc.freeze(mask)
+                    acc.add(1)                                   # warm-up: buffers, the active list
+                r.render_irradiance_device(buf.data_ptr(), out.data_ptr(), w, h, 1, 3, integrator, 1234)
+                t = {k: dict(seconds=[], kernel_ms=[]) for k in kinds}
+                units, traced = {}, {}
+                for _ in range(a.rounds):
+                    for k in kinds:                              # alternated
+                        if k == "one_shot":
+                            st = r.render_irradiance_device(buf.data_ptr(), out.data_ptr(), w, h, a.pass_spp, 3, integrator, 1234)
+                        else:
+                            st = accs[k].add(a.pass_spp)
+                        t[k]["seconds"].append(st["seconds"])
+                        t[k]["kernel_ms"].append(st["kernel_ms"])
+                        units[k] = st["work_units"]
+                        traced[k] = st["rays_traced"]
+            finally:
+                for acc in accs.values():
+                    acc.close()
+            line = dict(block="accum_pass_" + label, integrator=integrator, width=w, height=h, pass_spp=a.pass_spp,
+                        rounds=a.rounds, active_pixels=int(n - mask.sum()))
+            for k in kinds:
+                sec, kms = statistics.median(t[k]["seconds"]), statistics.median(t[k]["kernel_ms"])
+                line[k] = dict(seconds=sec, kernel_ms=kms, setup_ms=sec * 1e3 - kms, seconds_min=min(t[k]["seconds"]),
+                               seconds_max=max(t[k]["seconds"]), work_units=units[k], rays_traced=traced[k])
+            lines.append(line)
+            ratios["i%d_accum_pass_%s_points_over_%s" % (integrator, label, kinds[1] if label == "all" else "lens")] = \
+                _ratio(t["points"]["seconds"], t["one_shot" if label == "all" else "lens"]["seconds"])
+        # ---- the adaptive loop: what a bake saves against uniform sampling to the cap
+        texels = int(n - miss.sum())
+        with make["points"]() as acc:
+            if miss.any():
+                acc.freeze(miss.reshape(h, w))                   # (the camera's misses belong to no surface: masked)
+            t0 = time.perf_counter()
+            res = acc.add_adaptive(a.pass_spp, a.adaptive_cap, tol=a.adaptive_tol, quantile=1.0, min_batches=2)
+            wall = time.perf_counter() - t0
+        lines.append(dict(block="adaptive", integrator=integrator, width=w, height=h, pass_spp=a.pass_spp, cap=a.adaptive_cap,
+                          tol=a.adaptive_tol, texels=texels, masked=int(miss.sum()), passes=res["passes"],
+                          stopped_converged=res["stopped_converged"], active=res["active"], samples_total=res["samples_total"],
+                          fraction_of_uniform=res["samples_total"] / float(texels * a.adaptive_cap), wall_seconds=wall))
+    # ---- the create call, against a ray accumulator over the same bytes
+    make = {"points": lambda: r.accumulator_points_device(buf.data_ptr(), w, h, 3, 0, 1234),
+            "rays": lambda: r.accumulator_rays_device(buf.data_ptr(), w, h, 3, 0, 1234)}
+    t_create = {k: [] for k in make}
+    for k in make:
+        make[k]().close()
+    for _ in range(max(a.rounds, 5)):
+        for k in make:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            acc = make[k]()
+            t_create[k].append((time.perf_counter() - t0) * 1e3)
+            acc.close()
+    lines.append(dict(block="create", width=w, height=h, bytes=n * 24,
+                      create_points_ms=statistics.median(t_create["points"]), create_points_ms_min=min(t_create["points"]),
+                      create_rays_ms=statistics.median(t_create["rays"]), create_rays_ms_min=min(t_create["rays"]),
+                      note="host wall time of the blocking create calls over the same buffer, read as points and as rays"))
+    ratios["create_points_over_rays"] = _ratio(t_create["points"], t_create["rays"])
+    lines.append(dict(ratios=ratios))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--spp", type=int, default=16)
@@ -45,6 +133,10 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--cache-dir", default=os.path.join(tempfile.gettempdir(), "pt_bench_scene"))
+    ap.add_argument("--accum", action="store_true")
+    ap.add_argument("--pass-spp", type=int, default=4)
+    ap.add_argument("--adaptive-tol", type=float, default=0.2)
+    ap.add_argument("--adaptive-cap", type=int, default=32)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     p = os.path.join(a.cache_dir, "models", "sponza_standin.obj")
@@ -115,7 +207,9 @@ def main():
                           note="classify_call_ms: events around the blocking call (memsets, kernel, read-back, host sync); "
                                "copy_ms: a device-to-device copy of the same 24 B per point"))
         ratios["classify_over_copy"] = _ratio(t_cls, t_copy)
-    lines.append(dict(ratios=ratios))
+        lines.append(dict(ratios=ratios))
+        if a.accum:
+            lines.extend(accum_blocks(r, a, lens_cam, buf, miss, out, w, h))
     for line in lines:
         print(json.dumps(line))
     if a.out:
