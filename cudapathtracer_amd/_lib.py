@@ -114,6 +114,13 @@ class TemporalParams(C.Structure):   # pt_temporal_params, 16 B
     _fields_ = [("max_history", C.c_int32), ("normal_min", C.c_float), ("plane_tol", C.c_float), ("flags", C.c_uint32)]
 
 
+PT_LIGHTMAP_NO_ALBEDO = 0x1   # pt_lightmap_params.flags: the lightmap value alone, not albedo times it
+
+
+class LightmapParams(C.Structure):   # pt_lightmap_params, 16 B
+    _fields_ = [("fill", C.c_float * 3), ("flags", C.c_uint32)]
+
+
 class NoiseParams(C.Structure):
     _fields_ = [("tol", C.c_float), ("y_floor", C.c_float)]
 
@@ -295,6 +302,13 @@ SIGNATURES = {
     "pt_temporal_frames": (C.c_int, [C.c_void_p]),
     "pt_temporal_reset": (C.c_int, [C.c_void_p]),
     "pt_temporal_destroy": (None, [C.c_void_p]),
+    "pt_lightmap_dilate_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
+    "pt_lightmap_dilate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pt_lightmap_shade_device": (C.c_int, [C.c_void_p, C.POINTER(LightmapParams), C.c_uint32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pt_lightmap_shade": (C.c_int, [C.c_void_p, C.POINTER(LightmapParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_int, C.c_int, C.c_void_p]),
     "pt_destroy": (None, [C.c_void_p]),
 }
 

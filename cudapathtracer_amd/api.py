@@ -783,6 +783,77 @@ class Renderer:
         return dict(regular=int(rc.regular), irregular=int(rc.irregular), invalid=int(rc.invalid),
                     first_invalid=int(rc.first_invalid))
 
+    def lightmap_dilate(self, img, covered, radius, return_src=False):
+        """The gutter fill that ends a bake (pt_lightmap_dilate): every uncovered texel of the (H, W, 3) float32 lightmap
+        `img` takes the value of the nearest covered one within `radius` (0..16) texels in x and in y -- smallest
+        i*i + j*j, ties to the smaller j, then the smaller i; no wrap-around -- bit for bit; covered texels, and
+        uncovered ones with nothing in reach, keep theirs.  covered: (H, W), non-zero = covered (rays.chart_points'
+        `covered`).  Returns the filled lightmap; with return_src also the (H, W) int32 index y*W + x each texel was
+        taken from (its own for a covered one, -1 where nothing was in reach)."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("lightmap_dilate: the lightmap must have shape (H, W, 3)")
+        h, w = img.shape[:2]
+        cov = np.ascontiguousarray(np.asarray(covered) != 0, dtype=np.uint8)
+        if cov.size != w * h:
+            raise ValueError("lightmap_dilate: lightmap and covered differ in size")
+        out = np.empty_like(img)
+        src = np.empty((h, w), dtype=np.int32) if return_src else None
+        L.check(L.lib().pt_lightmap_dilate(self._h, w, h, int(radius), img.ctypes.data, cov.ctypes.data, out.ctypes.data,
+                                           None if src is None else src.ctypes.data))
+        return (out, src) if return_src else out
+
+    def lightmap_dilate_device(self, d_in_ptr, d_covered_ptr, d_out_ptr, width, height, radius, d_src_ptr=None,
+                               stream_ptr=None):
+        """pt_lightmap_dilate_device on raw device pointers: W*H*3 float32 in and out (d_out_ptr may equal d_in_ptr), W*H
+        covered bytes, optionally W*H int32 sources; blocking."""
+        L.check(L.lib().pt_lightmap_dilate_device(self._h, int(width), int(height), int(radius),
+                                                  None if not d_in_ptr else C.c_void_p(int(d_in_ptr)),
+                                                  None if not d_covered_ptr else C.c_void_p(int(d_covered_ptr)),
+                                                  None if not d_out_ptr else C.c_void_p(int(d_out_ptr)),
+                                                  None if not d_src_ptr else C.c_void_p(int(d_src_ptr)),
+                                                  None if stream_ptr is None else C.c_void_p(int(stream_ptr))))
+
+    @staticmethod
+    def lightmap_params(fill=(0.0, 0.0, 0.0), flags=0):
+        lp = L.LightmapParams()
+        lp.fill[0], lp.fill[1], lp.fill[2] = (float(v) for v in fill)
+        lp.flags = int(flags)
+        return lp
+
+    def lightmap_shade(self, features, tri_uv, lightmap, fill=(0.0, 0.0, 0.0), flags=0):
+        """A lightmapped view (pt_lightmap_shade): the colour of every record of a feature buffer (features(),
+        features_rays(): any view, jitter or ray set) under the (H, W, 3) float32 `lightmap`, looked up bilinearly at the
+        chart coordinates of the record's hit and multiplied by its albedo (PT_LIGHTMAP_NO_ALBEDO in flags: the value
+        alone).  tri_uv: (num_tris, 6) float32, the chart coordinates of v0, v1, v2 of every original triangle, a NaN
+        row for a triangle of no chart (rays.chart_uv_table).  Misses, emitters, spheres and triangles of no chart get
+        `fill`.  Returns float32 of the features' shape + (3,)."""
+        feat = np.ascontiguousarray(features, dtype=FEATURE)
+        uv = np.ascontiguousarray(tri_uv, dtype=np.float32)
+        lm = np.ascontiguousarray(lightmap, dtype=np.float32)
+        if lm.ndim != 3 or lm.shape[2] != 3:
+            raise ValueError("lightmap_shade: the lightmap must have shape (H, W, 3)")
+        nt = int(self._scene_view.num_tris)
+        if uv.size != nt * 6:
+            raise ValueError("lightmap_shade: tri_uv must have shape (%d, 6)" % nt)
+        lp = self.lightmap_params(fill, flags)
+        out = np.zeros(feat.shape + (3,), dtype=np.float32)
+        L.check(L.lib().pt_lightmap_shade(self._h, C.byref(lp), feat.size, feat.ctypes.data, uv.ctypes.data, lm.ctypes.data,
+                                          lm.shape[1], lm.shape[0], out.ctypes.data))
+        return out
+
+    def lightmap_shade_device(self, d_feat_ptr, n, d_tri_uv_ptr, d_map_ptr, map_w, map_h, d_out_ptr, fill=(0.0, 0.0, 0.0),
+                              flags=0, stream_ptr=None):
+        """pt_lightmap_shade_device on raw device pointers: n 48-byte feature records (16-byte aligned), num_tris * 6
+        float32 chart coordinates, map_w * map_h * 3 float32 lightmap, n * 3 float32 out; blocking."""
+        lp = self.lightmap_params(fill, flags)
+        L.check(L.lib().pt_lightmap_shade_device(self._h, C.byref(lp), int(n),
+                                                 None if not d_feat_ptr else C.c_void_p(int(d_feat_ptr)),
+                                                 None if not d_tri_uv_ptr else C.c_void_p(int(d_tri_uv_ptr)),
+                                                 None if not d_map_ptr else C.c_void_p(int(d_map_ptr)), int(map_w), int(map_h),
+                                                 None if not d_out_ptr else C.c_void_p(int(d_out_ptr)),
+                                                 None if stream_ptr is None else C.c_void_p(int(stream_ptr))))
+
 
 def accum_file_info(path):
     """Header of a checkpoint file (pt_accum_file_info, host-only): dict of params (spp = 0), camera,

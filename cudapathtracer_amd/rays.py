@@ -210,3 +210,43 @@ def feature_points(features, lift=1e-3):
     p, n = _lifted(pos, nrm, lift)
     p[miss] = 0.0
     return p, n, miss
+
+
+def chart_uv_table(num_tris, tris, uvs):
+    """The chart coordinates Renderer.lightmap_shade looks a lightmap up with: a (num_tris, 6) float32 table whose row t
+    holds (ua.x, ua.y, ub.x, ub.y, uc.x, uc.y), the chart coordinates of v0, v1, v2 of original triangle t, and NaN
+    for every triangle of no chart.  tris, uvs: chart_points' arguments -- T triangle indices and their (T, 3, 2)
+    coordinates; where a triangle is listed twice the first entry holds, as in chart_points."""
+    tris = np.atleast_1d(np.asarray(tris, dtype=np.int64))
+    uvs = np.asarray(uvs, dtype=np.float64)
+    if uvs.shape != (tris.shape[0], 3, 2):
+        raise ValueError("rays: uvs must have shape (%d, 3, 2)" % tris.shape[0])
+    num_tris = int(num_tris)
+    if tris.shape[0] and (tris.min() < 0 or tris.max() >= num_tris):
+        raise ValueError("rays: a chart triangle is outside 0..%d" % (num_tris - 1))
+    table = np.full((num_tris, 6), np.nan, dtype=F)
+    for k in range(tris.shape[0] - 1, -1, -1):   # (backwards: the first entry of a triangle is written last)
+        table[tris[k]] = uvs[k].reshape(6)
+    return table
+
+
+def point_features(points, normals, tri_of_texel):
+    """The feature records of a bake's texels (chart_points' points, normals and tri_of_texel), for the a-trous filters
+    (Renderer.denoise, denoise_guided) in texture space before the dilation: position and normal as given, albedo 1 and
+    depth 1 (so demodulation changes nothing and the depth weight measures scene units), prim the texel's triangle and
+    -1 where it is uncovered (the filters pass such a texel through and let it contribute to no neighbour).  Returns a
+    FEATURE array shaped like tri_of_texel; reshape it to (H, W) for the filters."""
+    tri = np.asarray(tri_of_texel, dtype=np.int64)
+    p = np.ascontiguousarray(points, dtype=F).reshape(-1, 3)
+    n = np.ascontiguousarray(normals, dtype=F).reshape(-1, 3)
+    if p.shape[0] != tri.size or n.shape[0] != tri.size:
+        raise ValueError("rays: points, normals and tri_of_texel differ in length")
+    if tri.size and tri.max() >= 2 ** 30:
+        raise ValueError("rays: a triangle id does not fit a feature record")
+    f = np.zeros(tri.size, dtype=api.FEATURE)
+    f["albedo"] = F(1.0)
+    f["depth"] = F(1.0)
+    f["normal"] = n
+    f["position"] = p
+    f["prim"] = np.where(tri.reshape(-1) < 0, -1, tri.reshape(-1)).astype(np.int32)
+    return f.reshape(tri.shape)

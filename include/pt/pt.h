@@ -1241,6 +1241,69 @@ int pt_temporal_frames(const pt_temporal* t);
 int pt_temporal_reset(pt_temporal* t);
 void pt_temporal_destroy(pt_temporal* t);
 
+/* ------------------------------------------------- lightmap finishing: the gutter fill and the lightmapped view
+ * A bake over a UV chart (pt_render_irradiance*, pt_accum_create_points*) leaves 0 in every texel of no chart.  A
+ * lightmap is sampled bilinearly, so along every chart border the sampler would mix covered texels with those zeros: a
+ * dark seam.  pt_lightmap_dilate* is the dilation pass that ends a bake; pt_lightmap_shade* shows a bake on the
+ * geometry from any view, one lookup per pixel of a feature buffer (hand-written gfx950 kernels, pt_lightmap.hip; no
+ * render kernel is touched).  All four block, and are refused while asynchronous renders are in flight.
+ *
+ * pt_lightmap_dilate*: in and out are width * height * 3 fp32 in scanline order (a lightmap is a texture: Morton order
+ * is not offered), covered is width * height bytes, non-zero = covered (rays.chart_points' `covered`), src (may be
+ * NULL) width * height int32.  The rule is in integers, so every implementation of it agrees exactly:
+ *   a covered texel keeps its input bit for bit, and src is its own index y*W + x;
+ *   an uncovered texel (x, y) looks at the covered texels (x+i, y+j) with |i| <= radius, |j| <= radius, inside the
+ *     image (no wrap-around), and takes the one with the smallest i*i + j*j, ties to the smaller j, then to the
+ *     smaller i: out is that texel's input bit for bit, src is (y+j)*W + (x+i);
+ *   if there is none, out is the texel's own input bit for bit and src is -1.
+ * Only covered texels are ever read as sources and they never change, so out may equal in (the same result);
+ * radius = 0 is a copy.  PT_E_INVALID, naming the argument: a null ctx, in, covered or out; a width or height outside
+ * 1..65535, or more than 2^31 - 1 texels; a radius outside 0..16; _device: an in, out or src that is not 4-byte
+ * aligned.  The host variant stages through device buffers of its own.
+ *
+ * pt_lightmap_shade*: one output (3 fp32) per feature record, in the records' own order -- any pt_render_features*
+ * buffer works (view, jitter and rays variants included), so no pixel order appears here.  tri_uv[6*t ..] holds the
+ * chart coordinates ua, ub, uc (x then y each) of v0, v1, v2 of ORIGINAL triangle t, the id a feature's prim carries;
+ * a NaN in its first float means "this triangle has no chart" (num_tris rows; may be NULL for a scene without
+ * triangles).  map is map_w * map_h * 3 fp32 in scanline order.  A record gets `fill` when prim < 0, or prim &
+ * PT_FEATURE_EMISSIVE, or prim >= num_tris (a sphere), or its triangle has no chart, or det below is 0 or not finite,
+ * or s or t below is not finite.  For every other record, all in f32, every operation rounded on its own, no
+ * contraction, IEEE division; clamp(v, lo, hi) is `v < lo ? lo : (v > hi ? hi : v)`, so a NaN stays one; v0, v1, v2
+ * are the scene's f32 vertices of triangle prim:
+ *   e1 = v1 - v0;  e2 = v2 - v0;  g = position - v0                               (componentwise)
+ *   dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z
+ *   d11 = dot(e1,e1);  d12 = dot(e1,e2);  d22 = dot(e2,e2);  g1 = dot(g,e1);  g2 = dot(g,e2)
+ *   det = d11*d22 - d12*d12
+ *   b1 = clamp((d22*g1 - d12*g2) / det, 0, 1);   b2 = clamp((d11*g2 - d12*g1) / det, 0, 1)
+ *   u = (ua.x + b1*(ub.x - ua.x)) + b2*(uc.x - ua.x);   v likewise with .y
+ *   s = u*(float)map_w - 0.5f;  t = v*(float)map_h - 0.5f        (not finite: fill);  then s = clamp(s, -1, (float)map_w),
+ *                                                                 t = clamp(t, -1, (float)map_h)
+ *   x0 = floorf(s);  fx = s - x0;  texel columns (int)x0 and (int)x0 + 1, each clamped to [0, map_w - 1];  rows likewise
+ *   per channel, L00 = map(column 0, row 0 of the four), L10 the next column, L01 the next row:
+ *     top = L00 + fx*(L10 - L00);  bot = L01 + fx*(L11 - L01);  val = top + fy*(bot - top)
+ *   out = albedo * val                                            (val alone with PT_LIGHTMAP_NO_ALBEDO)
+ * The lerp form is deliberate: a constant lightmap is reproduced exactly.  Every material here is Lambertian, so a
+ * texel's outgoing radiance is its albedo times the baked E/pi; emitters get `fill` (composite them from a 0-bounce
+ * render).  The triangles' vertices are read from the context's own original-order records (v0, e1, e2: the same f32
+ * subtractions), nothing is uploaded.  PT_E_INVALID, naming the argument: a null ctx or params, unknown flags, a map_w
+ * or map_h outside 1..65535, a null map, a null tri_uv (unless the scene has no triangles), a null feat or out (unless
+ * n = 0); _device: a d_feat that is not 16-byte aligned, a d_tri_uv, d_map or d_out that is not 4-byte aligned.
+ * n = 0 is PT_OK and touches nothing. */
+#define PT_LIGHTMAP_NO_ALBEDO 0x1u
+typedef struct {
+    float fill[3];     /* the colour of a record without a lightmap value (copied bit for bit) */
+    uint32_t flags;    /* PT_LIGHTMAP_NO_ALBEDO 0x1 */
+} pt_lightmap_params;   /* 16 B */
+int pt_lightmap_dilate_device(pt_ctx* ctx, int width, int height, int radius, const float* d_in, const uint8_t* d_covered,
+                              float* d_out, int32_t* d_src /* or NULL */, void* stream);
+int pt_lightmap_dilate(pt_ctx* ctx, int width, int height, int radius, const float* in, const uint8_t* covered, float* out,
+                       int32_t* src /* or NULL */);
+int pt_lightmap_shade_device(pt_ctx* ctx, const pt_lightmap_params* lp, uint32_t n, const pt_feature* d_feat,
+                             const float* d_tri_uv /* num_tris*6 */, const float* d_map, int map_w, int map_h,
+                             float* d_out /* n*3 */, void* stream);
+int pt_lightmap_shade(pt_ctx* ctx, const pt_lightmap_params* lp, uint32_t n, const pt_feature* feat, const float* tri_uv,
+                      const float* map, int map_w, int map_h, float* out);
+
 /* ----------------------------------------------------------- one process, N GPUs
  * A group of contexts on distinct devices with one RCCL communicator per device
  * (ncclCommInitAll).  pt_render_group renders shard i of N on context i -- image tiles dealt
